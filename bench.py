@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X stable-fluids hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,12 +10,17 @@ grid (BASELINE.json metric: Mcells/s per vel_step+dens_step, 20 Jacobi iteration
 workload is BASELINE.json configs[1]: 256^3 fp32, K = 20. For N > 1 the workload is configs[3]: the
 1024^3 fp32 grid, slab-decomposed along k, one slab per GPU, RCCL halo exchange ("scaling": "strong" —
 the grid is the same for every N; north_star's target is >= 6x at 8 GPUs on it). After the distributed
-phase rank 0 times the SAME grid on its own GPU alone for a few steps, so the line carries an in-run
-one-GPU denominator (`single_gpu`) and `speedup`. `--weak` keeps ~256^3 cells per GPU instead
+phase rank 0 times the SAME grid on its own GPU alone for a few steps (--full only), so the line carries an
+in-run one-GPU denominator (`single_gpu`) and `speedup`. `--weak` keeps ~256^3 cells per GPU instead
 (N_g = 320 / 408 / 512 for 2 / 4 / 8 GPUs, "scaling": "weak"). Inputs are the analytic fields of
 docs/SPEC.md §5, resident in HBM before the timed region starts.
 
-Rank 0 prints ONE JSON line. Besides the contract fields it carries
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps back to back and reports them
+(`value`, `ms_per_step` and what follows from them without further runs). `--dump-outputs DIR` writes u, v, w, dens
+as the last timed step left them (dump_outputs). `--full` adds the legs that take runs of their own:
+  step_times_ms           : per-step HIP-event times of a second loop of K steps (N = 1)
+  hbm_copy_gbps_same_run  : a device copy of 1 GiB in the same run
+  single_gpu, speedup     : N > 1, the one-GPU denominator described above
   roofline                : the dominant kernel (four fused Jacobi sweeps of lin_solve per launch) at 512^3 — the working set is far
                             beyond the 256 MiB Infinity Cache, so `achieved` is a statement about HBM — timed with
                             HIP events on the launch stream; `traffic` = counter-measured bytes per launch with its
@@ -23,6 +28,7 @@ Rank 0 prints ONE JSON line. Besides the contract fields it carries
   roofline_cache_resident : the same kernel on the benchmark grid (256^3: x, x0, x' of one field fit the Infinity
                             Cache, so the algorithmic rate can exceed the HBM peak — not an HBM measurement)
   cpu_baseline            : the serial CPU oracle (oracle/, "port") on the same workload, bounded sample
+  parity_in_run           : the device state after the cpu_baseline leg's steps, compared bit for bit with it
 The oracle is only the baseline/checker here, never the thing measured as `value`.
 """
 import argparse
@@ -40,6 +46,10 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0  # MI355X spec (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured float4 copy)
 WEAK_GRID = {1: 256, 2: 320, 4: 408, 8: 512}  # --weak: N_g^3 / gpus ~= 256^3, N_g divisible by gpus and by 4
 STRONG_GRID = 1024  # BASELINE.json configs[3]: the grid of every N > 1 run
+DUMP_FIELDS = ("u", "v", "w", "dens")  # what vel_step + dens_step hand back to their caller
+DUMP_BYTES = 64 << 20  # --dump-outputs: whole fields up to this many bytes in all, else a sample
+DUMP_SAMPLE = 1 << 20  # cells per field in the sample (fp64: 4 x 8 MB + 8 MB of indices)
+DUMP_SEED = 20240531
 
 
 def parse():
@@ -60,6 +70,12 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--local-slabs", type=int, default=1,
                     help="rehearsal: cut this rank's part into that many logical slabs on its one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: per-step event times, copy bandwidth, the one-GPU "
+                         "denominator of N > 1, the roofline legs, the CPU baseline and parity_in_run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write u, v, w, dens after the last timed step to DIR/<field>.npy (whole fields up to "
+                         f"{DUMP_BYTES >> 20} MB in all, else a fixed seeded sample of {DUMP_SAMPLE} cells per field)")
     return ap.parse_args()
 
 
@@ -177,6 +193,49 @@ def cpu_baseline(N, K, dtype, steps, dt, diff, visc):
                       f"(g++ -O2 -ffp-contract=off), {el:.1f} s", "host_cores_visible": os.cpu_count()}
 
 
+def dump_outputs(fs, N, dist, out_dir, batch=32):
+    """--dump-outputs: u, v, w and dens (shells included) as the last timed step left them, in the run's precision, as
+    DIR/<field>.npy. Whole (N+2)^3 fields when the four fit DUMP_BYTES; otherwise the same fixed, seeded sample of
+    DUMP_SAMPLE cells of every field, in ascending flat-index order, with the indices in DIR/sample_index.npy (float64,
+    exact). Every rank reads the cells of its output planes, `batch` planes at a time; rank 0 writes. Returns the
+    summary for the JSON line (rank 0) or None."""
+    from fluidsolvergpu_amd import dist as sfdist
+
+    S = N + 2
+    total = S ** 3
+    whole = len(DUMP_FIELDS) * total * np.dtype(fs.np_dtype).itemsize <= DUMP_BYTES
+    idx = None if whole else np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_SAMPLE, replace=False))
+    rank, world = (0, 1) if dist is None else (dist.get_rank(), dist.get_world_size())
+    ob, oe = sfdist.output_planes(N, rank, world)
+    local = {}
+    for name in DUMP_FIELDS:
+        parts = []
+        for b0 in range(ob, oe, batch):
+            b1 = min(b0 + batch, oe)
+            planes = fs.download_planes(name, b0, b1)
+            if idx is None:
+                parts.append(planes)
+            else:
+                lo, hi = np.searchsorted(idx, [b0 * S * S, b1 * S * S])
+                parts.append(planes.reshape(-1)[idx[lo:hi] - b0 * S * S])
+        local[name] = np.concatenate(parts)
+    gathered = [local]
+    if dist is not None:  # ranks own ascending plane ranges: concatenating in rank order keeps the global order
+        gathered = [None] * world if rank == 0 else None
+        dist.gather_object(local, gathered, dst=0)
+    if rank != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    for name in DUMP_FIELDS:
+        a = np.concatenate([g[name] for g in gathered])
+        assert a.shape == ((S, S, S) if whole else (DUMP_SAMPLE,)), (name, a.shape)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    if not whole:
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+    return {"fields": list(DUMP_FIELDS), "whole": whole, "cells_per_field": total if whole else DUMP_SAMPLE,
+            "seed": None if whole else DUMP_SEED}
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -246,6 +305,9 @@ def main():
     barrier()
     elapsed = sfdist.max_over_ranks(dist, time.perf_counter() - t0)
 
+    # what the timed path handed back after its last step, before anything else runs on the context
+    dumped = dump_outputs(fs, N, dist, args.dump_outputs) if args.dump_outputs else None
+
     # state sanity: finite, and the halo guard did not fire (sync would have raised)
     kb_o, ke_o = fs.owned_planes()
     probe = fs.download_planes("dens", kb_o, min(kb_o + 2, ke_o))
@@ -254,7 +316,7 @@ def main():
     # ---- per-step times (HIP events on the compute stream, one host sync per step): OUTSIDE the timed region above,
     # whose K steps run back to back as the contract asks; this second loop shows the spread the mean hides ----
     step_ms = []
-    if world == 1:
+    if args.full and world == 1:
         for _ in range(args.steps):
             fs.timer_start()
             step()
@@ -263,7 +325,8 @@ def main():
     # ---- parity in this very run: the state the cpu_baseline leg computes below (cpu_steps steps from the benchmark
     # inputs) computed by the device now, compared bit for bit once the oracle has it ----
     gpu_after = None
-    want_parity = world == 1 and not args.no_cpu_baseline and N <= 256 and os.environ.get("SF_BENCH_DRYRUN") != "1"
+    want_parity = (args.full and world == 1 and not args.no_cpu_baseline and N <= 256
+                   and os.environ.get("SF_BENCH_DRYRUN") != "1")
     if want_parity:
         upload_inputs(fs, N, dt)
         for _ in range(args.cpu_steps):
@@ -278,7 +341,6 @@ def main():
         value = cells * args.steps / elapsed / 1e6
         wsize = 4 if args.dtype == "f32" else 8
         step_bytes = cells * words_per_cell_step(K) * wsize
-        copy_gbps = fs.copy_bandwidth_gbps(1 << 30, 5)
         out = {
             "metric": ("Mcells/s per vel_step+dens_step (20 Jacobi iters) at 256^3; achieved HBM GB/s"
                        if (K == 20 and N == 256) else f"Mcells/s per vel_step+dens_step ({K} Jacobi iters) at {N}^3"),
@@ -302,9 +364,12 @@ def main():
                        "schedule": fs.schedule_info() if hasattr(fs, "schedule_info") else None},
             "achieved_hbm_gbps_step": step_bytes / (elapsed / args.steps) / 1e9 / world,
             "step_algorithmic_bytes_per_cell": words_per_cell_step(K) * wsize,
-            "hbm_copy_gbps_same_run": copy_gbps,
             "transport": fs.transport_info() if hasattr(fs, "transport_info") else None,
         }
+        if args.full:
+            out["hbm_copy_gbps_same_run"] = fs.copy_bandwidth_gbps(1 << 30, 5)
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if step_ms:
             out["step_times_ms"] = {"n": len(step_ms), "min": float(np.min(step_ms)), "median": float(np.median(step_ms)),
                                     "p90": float(np.percentile(step_ms, 90)), "mean": float(np.mean(step_ms)),
@@ -327,6 +392,10 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         dist = None
+    if not args.full:  # a plain run reports the timed steps only
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return
     if world > 1 and args.single_steps > 0:
         if rank == 0:
             try:

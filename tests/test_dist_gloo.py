@@ -148,9 +148,9 @@ def test_partition_arithmetic():
 
 @pytest.mark.parametrize("world,mode", [(2, "strong"), (4, "strong"), (2, "weak")])
 def test_bench_multirank_plumbing_dryrun(world, mode):
-    """bench.py --gpus N exactly as the driver launches it, with the solver replaced by a stub (SF_BENCH_DRYRUN=1):
+    """bench.py --gpus N --full exactly as the driver launches it, with the solver replaced by a stub (SF_BENCH_DRYRUN=1):
     rank 0 must print ONE JSON line with the contract fields, n_gpus == N, tagged as a dry run. Default for N > 1 is the
-    fixed grid ("scaling": "strong") followed by the one-GPU run of the same grid on rank 0 (`single_gpu`, `speedup`);
+    fixed grid ("scaling": "strong"); --full adds the one-GPU run of the same grid on rank 0 (`single_gpu`, `speedup`);
     `--weak` keeps the per-GPU cell count instead and reports "weak"."""
     import json
 
@@ -158,7 +158,7 @@ def test_bench_multirank_plumbing_dryrun(world, mode):
     env = dict(os.environ, OMP_NUM_THREADS="1", SF_BENCH_DRYRUN="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--grid", str(8 * world), "--roofline-n", "8"]
+           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--grid", str(8 * world), "--roofline-n", "8", "--full"]
     if mode == "weak":
         cmd.append("--weak")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)

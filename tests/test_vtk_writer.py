@@ -1,13 +1,13 @@
 """VTK frame writer parity: fluidsolvergpu_amd/csrc/sf_vtk.cpp vs the reference's visit_writer.
 
 Pinned two ways: (1) byte-equality with tests/golden/vtk/*.vtk, files written by the REFERENCE binary
-(tests/golden/make_vtk_golden.py); (2) when oracle/_ref is present, byte-equality on fresh random cases
-written by both libraries in this process."""
+(tests/golden/make_vtk_golden.py); (2) on seeded random cases, the SHA-256 and size of what the reference binary
+wrote for them (tests/golden/vtk_random_sha256.json, same generator) and, when oracle/_ref is present,
+byte-equality with the reference writing the same case in this process."""
 import hashlib
 import json
 import os
 
-import numpy as np
 import pytest
 
 import ref_writer
@@ -16,6 +16,7 @@ from fluidsolvergpu_amd import vtk as sfvtk
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "vtk")
 MANIFEST = json.load(open(os.path.join(GOLD, "MANIFEST.json")))
+RANDOM = json.load(open(os.path.join(os.path.dirname(GOLD), "vtk_random_sha256.json")))
 
 # hashes of files produced by the compiled reference writer.
 SURVEY_SHA = {
@@ -61,39 +62,29 @@ def test_cxx_linkage_names_are_drop_in(case, tmp_path):
     assert open(path, "rb").read() == open(os.path.join(GOLD, os.path.basename(path)), "rb").read()
 
 
-@pytest.mark.skipif(not ref_writer.available(), reason="oracle/_ref not built (reference absent)")
-@pytest.mark.parametrize("seed", range(6))
+def _same_as_reference(key, write, tmp_path):
+    """Writes the case with libsfvtk.so through `write(writer, path)`; its bytes must be those the reference wrote."""
+    mine = str(tmp_path / "mine.vtk")
+    write(sfvtk, mine)
+    data = open(mine, "rb").read()
+    assert len(data) == RANDOM[key]["bytes"] and hashlib.sha256(data).hexdigest() == RANDOM[key]["sha256"], key
+    if ref_writer.available():
+        ref = str(tmp_path / "ref.vtk")
+        write(ref_writer.Writer(), ref)
+        assert open(ref, "rb").read() == data
+
+
+@pytest.mark.parametrize("seed", vtk_cases.RANDOM_SEEDS)
 @pytest.mark.parametrize("ub", [0, 1])
 def test_random_regular_mesh_vs_live_reference(seed, ub, tmp_path):
-    rng = np.random.RandomState(100 + seed)
-    dims = [int(rng.randint(1, 12)) for _ in range(3)]
-    npts = dims[0] * dims[1] * dims[2]
-    ncells = max(dims[0] - 1, 1) * max(dims[1] - 1, 1) * max(dims[2] - 1, 1)
-    nvars = int(rng.randint(0, 6))
-    vardim = [int(rng.choice([1, 3])) for _ in range(nvars)]
-    centering = [int(rng.randint(0, 2)) for _ in range(nvars)]
-    names = [f"var{q}" for q in range(nvars)]
-    scale = 10.0 ** rng.randint(-30, 30, size=nvars)
-    vars_ = [(rng.standard_normal((npts if c else ncells) * d) * s).astype(np.float32)
-             for d, c, s in zip(vardim, centering, scale)]
-    a, b = str(tmp_path / "ref.vtk"), str(tmp_path / "mine.vtk")
-    ref_writer.Writer().write_regular_mesh(a, ub, dims, nvars, vardim, centering, names, vars_)
-    sfvtk.write_regular_mesh(b, ub, dims, nvars, vardim, centering, names, vars_)
-    assert open(a, "rb").read() == open(b, "rb").read()
+    args = vtk_cases.random_regular_case(seed, ub)
+    _same_as_reference(vtk_cases.random_case_key(seed, ub), lambda w, p: w.write_regular_mesh(p, *args), tmp_path)
 
 
-@pytest.mark.skipif(not ref_writer.available(), reason="oracle/_ref not built (reference absent)")
 def test_float_formatting_vs_live_reference(tmp_path):
     """%20.12e of 200k random bit patterns (all exponents, denormals, inf/nan) — to_chars == printf."""
-    rng = np.random.RandomState(7)
-    bits = rng.randint(0, 2 ** 32, size=200_000, dtype=np.uint64).astype(np.uint32)
-    vals = bits.view(np.float32)
-    n = len(vals)
-    a, b = str(tmp_path / "ref.vtk"), str(tmp_path / "mine.vtk")
-    args = (0, n, np.zeros(3 * n, np.float32), 1, [1], ["bits"], [vals])
-    ref_writer.Writer().write_point_mesh(a, *args)
-    sfvtk.write_point_mesh(b, *args)
-    assert open(a, "rb").read() == open(b, "rb").read()
+    args = vtk_cases.float_bits_case()
+    _same_as_reference(vtk_cases.FLOAT_BITS_KEY, lambda w, p: w.write_point_mesh(p, *args), tmp_path)
 
 
 def test_unwritable_path_raises(tmp_path):

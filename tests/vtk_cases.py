@@ -99,3 +99,41 @@ def run_case(writer, case, directory):
     else:
         raise ValueError(fn)
     return os.path.join(directory, name + ".vtk")
+
+
+def random_regular_case(seed, ub):
+    """A random regular mesh (dims 1..11, 0-5 variables of dimension 1 or 3, either centring, magnitudes 1e-30..1e30):
+    the arguments of write_regular_mesh after the file name."""
+    rng = np.random.RandomState(100 + seed)
+    dims = [int(rng.randint(1, 12)) for _ in range(3)]
+    npts = dims[0] * dims[1] * dims[2]
+    ncells = max(dims[0] - 1, 1) * max(dims[1] - 1, 1) * max(dims[2] - 1, 1)
+    nvars = int(rng.randint(0, 6))
+    vardim = [int(rng.choice([1, 3])) for _ in range(nvars)]
+    centering = [int(rng.randint(0, 2)) for _ in range(nvars)]
+    names = [f"var{q}" for q in range(nvars)]
+    scale = 10.0 ** rng.randint(-30, 30, size=nvars)
+    vars_ = [(rng.standard_normal((npts if c else ncells) * d) * s).astype(np.float32)
+             for d, c, s in zip(vardim, centering, scale)]
+    return (ub, dims, nvars, vardim, centering, names, vars_)
+
+
+def float_bits_case():
+    """200k random float32 bit patterns (all exponents, denormals, inf/nan) as one ASCII point-mesh variable: the
+    arguments of write_point_mesh after the file name."""
+    rng = np.random.RandomState(7)
+    bits = rng.randint(0, 2 ** 32, size=200_000, dtype=np.uint64).astype(np.uint32)
+    vals = bits.view(np.float32)
+    n = len(vals)
+    return (0, n, np.zeros(3 * n, np.float32), 1, [1], ["bits"], [vals])
+
+
+# the random cases of tests/test_vtk_writer.py, keyed as in tests/golden/vtk_random_sha256.json
+RANDOM_SEEDS = range(6)
+
+
+def random_case_key(seed, ub):
+    return f"regular_seed{seed}_ub{ub}"
+
+
+FLOAT_BITS_KEY = "float_bits_point_mesh"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/collect_profiles.sh <round-tag> — run ON THE GPU BOX (via gpurun). Produces under gpurun_out/profiles_<tag>/:
-#   bench.json                      the default bench.py line
+#   bench.json                      the bench.py --full line
 #   bench_stats/                    rocprofv3 --kernel-trace --stats of the same command (fewer steps)
 #   pmc_<N>/{trace,fetch,write,tcc,req}   separate --pmc passes for a 20-sweep lin_solve at N = 256 and 512
 #   sq_<N>/{insts,active,wait}      instruction-issue counters of the same solve (separate --pmc passes)
@@ -13,7 +13,7 @@ out=gpurun_out/profiles_$tag
 rm -rf $out
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py > $out/bench.json 2> $out/bench.err || exit 1
+python3 bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --roofline-n -1 > $out/bench_stats.log 2>&1 || exit 1
 export SF_SWEEP_K=20 SF_SWEEP_REPS=1
 for N in 256 512; do
