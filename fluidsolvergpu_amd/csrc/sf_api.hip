@@ -47,6 +47,7 @@ const char* sf_status_string(int status) {
         case SF_ERR_RCCL: return "SF_ERR_RCCL";
         case SF_ERR_HALO_EXCEEDED: return "SF_ERR_HALO_EXCEEDED";
         case SF_ERR_NO_DEVICE: return "SF_ERR_NO_DEVICE";
+        case SF_ERR_TRACER_OVERFLOW: return "SF_ERR_TRACER_OVERFLOW";
         default: return "SF_ERR_UNKNOWN";
     }
 }
@@ -180,6 +181,18 @@ int sf_tracers_advect(sf_ctx* ctx) {
 }
 int sf_tracers_get(sf_ctx* ctx, void* xyz, void* dens_sample, void* speed_sample) {
     return guarded(ctx, [&](SolverBase& s) { s.tracers_get(xyz, dens_sample, speed_sample); });
+}
+int sf_tracers_owned(const sf_ctx* ctx, int* n_owned) {
+    return guarded(const_cast<sf_ctx*>(ctx), [&](SolverBase& s) {
+        const int n = s.tracers_owned();
+        if (n_owned) *n_owned = n;
+    });
+}
+int sf_tracers_get_owned(sf_ctx* ctx, int* ids, void* xyz, void* dens_sample, void* speed_sample) {
+    return guarded(ctx, [&](SolverBase& s) { s.tracers_get_owned(ids, xyz, dens_sample, speed_sample); });
+}
+int sf_tracers_set_capacity(sf_ctx* ctx, int per_direction) {
+    return guarded(ctx, [&](SolverBase& s) { s.tracers_set_capacity(per_direction); });
 }
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });

@@ -92,6 +92,9 @@ public:
     virtual void tracers_set(int n, const void* xyz) = 0;
     virtual void tracers_advect() = 0;
     virtual void tracers_get(void* xyz, void* dens, void* speed) = 0;
+    virtual void tracers_set_capacity(int per_direction) = 0;
+    virtual int tracers_owned() = 0;
+    virtual void tracers_get_owned(int* ids, void* xyz, void* dens, void* speed) = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

@@ -13,7 +13,8 @@
 // writer thread downloads and encodes the frame while the main loop keeps stepping; the reference blocks on
 // cudaDeviceSynchronize + cudaMemcpy + per-value sprintf instead (solver-unidyn.cu:475-487). With --tracers N a
 // cloud of passive tracers is advected through the velocity field and written with write_point_mesh, the one
-// writer call the reference really makes (solver-unidyn.cu:487: ASCII, two point scalars).
+// writer call the reference really makes (solver-unidyn.cu:487: ASCII, two point scalars), on any decomposition: one
+// file with every tracer in one process, one file per rank (its own tracers, tracers_s_GPU<rank>_<frame>.vtk) on several.
 //
 // Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT in the environment
 // (e.g. `python -m torch.distributed.run --no-python --nproc-per-node 8 ./sf_driver ...`). Rank 0 creates the
@@ -305,9 +306,10 @@ static int run(const Options& o) {
         hw.resize(n);
     }
 
-    // tracers: a small lattice in the middle of the box, in grid-index coordinates (SPEC §6)
+    // tracers: a small lattice in the middle of the box, in grid-index coordinates (SPEC §6). Every rank seeds the
+    // same global lattice; each keeps the tracers its slabs own (SPEC §6.1).
     std::vector<T> tpos, tdens, tspeed;
-    if (o.tracers > 0 && o.slabs == 1 && o.world == 1) {
+    if (o.tracers > 0) {
         int side = 1;
         while (side * side * side < o.tracers) ++side;
         for (int c = 0; c < side && (int)tpos.size() / 3 < o.tracers; ++c)
@@ -324,19 +326,34 @@ static int run(const Options& o) {
     const int ntr = (int)(tpos.size() / 3);
 
     std::thread writer;  // at most one frame in flight
-    auto write_tracers = [&](int frame) {
-        std::vector<float> pts(3 * (size_t)ntr), m(ntr), sp(ntr);
-        for (int q = 0; q < 3 * ntr; ++q) pts[q] = (float)tpos[q];
-        for (int q = 0; q < ntr; ++q) {
+    // One process: all tracers in id order, "tracers_s<frame>.vtk". Several: each rank its own tracers in id order,
+    // "tracers_s_GPU<rank>_<frame>.vtk" (the per-device naming of the grid frames, solver-unidyn.cu:484).
+    int nout = ntr;  // tracers in the frame being written
+    auto fetch_tracers = [&]() {
+        if (o.world == 1) {
+            SF_CHECK_RETURN(sf_tracers_get(g_ctx, tpos.data(), tdens.data(), tspeed.data()));
+            nout = ntr;
+            return;
+        }
+        SF_CHECK_RETURN(sf_tracers_owned(g_ctx, &nout));  // <= ntr: the host buffers hold the whole lattice
+        SF_CHECK_RETURN(sf_tracers_get_owned(g_ctx, nullptr, tpos.data(), tdens.data(), tspeed.data()));
+    };
+    auto write_tracers = [&](int frame, int count) {
+        std::vector<float> pts(3 * (size_t)count), m(count), sp(count);
+        for (int q = 0; q < 3 * count; ++q) pts[q] = (float)tpos[q];
+        for (int q = 0; q < count; ++q) {
             m[q] = (float)tdens[q];
             sp[q] = (float)tspeed[q];
         }
         std::ostringstream oss;
-        oss << o.out << "/tracers_s" << frame << ".vtk";
+        if (o.world == 1)
+            oss << o.out << "/tracers_s" << frame << ".vtk";
+        else
+            oss << o.out << "/tracers_s_GPU" << o.rank << "_" << frame << ".vtk";
         int vardims[2] = {1, 1};
         const char* names[2] = {"density", "speed"};
         float* arrays[2] = {m.data(), sp.data()};
-        write_point_mesh(oss.str().c_str(), 0, ntr, pts.data(), 2, vardims, names, arrays);  // solver-unidyn.cu:487
+        write_point_mesh(oss.str().c_str(), 0, count, pts.data(), 2, vardims, names, arrays);  // solver-unidyn.cu:487
     };
 
     double total_ms = 0;
@@ -355,7 +372,7 @@ static int run(const Options& o) {
         if (o.every > 0 && t % o.every == 0) {
             const int frame = t / o.every;
             if (writer.joinable()) writer.join();  // the previous frame must be out before its buffers are reused
-            if (ntr > 0) SF_CHECK_RETURN(sf_tracers_get(g_ctx, tpos.data(), tdens.data(), tspeed.data()));
+            if (ntr > 0) fetch_tracers();
             if (o.sync_output) {
                 SF_CHECK_RETURN(sf_sync(g_ctx));
                 SF_CHECK_RETURN(sf_download_planes(g_ctx, SF_DENS, own_kb, own_ke, hd.data()));
@@ -363,11 +380,11 @@ static int run(const Options& o) {
                 SF_CHECK_RETURN(sf_download_planes(g_ctx, SF_V, own_kb, own_ke, hv.data()));
                 SF_CHECK_RETURN(sf_download_planes(g_ctx, SF_W, own_kb, own_ke, hw.data()));
                 write_frame<T>(o, frame, own_kb, own_ke, hd, hu, hv, hw);
-                if (ntr > 0) write_tracers(frame);
+                if (ntr > 0) write_tracers(frame, nout);
             } else {
                 const int fields[4] = {SF_DENS, SF_U, SF_V, SF_W};
                 SF_CHECK_RETURN(sf_snapshot(g_ctx, fields, 4));
-                writer = std::thread([&, frame]() {
+                writer = std::thread([&, frame, count = nout]() {
                     T* dst[4] = {hd.data(), hu.data(), hv.data(), hw.data()};
                     for (int q = 0; q < 4; ++q)
                         if (sf_snapshot_read_planes(g_ctx, q, own_kb, own_ke, dst[q]) != SF_OK) {
@@ -375,7 +392,7 @@ static int run(const Options& o) {
                             exit(1);
                         }
                     write_frame<T>(o, frame, own_kb, own_ke, hd, hu, hv, hw);
-                    if (ntr > 0) write_tracers(frame);
+                    if (ntr > 0) write_tracers(frame, count);
                 });
             }
         }

@@ -2090,7 +2090,10 @@ struct TriSampleDev {
     long q;
     long dj, dk;
     T s0, s1, t0, t1, r0, r1;
-    __device__ TriSampleDev(const Geom& g, T x, T y, T z) {
+    // clamp_plane (decomposed tracers, SPEC §6.1): the local plane k0 - kg0 is clamped into [0, np - 2] so that the
+    // two planes read are stored by this slab whatever the position (tracers owned elsewhere — loopback arrivals —
+    // included). A tracer owned by the slab reads inside that range already, so its sample does not change.
+    __device__ TriSampleDev(const Geom& g, T x, T y, T z, bool clamp_plane = false) {
         const int N = g.N;
         const T Nf = (T)N, lo = T(0.5), hi = Nf + T(0.5);
         if (x < lo) x = lo;
@@ -2109,7 +2112,9 @@ struct TriSampleDev {
         t0 = T(1) - t1;
         r1 = z - (T)k0;
         r0 = T(1) - r1;
-        q = row0(g, j0, k0 - g.kg0) + i0;
+        int kl = k0 - g.kg0;
+        if (clamp_plane) kl = kl < 0 ? 0 : (kl > g.np - 2 ? g.np - 2 : kl);
+        q = row0(g, j0, kl) + i0;
         dj = g.px;
         dk = g.plane;
     }
@@ -2154,6 +2159,185 @@ __global__ void __launch_bounds__(256) tracers_sample_kernel(Geom g, int n, cons
     const T a = S(u), b = S(v), c = S(w);
     dens_out[t] = S(dens);
     speed_out[t] = sqrt((a * a + b * b) + c * c);
+}
+
+// ---- Tracers on a decomposed grid (SPEC §6.1) ------------------------------------------------------------------
+// Each slab keeps a device list of the tracers it owns: 16-byte records (x, y, z, id) in fp32, 32 bytes in fp64.
+// The order inside a list is free (wave-level compaction); output restores it by id.
+template <class T>
+struct alignas(4 * sizeof(T)) TracerRec {
+    T x, y, z;
+    int id;
+};
+
+// Global slab that owns a tracer at height z: k0 exactly as TriSampleDev computes it (clamp, NaN -> 0, [0, N]), then
+// k0 in [s nzl + 1, (s + 1) nzl] -> s, and k0 = 0 -> slab 0. The host twin is Solver::tracer_owner.
+template <class T>
+__device__ __forceinline__ int tracer_owner(int N, int nzl, T z) {
+    z = clamp_coord(N, z);
+    int k0 = (z == z) ? (int)z : 0;
+    k0 = k0 < 0 ? 0 : (k0 > N ? N : k0);
+    return k0 == 0 ? 0 : (k0 - 1) / nzl;
+}
+
+// Send buffers hold a header record (its id field is the number of records written, possibly more than `cap` when the
+// buffer overflowed) followed by `cap` records; the same bytes travel as one RCCL message.
+template <class T>
+struct TracerMoveArgs {
+    const TracerRec<T>* in;  // the list owned at the start of the call
+    const int* n_in;
+    TracerRec<T>* keep;  // the other list of the ping-pong pair; *n_keep is zero on entry
+    int* n_keep;
+    TracerRec<T>* send[2];  // [0] to slab gid - 1, [1] to slab gid + 1 (nullptr where there is none)
+    int cap;                // records per send buffer after the header
+    int list_cap;           // records per list (the global tracer count)
+    int gid;
+    const T* u;
+    const T* v;
+    const T* w;
+    T dt0;
+    int* flag;  // bit 0: a send buffer or a list overflowed, bit 1: a tracer moved past a neighbouring slab
+};
+
+// Appends the active lanes' records to `dst` (count `*cnt`, capacity `cap`): one atomic per wave, slots by ballot +
+// prefix count. Returns false for a lane whose slot lies beyond the capacity (nothing is written for it).
+template <class T>
+__device__ __forceinline__ bool wave_append(bool active, const TracerRec<T>& r, TracerRec<T>* dst, int* cnt, int cap) {
+    const unsigned long long mask = __ballot(active);
+    if (mask == 0) return true;
+    const int lane = (int)(threadIdx.x & 63);
+    int base = 0;
+    if (lane == 0) base = atomicAdd(cnt, __popcll(mask));
+    base = __shfl(base, 0);
+    if (!active) return true;
+    const int slot = base + __popcll(mask & ((1ull << lane) - 1ull));
+    if (slot >= cap) return false;
+    dst[slot] = r;
+    return true;
+}
+
+// One slab's share of sf_tracers_advect: the SPEC §6 step of every owned tracer (same clamps, same order of
+// operations as tracers_advect_kernel), then the new owner: keepers go to the other list, migrants to the send buffer
+// of their direction. A migrant that finds its send buffer full, and a tracer that skipped a slab, stay in this list
+// and raise the flag (sf_sync reports it): nothing is dropped. The count lives in device memory, so the grid is sized
+// to the chip and strides over it; the loop bound is uniform per workgroup, so every ballot sees whole waves.
+template <class T>
+__global__ void __launch_bounds__(256) tracers_move_kernel(Geom g, TracerMoveArgs<T> A) {
+    int n = *A.n_in;
+    n = n < 0 ? 0 : (n > A.list_cap ? A.list_cap : n);
+    const int N = g.N;
+    const int stride = (int)(gridDim.x * blockDim.x);
+    for (int base = (int)(blockIdx.x * blockDim.x); base < n; base += stride) {
+        const int t = base + (int)threadIdx.x;
+        const bool live = t < n;
+        TracerRec<T> r{};
+        int dir = 0;  // owner - gid
+        if (live) {
+            r = A.in[t];
+            const T x = clamp_coord(N, r.x), y = clamp_coord(N, r.y), z = clamp_coord(N, r.z);
+            const TriSampleDev<T> S(g, x, y, z, true);
+            const T vx = S(A.u), vy = S(A.v), vz = S(A.w);
+            r.x = clamp_coord(N, x + A.dt0 * vx);
+            r.y = clamp_coord(N, y + A.dt0 * vy);
+            r.z = clamp_coord(N, z + A.dt0 * vz);
+            dir = tracer_owner(N, g.nzl, r.z) - A.gid;
+        }
+        const bool down = live && dir == -1, up = live && dir == 1;
+        bool over = false;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {  // (send[s] is the same for the whole grid: the branch is uniform)
+            const bool go = s ? up : down;
+            if (A.send[s] != nullptr)
+                over |= !wave_append(go, r, A.send[s] + 1, &A.send[s]->id, A.cap);
+            else
+                over |= go;
+        }
+        const bool jump = live && (dir < -1 || dir > 1);
+        const bool stay = live && (dir == 0 || jump || over);
+        const bool kept = wave_append(stay, r, A.keep, A.n_keep, A.list_cap);
+        if (over || !kept) atomicOr(A.flag, 1);
+        if (jump) atomicOr(A.flag, 2);
+    }
+}
+
+// Arrivals from the slab below (blockIdx.y = 0) and above (1) appended to the owner's list. src points at a send
+// buffer (neighbour in this process) or at this slab's receive buffer (RCCL, loopback); the count in its header is
+// clamped to the capacity, whatever arrived.
+template <class T>
+struct TracerArriveArgs {
+    const TracerRec<T>* src[2];
+    int cap;
+    TracerRec<T>* list;
+    int* n_list;
+    int list_cap;
+    int* flag;
+};
+
+template <class T>
+__global__ void __launch_bounds__(256) tracers_arrive_kernel(TracerArriveArgs<T> A) {
+    const TracerRec<T>* src = blockIdx.y == 0 ? A.src[0] : A.src[1];
+    if (src == nullptr) return;
+    int n = src[0].id;
+    n = n < 0 ? 0 : (n > A.cap ? A.cap : n);
+    const int stride = (int)(gridDim.x * blockDim.x);
+    for (int base = (int)(blockIdx.x * blockDim.x); base < n; base += stride) {
+        const int t = base + (int)threadIdx.x;
+        const bool live = t < n;
+        TracerRec<T> r{};
+        if (live) r = src[1 + t];
+        if (!wave_append(live, r, A.list, A.n_list, A.list_cap)) atomicOr(A.flag, 1);
+    }
+}
+
+// Zeroes the counts a call appends to: the next list and the two send headers.
+static __global__ void tracers_reset_kernel(int* n_next, int* hdr_lo, int* hdr_hi) {
+    if (threadIdx.x == 0) {
+        *n_next = 0;
+        if (hdr_lo) *hdr_lo = 0;
+        if (hdr_hi) *hdr_hi = 0;
+    }
+}
+
+// Output path: position and (dens != nullptr) density and speed samples of every listed tracer, written at index id
+// (offset < 0: sf_tracers_get's dense arrays; ids outside [0, n_out) are skipped) or at offset + list index
+// (sf_tracers_get_owned, with the id alongside).
+template <class T>
+struct TracerOutArgs {
+    const TracerRec<T>* list;
+    const int* n_list;
+    int list_cap;
+    const T* dens;
+    const T* u;
+    const T* v;
+    const T* w;
+    int n_out;
+    int offset;
+    T* pos;
+    T* dens_out;
+    T* speed_out;
+    int* id_out;
+};
+
+template <class T>
+__global__ void __launch_bounds__(256) tracers_out_kernel(Geom g, TracerOutArgs<T> A) {
+    int n = *A.n_list;
+    n = n < 0 ? 0 : (n > A.list_cap ? A.list_cap : n);
+    const int stride = (int)(gridDim.x * blockDim.x);
+    for (int t = (int)(blockIdx.x * blockDim.x + threadIdx.x); t < n; t += stride) {
+        const TracerRec<T> r = A.list[t];
+        const int d = A.offset < 0 ? r.id : A.offset + t;
+        if (d < 0 || d >= A.n_out) continue;
+        A.pos[3 * d] = r.x;
+        A.pos[3 * d + 1] = r.y;
+        A.pos[3 * d + 2] = r.z;
+        if (A.id_out) A.id_out[d] = r.id;
+        if (A.dens) {
+            const TriSampleDev<T> S(g, r.x, r.y, r.z, true);
+            const T a = S(A.u), b = S(A.v), c = S(A.w);
+            A.dens_out[d] = S(A.dens);
+            A.speed_out[d] = sqrt((a * a + b * b) + c * c);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -37,6 +37,14 @@ class Solver final : public SolverBase {
         hipEvent_t boundary_done = nullptr;
         hipEvent_t halo_done = nullptr;
         int* d_flag = nullptr;
+        // tracers of a decomposed context (SPEC §6.1): the owned list (a ping-pong pair and its two counts), the send
+        // buffers towards slab gid - 1 / gid + 1 and, where that neighbour's records arrive as a message (another
+        // process, loopback, SF_FLAG_RCCL_SELF), the receive buffers; tr_flag: overflow / skipped-slab bits
+        sfk::TracerRec<T>* tr_list[2] = {};
+        int* tr_cnt = nullptr;
+        sfk::TracerRec<T>* tr_send[2] = {};
+        sfk::TracerRec<T>* tr_recv[2] = {};
+        int* tr_flag = nullptr;
     };
 
 public:
@@ -318,9 +326,7 @@ public:
         }
         if (t0_) (void)hipEventDestroy(t0_);
         if (t1_) (void)hipEventDestroy(t1_);
-        if (tr_pos_) (void)hipFree(tr_pos_);
-        if (tr_dens_) (void)hipFree(tr_dens_);
-        if (tr_speed_) (void)hipFree(tr_speed_);
+        tracers_free();
         if (copy_src_) (void)hipFree(copy_src_);
         if (copy_dst_) (void)hipFree(copy_dst_);
     }
@@ -680,10 +686,31 @@ public:
                     SF_HIP(hipDeviceSynchronize());
                 }
             }
+            int tr_bits = 0;  // decomposed tracers: bit 0 overflow, bit 1 a tracer skipped a slab
+            for (Slab& sl : slabs_) {
+                if (!sl.tr_flag) continue;
+                int flag = 0;
+                SF_HIP(hipMemcpy(&flag, sl.tr_flag, sizeof(int), hipMemcpyDeviceToHost));
+                if (flag) {
+                    tr_bits |= flag;
+                    SF_HIP(hipMemset(sl.tr_flag, 0, sizeof(int)));
+                    SF_HIP(hipDeviceSynchronize());
+                }
+            }
             if (exceeded)
                 throw Failure{SF_ERR_HALO_EXCEEDED,
                               "advect back-traced more than one plane across a slab boundary "
                               "(|dt*N*w| >= 1): results differ from the undecomposed solve"};
+            if (tr_bits & 1)
+                throw Failure{SF_ERR_TRACER_OVERFLOW,
+                              "more tracers left a slab for one neighbour in one tracers_advect than the capacity "
+                              "(sf_tracers_set_capacity) holds: the surplus stayed with the slab they left, and the "
+                              "tracers are no longer those of the undecomposed run"};
+            if (tr_bits & 2)
+                throw Failure{SF_ERR_HALO_EXCEEDED,
+                              "a tracer moved past a neighbouring slab in one tracers_advect (|dt*N*v_z| >= planes "
+                              "per slab): it stayed with the slab it left, and the tracers are no longer those of "
+                              "the undecomposed run"};
         }
     }
 
@@ -788,50 +815,204 @@ public:
         for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.os));
     }
 
-    // ---- tracers (SPEC §6) ----------------------------------------------------------------------
+    // ---- tracers (SPEC §6; decomposed contexts §6.1) ------------------------------------------------------------
     void tracers_set(int n, const void* xyz) override {
         join();
-        SF_REQUIRE(P_ == 1, "tracers need a single-slab context");
         SF_REQUIRE(n >= 0 && (n == 0 || xyz != nullptr), "bad tracer array");
         SF_HIP(hipSetDevice(device_));
-        if (tr_pos_) (void)hipFree(tr_pos_);
-        if (tr_dens_) (void)hipFree(tr_dens_);
-        if (tr_speed_) (void)hipFree(tr_speed_);
-        tr_pos_ = tr_dens_ = tr_speed_ = nullptr;
+        tracers_free();
         tr_n_ = n;
         if (n == 0) return;
         SF_HIP(hipMalloc(&tr_pos_, (size_t)3 * n * sizeof(T)));
         SF_HIP(hipMalloc(&tr_dens_, (size_t)n * sizeof(T)));
         SF_HIP(hipMalloc(&tr_speed_, (size_t)n * sizeof(T)));
-        SF_HIP(hipMemcpyAsync(tr_pos_, xyz, (size_t)3 * n * sizeof(T), hipMemcpyHostToDevice, slabs_[0].cs));
-        SF_HIP(hipStreamSynchronize(slabs_[0].cs));
+        if (P_ == 1) {
+            SF_HIP(hipMemcpyAsync(tr_pos_, xyz, (size_t)3 * n * sizeof(T), hipMemcpyHostToDevice, slabs_[0].cs));
+            SF_HIP(hipStreamSynchronize(slabs_[0].cs));
+            return;
+        }
+        // every rank gets the same global array and keeps the tracers its slabs own; the id is the index, positions
+        // stay raw (unclamped) until the first tracers_advect
+        const T* p = static_cast<const T*>(xyz);
+        std::vector<std::vector<sfk::TracerRec<T>>> own(L_);
+        for (int t = 0; t < n; ++t) {
+            const int s = tracer_owner(p[3 * t + 2]) - rank_ * L_;
+            if (s >= 0 && s < L_) own[s].push_back(sfk::TracerRec<T>{p[3 * t], p[3 * t + 1], p[3 * t + 2], t});
+        }
+        SF_HIP(hipMalloc(&tr_ids_, (size_t)n * sizeof(int)));
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            for (auto*& l : sl.tr_list) SF_HIP(hipMalloc(&l, (size_t)n * sizeof(sfk::TracerRec<T>)));
+            SF_HIP(hipMalloc(&sl.tr_cnt, 2 * sizeof(int)));
+            SF_HIP(hipMalloc(&sl.tr_flag, sizeof(int)));
+            const int cnt[2] = {(int)own[s].size(), 0}, zero = 0;
+            if (!own[s].empty())
+                SF_HIP(hipMemcpy(sl.tr_list[0], own[s].data(), own[s].size() * sizeof(sfk::TracerRec<T>),
+                                 hipMemcpyHostToDevice));
+            SF_HIP(hipMemcpy(sl.tr_cnt, cnt, sizeof cnt, hipMemcpyHostToDevice));
+            SF_HIP(hipMemcpy(sl.tr_flag, &zero, sizeof zero, hipMemcpyHostToDevice));
+        }
+        tr_cur_ = 0;
+        tracers_alloc_messages();
     }
+
+    void tracers_set_capacity(int per_direction) override {
+        SF_REQUIRE(per_direction >= 1, "tracer capacity must be >= 1");
+        join();
+        SF_HIP(hipSetDevice(device_));
+        tr_cap_req_ = per_direction;
+        if (P_ > 1 && tr_n_ > 0) tracers_alloc_messages();
+    }
+
+    // One dt for every tracer. P > 1: per slab one kernel advects, classifies and compacts its tracers (keepers into
+    // the other list of the pair, migrants into the send buffer of their direction); the send buffers then reach the
+    // neighbours through the ghost-plane transports — read in place by a neighbour in this process, one grouped RCCL
+    // send / receive per neighbouring process (all slabs in one group under SF_FLAG_RCCL_SELF), a local copy under
+    // SF_FLAG_LOOPBACK_HALO — and a second kernel appends the arrivals. Nothing is read back to the host.
     void tracers_advect() override {
         join();
-        SF_REQUIRE(P_ == 1, "tracers need a single-slab context");
         if (tr_n_ == 0) return;
         SF_HIP(hipSetDevice(device_));
-        Slab& sl = slabs_[0];
-        hipLaunchKernelGGL((sfk::tracers_advect_kernel<T>), dim3((unsigned)ceil_div(tr_n_, 256)), dim3(256), 0, sl.cs,
-                           sl.geom, tr_n_, tr_pos_, sl.field[SF_U], sl.field[SF_V], sl.field[SF_W], dt_ * (T)N_);
-        SF_HIP(hipGetLastError());
+        if (P_ == 1) {
+            Slab& sl = slabs_[0];
+            hipLaunchKernelGGL((sfk::tracers_advect_kernel<T>), dim3((unsigned)ceil_div(tr_n_, 256)), dim3(256), 0,
+                               sl.cs, sl.geom, tr_n_, tr_pos_, sl.field[SF_U], sl.field[SF_V], sl.field[SF_W],
+                               dt_ * (T)N_);
+            SF_HIP(hipGetLastError());
+            return;
+        }
+        const int cur = tr_cur_, nxt = cur ^ 1;
+        // the previous call's arrivals kernels of neighbours in this process read this slab's send buffers
+        for (Slab& sl : slabs_) ev_record(sl, &Slab::cs_mark, sl.cs);
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            for (int d = 0; d < 2; ++d)
+                if (tr_side(s, d) == TR_LOCAL) st_wait(sl, sl.cs, slabs_[s + (d ? 1 : -1)], &Slab::cs_mark);
+            hipLaunchKernelGGL(sfk::tracers_reset_kernel, dim3(1), dim3(64), 0, sl.cs, sl.tr_cnt + nxt,
+                               sl.tr_send[0] ? &sl.tr_send[0]->id : nullptr, sl.tr_send[1] ? &sl.tr_send[1]->id : nullptr);
+            sfk::TracerMoveArgs<T> A;
+            A.in = sl.tr_list[cur];
+            A.n_in = sl.tr_cnt + cur;
+            A.keep = sl.tr_list[nxt];
+            A.n_keep = sl.tr_cnt + nxt;
+            A.send[0] = sl.tr_send[0];
+            A.send[1] = sl.tr_send[1];
+            A.cap = tr_cap_;
+            A.list_cap = tr_n_;
+            A.gid = sl.gid;
+            A.u = sl.field[SF_U];
+            A.v = sl.field[SF_V];
+            A.w = sl.field[SF_W];
+            A.dt0 = dt_ * (T)N_;
+            A.flag = sl.tr_flag;
+            hipLaunchKernelGGL((sfk::tracers_move_kernel<T>), dim3(tracer_grid(tr_n_)), dim3(256), 0, sl.cs, sl.geom, A);
+            SF_HIP(hipGetLastError());
+            tr_whole("tracers_move", sl, {A.u, A.v, A.w, A.in},
+                     {A.keep, sl.tr_send[0] ? (const void*)sl.tr_send[0] : A.keep,
+                      sl.tr_send[1] ? (const void*)sl.tr_send[1] : A.keep});
+        }
+        for (Slab& sl : slabs_) ev_record(sl, &Slab::cs_mark, sl.cs);
+        tracers_transport();
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            sfk::TracerArriveArgs<T> A;
+            bool msg = false;
+            for (int d = 0; d < 2; ++d) {
+                const int side = tr_side(s, d);
+                Slab* nb = side == TR_NONE ? nullptr : &slabs_[s + (d ? 1 : -1)];
+                A.src[d] = side == TR_LOCAL ? nb->tr_send[1 - d] : (side == TR_MSG ? sl.tr_recv[d] : nullptr);
+                if (side == TR_LOCAL) st_wait(sl, sl.cs, *nb, &Slab::cs_mark);
+                if (side == TR_MSG && rccl_self_) st_wait(sl, sl.cs, *nb, &Slab::halo_done);
+                msg = msg || side == TR_MSG;
+            }
+            if (msg) st_wait(sl, sl.cs, sl, &Slab::halo_done);
+            A.cap = tr_cap_;
+            A.list = sl.tr_list[nxt];
+            A.n_list = sl.tr_cnt + nxt;
+            A.list_cap = tr_n_;
+            A.flag = sl.tr_flag;
+            hipLaunchKernelGGL((sfk::tracers_arrive_kernel<T>), dim3(tracer_grid(tr_cap_), 2), dim3(256), 0, sl.cs, A);
+            SF_HIP(hipGetLastError());
+            tr_whole("tracers_arrive", sl, {A.src[0] ? (const void*)A.src[0] : A.list, A.src[1] ? (const void*)A.src[1] : A.list},
+                     {A.list});
+        }
+        tr_cur_ = nxt;
     }
+
     void tracers_get(void* xyz, void* dens, void* speed) override {
         join();
-        SF_REQUIRE(P_ == 1, "tracers need a single-slab context");
+        SF_REQUIRE(nranks_ == 1, "sf_tracers_get returns every tracer, but this context holds only its rank's: "
+                                 "use sf_tracers_get_owned on a multi-rank context");
         if (tr_n_ == 0) return;
         SF_HIP(hipSetDevice(device_));
         Slab& sl = slabs_[0];
-        if (dens || speed) {
-            hipLaunchKernelGGL((sfk::tracers_sample_kernel<T>), dim3((unsigned)ceil_div(tr_n_, 256)), dim3(256), 0,
-                               sl.cs, sl.geom, tr_n_, tr_pos_, sl.field[SF_DENS], sl.field[SF_U], sl.field[SF_V],
-                               sl.field[SF_W], tr_dens_, tr_speed_);
-            SF_HIP(hipGetLastError());
+        if (P_ == 1) {
+            if (dens || speed) {
+                hipLaunchKernelGGL((sfk::tracers_sample_kernel<T>), dim3((unsigned)ceil_div(tr_n_, 256)), dim3(256), 0,
+                                   sl.cs, sl.geom, tr_n_, tr_pos_, sl.field[SF_DENS], sl.field[SF_U], sl.field[SF_V],
+                                   sl.field[SF_W], tr_dens_, tr_speed_);
+                SF_HIP(hipGetLastError());
+            }
+        } else {
+            // every slab scatters its tracers by id into the dense arrays (disjoint ids; read back after a host sync)
+            for (Slab& s : slabs_) tracers_out(s, -1, dens || speed, false);
+            for (Slab& s : slabs_) SF_HIP(hipStreamSynchronize(s.cs));
         }
         if (xyz) SF_HIP(hipMemcpyAsync(xyz, tr_pos_, (size_t)3 * tr_n_ * sizeof(T), hipMemcpyDeviceToHost, sl.cs));
         if (dens) SF_HIP(hipMemcpyAsync(dens, tr_dens_, (size_t)tr_n_ * sizeof(T), hipMemcpyDeviceToHost, sl.cs));
         if (speed) SF_HIP(hipMemcpyAsync(speed, tr_speed_, (size_t)tr_n_ * sizeof(T), hipMemcpyDeviceToHost, sl.cs));
         SF_HIP(hipStreamSynchronize(sl.cs));
+    }
+
+    int tracers_owned() override {
+        join();
+        SF_HIP(hipSetDevice(device_));
+        if (P_ == 1 || tr_n_ == 0) return tr_n_;
+        int total = 0;
+        for (int c : tracer_counts()) total += c;
+        return total;
+    }
+
+    // The tracers of this context in ascending id order (what one rank writes into its point-mesh file).
+    void tracers_get_owned(int* ids, void* xyz, void* dens, void* speed) override {
+        join();
+        if (tr_n_ == 0) return;
+        SF_HIP(hipSetDevice(device_));
+        if (P_ == 1) {
+            if (ids)
+                for (int t = 0; t < tr_n_; ++t) ids[t] = t;
+            if (xyz || dens || speed) tracers_get(xyz, dens, speed);
+            return;
+        }
+        const std::vector<int> cnt = tracer_counts();
+        int total = 0;
+        for (int s = 0; s < L_; ++s) {
+            tracers_out(slabs_[s], total, dens || speed, true);
+            total += cnt[s];
+        }
+        total = std::min(total, tr_n_);
+        for (Slab& s : slabs_) SF_HIP(hipStreamSynchronize(s.cs));
+        std::vector<int> hid(total);
+        std::vector<T> hpos((size_t)3 * total), hd(total), hs(total);
+        if (total > 0) {
+            SF_HIP(hipMemcpy(hid.data(), tr_ids_, (size_t)total * sizeof(int), hipMemcpyDeviceToHost));
+            SF_HIP(hipMemcpy(hpos.data(), tr_pos_, (size_t)3 * total * sizeof(T), hipMemcpyDeviceToHost));
+            if (dens || speed) {
+                SF_HIP(hipMemcpy(hd.data(), tr_dens_, (size_t)total * sizeof(T), hipMemcpyDeviceToHost));
+                SF_HIP(hipMemcpy(hs.data(), tr_speed_, (size_t)total * sizeof(T), hipMemcpyDeviceToHost));
+            }
+        }
+        std::vector<int> order(total);
+        for (int q = 0; q < total; ++q) order[q] = q;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return hid[a] < hid[b]; });
+        for (int q = 0; q < total; ++q) {
+            const int o = order[q];
+            if (ids) ids[q] = hid[o];
+            if (xyz)
+                for (int c = 0; c < 3; ++c) static_cast<T*>(xyz)[3 * q + c] = hpos[3 * (size_t)o + c];
+            if (dens) static_cast<T*>(dens)[q] = hd[o];
+            if (speed) static_cast<T*>(speed)[q] = hs[o];
+        }
     }
 
     int lin_solve_launches(int iters) const override {
@@ -859,6 +1040,187 @@ private:
     // ---- helpers --------------------------------------------------------------------------
     static void check_field(int f) { SF_REQUIRE(f >= 0 && f < SF_NUM_FIELDS, "field id out of range"); }
     static void check_b(int b) { SF_REQUIRE(b >= 0 && b <= 3, "boundary mode b must be 0..3"); }
+
+    // ---- decomposed tracers (SPEC §6.1) ------------------------------------------------------------------------
+    // How the records of the neighbour below (d = 0) / above (d = 1) of local slab s reach it: no neighbour, read in
+    // place from the neighbour's send buffer (same process), or a message into this slab's receive buffer.
+    enum { TR_NONE = 0, TR_LOCAL = 1, TR_MSG = 2 };
+    int tr_side(int s, int d) const {
+        const int gid = slabs_[s].gid;
+        if (d == 0 ? gid == 0 : gid == P_ - 1) return TR_NONE;
+        const bool in_process = d == 0 ? s > 0 : s < L_ - 1;
+        return (in_process && !rccl_self_) ? TR_LOCAL : TR_MSG;
+    }
+    // host twin of sfk::tracer_owner (same T arithmetic): the global slab whose planes the sample at height z reads
+    int tracer_owner(T z) const {
+        const T lo = T(0.5), hi = (T)N_ + T(0.5);
+        if (z < lo) z = lo;
+        if (z > hi) z = hi;
+        int k0 = (z == z) ? (int)z : 0;
+        k0 = k0 < 0 ? 0 : (k0 > N_ ? N_ : k0);
+        return k0 == 0 ? 0 : (k0 - 1) / nzl_;
+    }
+    unsigned tracer_grid(int n) const {
+        return (unsigned)std::max(1L, std::min(ceil_div((long)n, 256L), (long)num_cu_ * 8));
+    }
+    template <class P>
+    static void release(P*& p) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    void tracers_free() {
+        (void)hipDeviceSynchronize();  // earlier launches may still use the buffers
+        release(tr_pos_);
+        release(tr_dens_);
+        release(tr_speed_);
+        release(tr_ids_);
+        for (Slab& sl : slabs_) {
+            for (int q = 0; q < 2; ++q) {
+                release(sl.tr_list[q]);
+                release(sl.tr_send[q]);
+                release(sl.tr_recv[q]);
+            }
+            release(sl.tr_cnt);
+            release(sl.tr_flag);
+        }
+        tr_n_ = 0;
+    }
+    // (Re)allocates the send / receive buffers for the capacity in force: a header record + tr_cap_ records each.
+    void tracers_alloc_messages() {
+        SF_HIP(hipDeviceSynchronize());
+        tr_cap_ = tr_cap_req_ > 0 ? std::min(tr_cap_req_, tr_n_) : tr_n_;
+        const size_t bytes = (size_t)(tr_cap_ + 1) * sizeof(sfk::TracerRec<T>);
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            for (int d = 0; d < 2; ++d) {
+                release(sl.tr_send[d]);
+                release(sl.tr_recv[d]);
+                const int side = tr_side(s, d);
+                if (side == TR_NONE) continue;
+                SF_HIP(hipMalloc(&sl.tr_send[d], bytes));
+                SF_HIP(hipMemset(sl.tr_send[d], 0, bytes));
+                if (side == TR_MSG) {
+                    SF_HIP(hipMalloc(&sl.tr_recv[d], bytes));
+                    SF_HIP(hipMemset(sl.tr_recv[d], 0, bytes));
+                }
+            }
+        }
+        SF_HIP(hipDeviceSynchronize());
+    }
+    // The messages of one tracers_advect: issued on the halo streams after the move kernels (cs_mark), completion in
+    // halo_done. Each message is the whole send buffer (header + capacity): the receiver cannot know the count on the
+    // host without a sync.
+    void tracers_transport() {
+        const size_t bytes = (size_t)(tr_cap_ + 1) * sizeof(sfk::TracerRec<T>);
+        if (rccl_self_) {
+            // as exchange_rccl_self: every transfer is the pair (send from the owner, receive into the neighbour), all
+            // slabs in one group
+            for (int s = 0; s < L_; ++s) {
+                Slab& sl = slabs_[s];
+                st_wait(sl, sl.hs, sl, &Slab::cs_mark);
+                if (s > 0) st_wait(sl, sl.hs, slabs_[s - 1], &Slab::cs_mark);
+                if (s < L_ - 1) st_wait(sl, sl.hs, slabs_[s + 1], &Slab::cs_mark);
+            }
+            SF_NCCL(ncclGroupStart());
+            for (int s = 0; s + 1 < L_; ++s) {
+                Slab& lo = slabs_[s];
+                Slab& hi = slabs_[s + 1];
+                SF_NCCL(ncclSend(lo.tr_send[1], bytes, ncclUint8, 0, comm_, lo.hs));
+                SF_NCCL(ncclRecv(hi.tr_recv[0], bytes, ncclUint8, 0, comm_, hi.hs));
+                SF_NCCL(ncclSend(hi.tr_send[0], bytes, ncclUint8, 0, comm_, hi.hs));
+                SF_NCCL(ncclRecv(lo.tr_recv[1], bytes, ncclUint8, 0, comm_, lo.hs));
+            }
+            SF_NCCL(ncclGroupEnd());
+            ++rccl_groups_;
+            for (int s = 0; s < L_; ++s) {
+                Slab& sl = slabs_[s];
+                if (trace_) {
+                    std::vector<Acc> acc;
+                    for (int d = 0; d < 2; ++d) {
+                        if (!sl.tr_recv[d]) continue;
+                        acc.push_back({sl.tr_send[d], false, 0, nplanes_});
+                        acc.push_back({slabs_[s + (d ? 1 : -1)].tr_send[1 - d], false, 0, nplanes_});
+                        acc.push_back({sl.tr_recv[d], true, 0, nplanes_});
+                    }
+                    tr_op("tracers_rccl_self", sl, sl.hs, acc);
+                }
+                ev_record(sl, &Slab::halo_done, sl.hs);
+            }
+            return;
+        }
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            const bool m[2] = {tr_side(s, 0) == TR_MSG, tr_side(s, 1) == TR_MSG};
+            if (!m[0] && !m[1]) continue;
+            st_wait(sl, sl.hs, sl, &Slab::cs_mark);
+            if (loopback_) {
+                // SF_FLAG_LOOPBACK_HALO: the same bytes on the same stream, from this slab's own send buffers
+                sfk::HaloCopyArgs H;
+                H.nseg = 0;
+                H.n16 = (long)(bytes / 16);
+                for (int d = 0; d < 2; ++d)
+                    if (m[d]) {
+                        H.src[H.nseg] = reinterpret_cast<const float4*>(sl.tr_send[d]);
+                        H.dst[H.nseg++] = reinterpret_cast<float4*>(sl.tr_recv[d]);
+                    }
+                const unsigned gx = (unsigned)std::max(1L, std::min((H.n16 + 255) / 256, 512L));
+                hipLaunchKernelGGL(sfk::halo_copy_kernel, dim3(gx, H.nseg), dim3(256), 0, sl.hs, H);
+                SF_HIP(hipGetLastError());
+            } else {
+                SF_NCCL(ncclGroupStart());
+                for (int d = 0; d < 2; ++d)
+                    if (m[d]) {
+                        SF_NCCL(ncclSend(sl.tr_send[d], bytes, ncclUint8, rank_ + (d ? 1 : -1), comm_, sl.hs));
+                        SF_NCCL(ncclRecv(sl.tr_recv[d], bytes, ncclUint8, rank_ + (d ? 1 : -1), comm_, sl.hs));
+                    }
+                SF_NCCL(ncclGroupEnd());
+                ++rccl_groups_;
+            }
+            if (trace_) {
+                std::vector<Acc> acc;
+                for (int d = 0; d < 2; ++d)
+                    if (m[d]) {
+                        acc.push_back({sl.tr_send[d], false, 0, nplanes_});
+                        acc.push_back({sl.tr_recv[d], true, 0, nplanes_});
+                    }
+                tr_op(loopback_ ? "tracers_loopback" : "tracers_rccl", sl, sl.hs, acc);
+            }
+            ev_record(sl, &Slab::halo_done, sl.hs);
+        }
+    }
+    // Output kernel of one slab on its compute stream: scatter by id (offset < 0) or pack at offset, see
+    // sfk::tracers_out_kernel. with_ids: also the ids (tr_ids_).
+    void tracers_out(Slab& sl, int offset, bool sample, bool with_ids) {
+        sfk::TracerOutArgs<T> A;
+        A.list = sl.tr_list[tr_cur_];
+        A.n_list = sl.tr_cnt + tr_cur_;
+        A.list_cap = tr_n_;
+        A.dens = sample ? ensure(sl, SF_DENS) : nullptr;
+        A.u = sl.field[SF_U];
+        A.v = sl.field[SF_V];
+        A.w = sl.field[SF_W];
+        A.n_out = tr_n_;
+        A.offset = offset;
+        A.pos = tr_pos_;
+        A.dens_out = tr_dens_;
+        A.speed_out = tr_speed_;
+        A.id_out = with_ids ? tr_ids_ : nullptr;
+        hipLaunchKernelGGL((sfk::tracers_out_kernel<T>), dim3(tracer_grid(tr_n_)), dim3(256), 0, sl.cs, sl.geom, A);
+        SF_HIP(hipGetLastError());
+        // (the dense output arrays are written at disjoint indices by the slabs and read after a host sync: not traced)
+        tr_whole("tracers_out", sl, {A.list, A.u, A.v, A.w, sample ? (const void*)A.dens : A.list}, {});
+    }
+    // Tracers held per local slab now (synchronises).
+    std::vector<int> tracer_counts() {
+        std::vector<int> c(L_, 0);
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            SF_HIP(hipStreamSynchronize(sl.cs));
+            SF_HIP(hipMemcpy(&c[s], sl.tr_cnt + tr_cur_, sizeof(int), hipMemcpyDeviceToHost));
+            c[s] = std::max(0, std::min(c[s], tr_n_));
+        }
+        return c;
+    }
 
     T* alloc_field() {
         T* p = nullptr;
@@ -2126,6 +2488,10 @@ private:
     T* tr_dens_ = nullptr;
     T* tr_speed_ = nullptr;
     int tr_n_ = 0, snap_count_ = 0;
+    // decomposed tracers: dense id-indexed output / owned-order id output, the list of the ping-pong pair in use, the
+    // send capacity in force and the one asked for (sf_tracers_set_capacity; <= 0: the tracer count)
+    int* tr_ids_ = nullptr;
+    int tr_cur_ = 0, tr_cap_ = 0, tr_cap_req_ = 0;
     void* copy_src_ = nullptr;
     void* copy_dst_ = nullptr;
     size_t copy_bytes_ = 0;

@@ -16,7 +16,7 @@ if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
 lib = C.CDLL(LIB_PATH)
 
-SF_OK, SF_ERR_INVALID, SF_ERR_HIP, SF_ERR_RCCL, SF_ERR_HALO_EXCEEDED, SF_ERR_NO_DEVICE = range(6)
+SF_OK, SF_ERR_INVALID, SF_ERR_HIP, SF_ERR_RCCL, SF_ERR_HALO_EXCEEDED, SF_ERR_NO_DEVICE, SF_ERR_TRACER_OVERFLOW = range(7)
 SF_F32, SF_F64 = 0, 1
 FIELD_IDS = {"u": 0, "v": 1, "w": 2, "u0": 3, "v0": 4, "w0": 5, "dens": 6, "dens0": 7,
              "user0": 8, "user1": 9, "user2": 10, "user3": 11}
@@ -33,6 +33,7 @@ ABI_SYMBOLS = (
     "sf_set_iters", "sf_set_coefficients", "sf_sync", "sf_last_error", "sf_timer_start", "sf_timer_stop",
     "sf_measure_copy_bandwidth", "sf_layout_info", "sf_schedule_info", "sf_lin_solve_launches", "sf_snapshot", "sf_snapshot_read",
     "sf_tracers_set", "sf_tracers_advect", "sf_tracers_get", "sf_bind_sources", "sf_transport_info", "sf_snapshot_read_planes",
+    "sf_tracers_owned", "sf_tracers_get_owned", "sf_tracers_set_capacity",
 )
 
 
@@ -82,6 +83,9 @@ lib.sf_snapshot_read_planes.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_voi
 lib.sf_tracers_set.argtypes = [_ctx, C.c_int, C.c_void_p]
 lib.sf_tracers_advect.argtypes = [_ctx]
 lib.sf_tracers_get.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sf_tracers_owned.argtypes = [_ctx, C.POINTER(C.c_int)]
+lib.sf_tracers_get_owned.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.sf_tracers_set_capacity.argtypes = [_ctx, C.c_int]
 lib.sf_layout_info.argtypes = [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
 lib.sf_schedule_info.argtypes = [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 lib.sf_transport_info.argtypes = [_ctx, C.POINTER(C.c_int), C.POINTER(C.c_long)]
@@ -284,6 +288,29 @@ class FluidSolver:
                                     dens.ctypes.data_as(C.c_void_p) if sample else None,
                                     speed.ctypes.data_as(C.c_void_p) if sample else None))
         return xyz, dens, speed
+
+    def tracers_owned(self):
+        """Tracers this context holds now (all of them on one slab or one rank)."""
+        n = C.c_int()
+        self._ck(lib.sf_tracers_owned(self._h, C.byref(n)))
+        return n.value
+
+    def tracers_get_owned(self, sample=True):
+        """This context's tracers in ascending id order: (ids, xyz, dens, speed); dens / speed are zeros when
+        sample is False."""
+        n = self.tracers_owned()
+        ids = np.zeros(n, np.int32)
+        xyz = np.zeros((n, 3), self.np_dtype)
+        dens = np.zeros(n, self.np_dtype)
+        speed = np.zeros(n, self.np_dtype)
+        self._ck(lib.sf_tracers_get_owned(self._h, ids.ctypes.data_as(C.c_void_p), xyz.ctypes.data_as(C.c_void_p),
+                                          dens.ctypes.data_as(C.c_void_p) if sample else None,
+                                          speed.ctypes.data_as(C.c_void_p) if sample else None))
+        return ids, xyz, dens, speed
+
+    def tracers_set_capacity(self, per_direction):
+        """Most tracers one slab may hand to one neighbour per tracers_advect (default: the tracer count)."""
+        self._ck(lib.sf_tracers_set_capacity(self._h, int(per_direction)))
 
     def lin_solve_launches(self, iters):
         return int(lib.sf_lin_solve_launches(self._h, int(iters)))

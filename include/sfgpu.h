@@ -37,7 +37,8 @@ typedef enum sf_status {
     SF_ERR_HIP = 2,           /* a HIP runtime call failed (message has hipGetErrorString) */
     SF_ERR_RCCL = 3,          /* an RCCL call failed */
     SF_ERR_HALO_EXCEEDED = 4, /* advect back-traced beyond the slab's ghost plane (SPEC §4) */
-    SF_ERR_NO_DEVICE = 5      /* no usable gfx950 device: there is NO CPU fallback */
+    SF_ERR_NO_DEVICE = 5,     /* no usable gfx950 device: there is NO CPU fallback */
+    SF_ERR_TRACER_OVERFLOW = 6 /* more tracers left a slab for one neighbour in one call than the capacity holds */
 } sf_status;
 
 typedef enum sf_dtype { SF_F32 = 0, SF_F64 = 1 } sf_dtype;
@@ -146,19 +147,35 @@ int sf_snapshot_read(sf_ctx* ctx, int index, void* host);
  * rank of a decomposed run needs for its own frame file: solver-unidyn.cu:484-490 writes one file per device). */
 int sf_snapshot_read_planes(sf_ctx* ctx, int index, int k_begin, int k_end, void* host);
 
-/* Tracer particles (docs/SPEC.md §6; feeds the write_point_mesh call of solver-unidyn.cu:487). Positions are
- * x y z triples in grid-index coordinates, element type = the context's dtype. Single-slab contexts only.
- * sf_tracers_advect moves them through SF_U/V/W by one dt; sf_tracers_get returns positions and, if the
- * pointers are non-NULL, the density and speed sampled at each tracer. */
+/* Tracer particles (docs/SPEC.md §6, §6.1; feeds the write_point_mesh call of solver-unidyn.cu:487). Positions are
+ * x y z triples in grid-index coordinates, element type = the context's dtype. A tracer's id is its index in the
+ * array given to sf_tracers_set; positions are kept raw (a set followed by a get returns the caller's values).
+ * sf_tracers_advect moves them through SF_U/V/W by one dt; sf_tracers_get returns positions and, if the pointers
+ * are non-NULL, the density and speed sampled at each tracer, all n in id order.
+ * Decomposed contexts: each slab holds the tracers whose sample reads its planes and hands them to the neighbouring
+ * slab when they cross into it; results are bit-identical to one slab. A tracer that moves past a neighbouring slab
+ * in one call is reported by sf_sync as SF_ERR_HALO_EXCEEDED. On several ranks every rank passes the same global
+ * array to sf_tracers_set, and sf_tracers_set and sf_tracers_advect are collective (every rank calls them, as with
+ * vel_step); sf_tracers_get then fails with SF_ERR_INVALID: each rank reads its own with sf_tracers_get_owned. */
 int sf_tracers_set(sf_ctx* ctx, int n, const void* xyz);
 int sf_tracers_advect(sf_ctx* ctx);
 int sf_tracers_get(sf_ctx* ctx, void* xyz, void* dens_sample, void* speed_sample);
+/* Number of tracers this context holds now (all n on one slab). Synchronises. */
+int sf_tracers_owned(const sf_ctx* ctx, int* n_owned);
+/* This context's tracers in ascending id order: ids (int), positions and samples as in sf_tracers_get, each array
+ * sized by sf_tracers_owned; any pointer may be NULL. What one rank writes into its own point-mesh file. */
+int sf_tracers_get_owned(sf_ctx* ctx, int* ids, void* xyz, void* dens_sample, void* speed_sample);
+/* The most tracers one slab may hand to one neighbour in one sf_tracers_advect (default: the tracer count, which
+ * never overflows). Sizes the per-direction message buffers; must be the same on every rank. More migrants than
+ * that are kept by the slab they leave and reported by sf_sync as SF_ERR_TRACER_OVERFLOW. */
+int sf_tracers_set_capacity(sf_ctx* ctx, int per_direction);
 
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);
 int sf_set_coefficients(sf_ctx* ctx, double dt, double diff, double visc);
 
-/* Waits for all streams of the context; returns deferred errors (SF_ERR_HALO_EXCEEDED, HIP faults).
+/* Waits for all streams of the context; returns deferred errors (SF_ERR_HALO_EXCEEDED, SF_ERR_TRACER_OVERFLOW,
+ * HIP faults).
  * Role of the cudaDeviceSynchronize calls of solver-unidyn.cu:369,380,403. */
 int sf_sync(sf_ctx* ctx);
 /* Message of the last failing call on ctx (ctx == NULL: of the last failing sf_create). */
