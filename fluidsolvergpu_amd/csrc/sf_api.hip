@@ -144,6 +144,18 @@ int sf_advect(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w) {
 int sf_project(sf_ctx* ctx, int u, int v, int w, int p, int div) {
     return guarded(ctx, [&](SolverBase& s) { s.project(u, v, w, p, div); });
 }
+int sf_vorticity_magnitude(sf_ctx* ctx, int u, int v, int w, int dst) {
+    return guarded(ctx, [&](SolverBase& s) { s.vorticity_magnitude(u, v, w, dst); });
+}
+int sf_add_forces(sf_ctx* ctx, int u, int v, int w, int dens, int su, int sv, int sw) {
+    return guarded(ctx, [&](SolverBase& s) { s.add_forces(u, v, w, dens, su, sv, sw); });
+}
+int sf_set_vorticity_confinement(sf_ctx* ctx, double eps) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_vorticity_confinement(eps); });
+}
+int sf_set_buoyancy(sf_ctx* ctx, double beta, double ambient, int axis) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_buoyancy(beta, ambient, axis); });
+}
 int sf_snapshot(sf_ctx* ctx, const int* fields, int nfields) {
     return guarded(ctx, [&](SolverBase& s) { s.snapshot(fields, nfields); });
 }

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <chrono>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -76,6 +77,10 @@ public:
     virtual void diffuse(int b, int x, int x0, double diff) = 0;
     virtual void advect(int b, int d, int d0, int u, int v, int w) = 0;
     virtual void project(int u, int v, int w, int p, int div) = 0;
+    virtual void vorticity_magnitude(int u, int v, int w, int dst) = 0;
+    virtual void add_forces(int u, int v, int w, int dens, int su, int sv, int sw) = 0;
+    virtual void set_vorticity_confinement(double eps) = 0;
+    virtual void set_buoyancy(double beta, double ambient, int axis) = 0;
     virtual void set_iters(int iters) = 0;
     virtual void set_coefficients(double dt, double diff, double visc) = 0;
     virtual void sync() = 0;

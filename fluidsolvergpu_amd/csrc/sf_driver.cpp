@@ -24,6 +24,9 @@
 //
 //   sf_driver [--n 64] [--steps 20] [--iters 20] [--dtype f32|f64] [--every 10] [--out DIR]
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
+//             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1]
+// --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
+// BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -57,6 +60,8 @@ static sf_ctx* g_ctx = nullptr;
 
 struct Options {
     int n = 64, steps = 20, iters = 20, every = 10, device = 0, slabs = 1, tracers = 0;
+    double vorticity = 0.0, buoyancy = 0.0, ambient = 0.0;
+    int buoyancy_axis = 1;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
     int rank = 0, world = 1, local_rank = 0;
@@ -151,6 +156,10 @@ static Options parse(int argc, char** argv) {
         else if (s == "--quiet") o.quiet = true;
         else if (s == "--sync-output") o.sync_output = true;
         else if (s == "--tracers") o.tracers = atoi(next());
+        else if (s == "--vorticity") o.vorticity = atof(next());
+        else if (s == "--buoyancy") o.buoyancy = atof(next());
+        else if (s == "--ambient") o.ambient = atof(next());
+        else if (s == "--buoyancy-axis") o.buoyancy_axis = atoi(next());
         // rehearsal of ONE rank's share on a one-GPU box: the geometry, buffers, launches and frame file of rank
         // --rank of --world, halo messages replaced by device-local copies (SF_FLAG_LOOPBACK_HALO), no communicator
         else if (s == "--loopback") o.loopback = true;
@@ -295,6 +304,9 @@ static int run(const Options& o) {
     SF_CHECK_RETURN(sf_set_bnd(g_ctx, 0, SF_DENS));
     // sources stay resident in HBM (SF_USER0..3) and are re-injected every step
     SF_CHECK_RETURN(sf_bind_sources(g_ctx, SF_USER0, SF_USER1, SF_USER2, SF_USER3));
+    // forces (SPEC §8): added by every vel_step to copies of the bound sources
+    SF_CHECK_RETURN(sf_set_vorticity_confinement(g_ctx, o.vorticity));
+    SF_CHECK_RETURN(sf_set_buoyancy(g_ctx, o.buoyancy, o.ambient, o.buoyancy_axis));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

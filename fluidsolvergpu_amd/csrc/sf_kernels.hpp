@@ -2016,6 +2016,132 @@ __global__ void __launch_bounds__(256) project_sub_kernel(Geom g, ProjectArgs<T>
 }
 
 // ---------------------------------------------------------------------------------------------
+// External forces (docs/SPEC.md §8): vorticity confinement and buoyancy, two passes.
+//   pass A (vorticity_mag_kernel): mag = |curl(u, v, w)| on interior cells, set_bnd(0, mag) fused; 4 words per cell
+//   pass B (add_forces_kernel):    s_a += f_a (confinement, curl recomputed at the centre from the same loads, so the
+//                                  same bits), then s_axis += beta*(dens - amb); ~11 words per cell
+// One cell per lane along i, a wave per 64 cells of a row (the mapping of advect_row_kernel), rows in the pitched layout.
+// The i/j/k +-1 neighbours are plain loads: the lines were fetched by the same wave or by the neighbouring rows' waves.
+template <class T>
+struct ForceArgs {
+    const T* u;
+    const T* v;
+    const T* w;
+    T* mag;          // pass A: written; pass B: read at +-1 on each axis
+    const T* dens;   // pass B with buoyancy
+    const T* src[3]; // pass B: the sources read (bound slots, or the slots written themselves)
+    T* dst[3];       // pass B: the sources written
+    T c_grad, eps_h, beta, amb, tiny;
+    int axis;        // buoyancy component 0 = u, 1 = v, 2 = w
+    int split, gap;  // plane-range split of a boundary launch (TileMap::split / gap)
+    int wpr;         // waves per row = ceil(N / 64)
+};
+
+// Wave -> (i, j, local plane). False for lanes past the row end and for waves past the launch.
+__device__ __forceinline__ bool force_cell(const Geom& g, int kb, int ke, int split, int gap, int wpr, int& i, int& j,
+                                           int& kl) {
+    const int lane = (int)threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + ((int)threadIdx.x >> 6));
+    const int row = wv / wpr;  // (wave-uniform: scalar arithmetic)
+    if (row >= g.N * (ke - kb)) return false;
+    const int seg = wv - row * wpr;
+    const int kq = row / g.N;
+    kl = kb + kq + (kq >= split ? gap : 0);
+    j = 1 + row - kq * g.N;
+    i = 1 + seg * 64 + lane;
+    return i <= g.N;
+}
+
+// SPEC §8 vorticity at the cell whose offset is q (neighbours as stored, shells included).
+template <class T>
+__device__ __forceinline__ void curl_at(const Geom& g, const ForceArgs<T>& A, long q, T& wx, T& wy, T& wz) {
+    const long px = g.px, pl = g.plane;
+    const T u_jp = A.u[q + px], u_jm = A.u[q - px], u_kp = A.u[q + pl], u_km = A.u[q - pl];
+    const T v_ip = A.v[q + 1], v_im = A.v[q - 1], v_kp = A.v[q + pl], v_km = A.v[q - pl];
+    const T w_ip = A.w[q + 1], w_im = A.w[q - 1], w_jp = A.w[q + px], w_jm = A.w[q - px];
+    wx = A.c_grad * ((w_jp - w_jm) - (v_kp - v_km));
+    wy = A.c_grad * ((u_kp - u_km) - (w_ip - w_im));
+    wz = A.c_grad * ((v_ip - v_im) - (u_jp - u_jm));
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) vorticity_mag_kernel(Geom g, ForceArgs<T> A, int kb, int ke) {
+    int i, j, kl;
+    if (!force_cell(g, kb, ke, A.split, A.gap, A.wpr, i, j, kl)) return;
+    const long q = row0(g, j, kl) + i;
+    T wx, wy, wz;
+    curl_at(g, A, q, wx, wy, wz);
+    T out[1];
+    out[0] = sqrt((wx * wx + wy * wy) + wz * wz);  // correctly rounded (no fast-math, no rsqrt)
+    A.mag[q] = out[0];
+    emit_shells<T, 1>(A.mag, g, 0, i, j, kl, out, 1, true);
+}
+
+// Every shell cell of the grid that lies next to interior cell (i, j, kl) and to no interior cell nearer (the cells
+// set_bnd derives from it: faces, edges, corners; k-shell only on the wall slabs): dst = src there.
+template <class T>
+__device__ __forceinline__ void copy_shells(const Geom& g, const T* __restrict__ src, T* __restrict__ dst, long q, int i,
+                                            int j, int kl) {
+    const int N = g.N, kg = g.kg0 + kl;
+    const bool ilo = i == 1, ihi = i == N, jlo = j == 1, jhi = j == N;
+    const bool klo = g.wall_lo && kg == 1, khi = g.wall_hi && kg == N;
+    if (!(ilo | ihi | jlo | jhi | klo | khi)) return;
+    for (int dk = -1; dk <= 1; ++dk) {
+        if ((dk < 0 && !klo) || (dk > 0 && !khi)) continue;
+        for (int dj = -1; dj <= 1; ++dj) {
+            if ((dj < 0 && !jlo) || (dj > 0 && !jhi)) continue;
+            for (int di = -1; di <= 1; ++di) {
+                if ((di < 0 && !ilo) || (di > 0 && !ihi) || (di == 0 && dj == 0 && dk == 0)) continue;
+                const long o = q + di + (long)dj * g.px + (long)dk * g.plane;
+                dst[o] = src[o];
+            }
+        }
+    }
+}
+
+// VORT: eps != 0, BUOY: beta != 0 (a zero coefficient's term is not evaluated: SPEC §8). BOUND: some dst[a] is not
+// src[a] (sources bound to resident slots): the interior gets src + f, the shells a copy of src.
+template <class T, bool VORT, bool BUOY, bool BOUND>
+__global__ void __launch_bounds__(256) add_forces_kernel(Geom g, ForceArgs<T> A, int kb, int ke) {
+    int i, j, kl;
+    if (!force_cell(g, kb, ke, A.split, A.gap, A.wpr, i, j, kl)) return;
+    const long q = row0(g, j, kl) + i;
+    T s[3] = {};
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        if (VORT || BOUND || a == A.axis) s[a] = A.src[a][q];
+    if constexpr (VORT) {
+        const long px = g.px, pl = g.plane;
+        const T m_ip = A.mag[q + 1], m_im = A.mag[q - 1], m_jp = A.mag[q + px], m_jm = A.mag[q - px];
+        const T m_kp = A.mag[q + pl], m_km = A.mag[q - pl];
+        T wx, wy, wz;
+        curl_at(g, A, q, wx, wy, wz);
+        const T ex = A.c_grad * (m_ip - m_im);
+        const T ey = A.c_grad * (m_jp - m_jm);
+        const T ez = A.c_grad * (m_kp - m_km);
+        const T len = sqrt((ex * ex + ey * ey) + ez * ez);
+        const T r = T(1) / (len + A.tiny);  // correctly rounded division
+        const T nx = ex * r, ny = ey * r, nz = ez * r;
+        s[0] = s[0] + A.eps_h * ((ny * wz) - (nz * wy));
+        s[1] = s[1] + A.eps_h * ((nz * wx) - (nx * wz));
+        s[2] = s[2] + A.eps_h * ((nx * wy) - (ny * wx));
+    }
+    if constexpr (BUOY) {
+        const T fb = A.beta * (A.dens[q] - A.amb);
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            if (a == A.axis) s[a] = s[a] + fb;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!(VORT || BOUND || a == A.axis)) continue;  // buoyancy in place: one component changes
+        A.dst[a][q] = s[a];
+        if constexpr (BOUND)
+            if (A.dst[a] != A.src[a]) copy_shells(g, A.src[a], A.dst[a], q, i, j, kl);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Stand-alone set_bnd (SPEC §3), three dependent passes reading memory exactly like the oracle.
 // Only used by sf_set_bnd(); the step kernels fuse it. pass 0 = faces, 1 = edges, 2 = corners.
 template <class T>

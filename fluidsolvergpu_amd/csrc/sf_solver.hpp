@@ -20,11 +20,14 @@ template <class T>
 class Solver final : public SolverBase {
     static constexpr int W = sfk::VecT<T>::W;
     static constexpr int NSCRATCH = 3;
+    // internal slot for |curl u| of the forces (SPEC §8) while they are issued: it aliases scratch[0], which no solve
+    // holds at that point, and is null otherwise (exchange() addresses fields by slot)
+    static constexpr int MAG_SLOT = SF_NUM_FIELDS;
 
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
         sfk::Geom geom{};
-        T* field[SF_NUM_FIELDS] = {};
+        T* field[SF_NUM_FIELDS + 1] = {};
         T* scratch[NSCRATCH] = {};
         T* snap[4] = {};               // snapshot buffers for asynchronous output
         hipStream_t os = nullptr;      // output (copy) stream
@@ -518,6 +521,38 @@ public:
         op_project(u, v, w, p, div);
     }
 
+    // SPEC §8 vorticity into dst (set_bnd(0) and ghost planes included)
+    void vorticity_magnitude(int u, int v, int w, int dst) override {
+        for (int f : {u, v, w, dst}) check_field(f);
+        SF_REQUIRE(dst != u && dst != v && dst != w, "vorticity_magnitude: dst must not be u, v or w");
+        SF_HIP(hipSetDevice(device_));
+        op_vorticity(u, v, w, dst);
+    }
+
+    // SPEC §8 add_forces, the sources updated in place
+    void add_forces(int u, int v, int w, int dens, int su, int sv, int sw) override {
+        const int all[7] = {u, v, w, dens, su, sv, sw};
+        for (int a = 0; a < 7; ++a) {
+            check_field(all[a]);
+            for (int c = a + 1; c < 7; ++c) SF_REQUIRE(all[a] != all[c], "add_forces: slots must be distinct");
+        }
+        SF_HIP(hipSetDevice(device_));
+        const int s[3] = {su, sv, sw};
+        op_add_forces(u, v, w, dens, s, s);
+    }
+
+    void set_vorticity_confinement(double eps) override {
+        SF_REQUIRE(std::isfinite(eps) && eps >= 0.0, "vorticity confinement: eps must be finite and >= 0");
+        eps_ = (T)eps;
+    }
+    void set_buoyancy(double beta, double ambient, int axis) override {
+        SF_REQUIRE(std::isfinite(beta) && std::isfinite(ambient), "buoyancy: beta and ambient must be finite");
+        SF_REQUIRE(axis >= 0 && axis <= 2, "buoyancy: axis must be 0, 1 or 2");
+        beta_ = (T)beta;
+        amb_ = (T)ambient;
+        axis_ = axis;
+    }
+
     void bind_sources(int su, int sv, int sw, int sd) override {
         const int b[4] = {su, sv, sw, sd};
         const int own[4] = {SF_U0, SF_V0, SF_W0, SF_DENS0};
@@ -538,6 +573,8 @@ public:
         std::vector<T*> before, after;
         int K;
         T dt, diff, visc;
+        T eps, beta, amb;  // forces (SPEC §8): their scalars are baked into the captured launches
+        int axis;
         int bound[4];
         hipGraphExec_t exec;
     };
@@ -548,6 +585,7 @@ public:
         for (T* f : sl.scratch) st.push_back(f);
         return st;
     }
+    static bool same_bits(T a, T b) { return std::memcmp(&a, &b, sizeof(T)) == 0; }
     void apply_state(const std::vector<T*>& st) {
         Slab& sl = slabs_[0];
         size_t q = 0;
@@ -565,7 +603,8 @@ public:
             if (bound_[q] >= 0) ensure(sl, bound_[q]);  // no allocation may happen inside a capture
         const std::vector<T*> before = pointer_state();
         for (GraphEntry& e : graph_cache_)
-            if (e.op == op && e.K == K_ && e.dt == dt_ && e.diff == diff_ && e.visc == visc_ &&
+            if (e.op == op && e.K == K_ && e.dt == dt_ && e.diff == diff_ && e.visc == visc_ && same_bits(e.eps, eps_) &&
+                same_bits(e.beta, beta_) && same_bits(e.amb, amb_) && e.axis == axis_ &&
                 std::equal(e.bound, e.bound + 4, bound_) && e.before == before) {
                 SF_HIP(hipGraphLaunch(e.exec, sl.cs));
                 apply_state(e.after);
@@ -590,6 +629,10 @@ public:
         e.dt = dt_;
         e.diff = diff_;
         e.visc = visc_;
+        e.eps = eps_;
+        e.beta = beta_;
+        e.amb = amb_;
+        e.axis = axis_;
         std::copy(bound_, bound_ + 4, e.bound);
         SF_HIP(hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0));
         SF_HIP(hipGraphDestroy(graph));
@@ -616,13 +659,21 @@ public:
         // leave the i-shell unwritten (no partial writes to HBM: a 512^3 last pass takes 441 instead of 520 us). K_ = 0
         // runs no sweep: the fields keep their caller-written shells and are read from memory as before.
         const bool dead = ishell_skip_ && K_ >= 1 && dead_ishell_opt_;
+        // SPEC §8: with a force on, the sources (bound slots, or the x0 slots themselves) plus the forces go into the
+        // x0 slots first, and the step continues as with unbound sources
+        const bool forces = eps_ != T(0) || beta_ != T(0);
+        if (forces) {
+            int src[3];
+            for (int q = 0; q < 3; ++q) src[q] = bound_[q] >= 0 ? bound_[q] : vel0[q];
+            op_add_forces(SF_U, SF_V, SF_W, SF_DENS, src, vel0);
+        }
         dead_ishell_ = dead;
-        if (bound_[0] >= 0 && bound_[1] >= 0 && bound_[2] >= 0) {
+        if (!forces && bound_[0] >= 0 && bound_[1] >= 0 && bound_[2] >= 0) {
             const int src[3] = {bound_[0], bound_[1], bound_[2]};
             op_diffuse_src<3>(vel, vel0, b123, src, a, T(1) + T(6) * a, K_);
         } else {
             for (int q = 0; q < 3; ++q)
-                if (bound_[q] >= 0) copy_field(vel0[q], bound_[q]);
+                if (!forces && bound_[q] >= 0) copy_field(vel0[q], bound_[q]);
             op_add_source<3>(vel, vel0);
             swap_slots(SF_U0, SF_U);
             swap_slots(SF_V0, SF_V);
@@ -2451,6 +2502,122 @@ private:
         exchange<3>(uvw);
     }
 
+    // ---- external forces (SPEC §8) ------------------------------------------------------------------------------
+    sfk::ForceArgs<T> force_args() const {
+        const T Nf = (T)N_;
+        const T h = T(1) / Nf;
+        sfk::ForceArgs<T> A{};
+        A.c_grad = T(0.5) * Nf;
+        A.eps_h = eps_ * h;
+        A.beta = beta_;
+        A.amb = amb_;
+        A.tiny = (T)1e-20;
+        A.axis = axis_;
+        A.split = split_;
+        A.gap = gap_;
+        A.wpr = ceil_div(N_, 64);
+        return A;
+    }
+    unsigned force_blocks(int nplanes) const { return (unsigned)ceil_div((long)ceil_div(N_, 64) * N_ * nplanes, 4L); }
+
+    // pass A: mag = |curl(u, v, w)| on the owned planes with its shells, then its ghost planes
+    void op_vorticity(int u, int v, int w, int mag) {
+        for (Slab& sl : slabs_)
+            for (int f : {u, v, w, mag}) ensure(sl, f);
+        if (trace_) {
+            acc_name_ = "vorticity";
+            acc_fn_ = [&](Slab& sl, int a, int b_, std::vector<Acc>& acc) {
+                int lo, hi;
+                wr_range(sl, a, b_, lo, hi);
+                acc.push_back({sl.field[u], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[v], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[w], false, a, b_});
+                acc.push_back({sl.field[mag], true, lo, hi});
+            };
+        }
+        for_planes([&](Slab& sl, int kb, int ke) {
+            sfk::ForceArgs<T> A = force_args();
+            A.u = sl.field[u];
+            A.v = sl.field[v];
+            A.w = sl.field[w];
+            A.mag = sl.field[mag];
+            hipLaunchKernelGGL((sfk::vorticity_mag_kernel<T>), dim3(force_blocks(ke - kb)), dim3(256), 0, sl.cur, sl.geom,
+                               A, kb, ke);
+        });
+        acc_fn_ = nullptr;
+        const int m[1] = {mag};
+        exchange<1>(m);
+    }
+
+    template <bool VORT, bool BUOY, bool BOUND>
+    void launch_forces(Slab& sl, const sfk::ForceArgs<T>& A, int kb, int ke) {
+        hipLaunchKernelGGL((sfk::add_forces_kernel<T, VORT, BUOY, BOUND>), dim3(force_blocks(ke - kb)), dim3(256), 0, sl.cur,
+                           sl.geom, A, kb, ke);
+    }
+
+    // add_forces(u, v, w, dens, src -> dst): dst_a = src_a + f_a on interior cells, src's shells copied where dst is
+    // another slot (bound sources), then the ghost planes of dst. |curl u| lives in scratch[0] meanwhile.
+    void op_add_forces(int u, int v, int w, int dens, const int (&src)[3], const int (&dst)[3]) {
+        const bool vort = eps_ != T(0), buoy = beta_ != T(0);
+        if (!vort && !buoy) return;
+        const bool bound = src[0] != dst[0] || src[1] != dst[1] || src[2] != dst[2];
+        for (Slab& sl : slabs_) {
+            for (int f : {u, v, w, dens}) ensure(sl, f);
+            for (int a = 0; a < 3; ++a) {
+                ensure(sl, src[a]);
+                ensure(sl, dst[a]);
+            }
+        }
+        if (vort) {
+            for (Slab& sl : slabs_) sl.field[MAG_SLOT] = sl.scratch[0];
+            op_vorticity(u, v, w, MAG_SLOT);
+        }
+        if (trace_) {
+            acc_name_ = "add_forces";
+            acc_fn_ = [&, vort, buoy](Slab& sl, int a, int b_, std::vector<Acc>& acc) {
+                int lo, hi;
+                wr_range(sl, a, b_, lo, hi);
+                if (vort) {
+                    acc.push_back({sl.field[u], false, a - 1, b_ + 1});
+                    acc.push_back({sl.field[v], false, a - 1, b_ + 1});
+                    acc.push_back({sl.field[w], false, a, b_});
+                    acc.push_back({sl.field[MAG_SLOT], false, a - 1, b_ + 1});
+                }
+                if (buoy) acc.push_back({sl.field[dens], false, a, b_});
+                for (int c = 0; c < 3; ++c) {
+                    const bool copy = src[c] != dst[c];  // shells copied too (wall planes on the end slabs)
+                    if (!(vort || copy || c == axis_)) continue;
+                    acc.push_back({sl.field[src[c]], false, copy ? lo : a, copy ? hi : b_});
+                    acc.push_back({sl.field[dst[c]], true, copy ? lo : a, copy ? hi : b_});
+                }
+            };
+        }
+        for_planes([&](Slab& sl, int kb, int ke) {
+            sfk::ForceArgs<T> A = force_args();
+            A.u = sl.field[u];
+            A.v = sl.field[v];
+            A.w = sl.field[w];
+            A.mag = vort ? sl.field[MAG_SLOT] : nullptr;
+            A.dens = sl.field[dens];
+            for (int a = 0; a < 3; ++a) {
+                A.src[a] = sl.field[src[a]];
+                A.dst[a] = sl.field[dst[a]];
+            }
+            if (vort && buoy)
+                bound ? launch_forces<true, true, true>(sl, A, kb, ke) : launch_forces<true, true, false>(sl, A, kb, ke);
+            else if (vort)
+                bound ? launch_forces<true, false, true>(sl, A, kb, ke) : launch_forces<true, false, false>(sl, A, kb, ke);
+            else
+                bound ? launch_forces<false, true, true>(sl, A, kb, ke) : launch_forces<false, true, false>(sl, A, kb, ke);
+        });
+        acc_fn_ = nullptr;
+        // the sources' ghost planes: the fused first sweep of diffuse evaluates on the first ghost plane and reads x0
+        // and the initial iterate there (see op_project)
+        exchange<3>(dst);
+        if (vort)
+            for (Slab& sl : slabs_) sl.field[MAG_SLOT] = nullptr;
+    }
+
     int N_, K_, device_;
     int L_ = 1, nranks_ = 1, rank_ = 0, P_ = 1, G_ = 1;
     int fuse_maxvec_ = 512, ovl_mode_ = 1;  // fuse_maxvec_: widest row (vectors) the fused kernels take
@@ -2460,6 +2627,8 @@ private:
     std::vector<GraphEntry> graph_cache_;
     int split_ = INT_MAX, gap_ = 0;  // plane-range split of the launch being issued (for_planes)
     T dt_{}, diff_{}, visc_{};
+    T eps_{}, beta_{}, amb_{};  // forces of SPEC §8 (0: off)
+    int axis_ = 1;
     int num_cu_ = 256;
     int nzl_ = 0, lead_ = 0, px_ = 0, nplanes_ = 0, nt_mode_ = 2;
     int advect_row_ = 1;  // 0 gather form always, 1 one cell per lane for the three velocity components, 2 / 3 always

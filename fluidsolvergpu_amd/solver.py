@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "sf_measure_copy_bandwidth", "sf_layout_info", "sf_schedule_info", "sf_lin_solve_launches", "sf_snapshot", "sf_snapshot_read",
     "sf_tracers_set", "sf_tracers_advect", "sf_tracers_get", "sf_bind_sources", "sf_transport_info", "sf_snapshot_read_planes",
     "sf_tracers_owned", "sf_tracers_get_owned", "sf_tracers_set_capacity",
+    "sf_set_vorticity_confinement", "sf_set_buoyancy", "sf_vorticity_magnitude", "sf_add_forces",
 )
 
 
@@ -69,6 +70,10 @@ lib.sf_lin_solve.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, C.c_do
 lib.sf_diffuse.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_double]
 lib.sf_advect.argtypes = [_ctx] + [C.c_int] * 6
 lib.sf_project.argtypes = [_ctx] + [C.c_int] * 5
+lib.sf_vorticity_magnitude.argtypes = [_ctx] + [C.c_int] * 4
+lib.sf_add_forces.argtypes = [_ctx] + [C.c_int] * 7
+lib.sf_set_vorticity_confinement.argtypes = [_ctx, C.c_double]
+lib.sf_set_buoyancy.argtypes = [_ctx, C.c_double, C.c_double, C.c_int]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -227,6 +232,21 @@ class FluidSolver:
 
     def project(self, u, v, w, p, div):
         self._ck(lib.sf_project(self._h, _fid(u), _fid(v), _fid(w), _fid(p), _fid(div)))
+
+    # -- external forces (docs/SPEC.md §8) ---------------------------------------------------
+    def set_vorticity_confinement(self, eps):
+        """Vorticity confinement strength applied by vel_step (0 = off, the default)."""
+        self._ck(lib.sf_set_vorticity_confinement(self._h, float(eps)))
+
+    def set_buoyancy(self, beta, ambient=0.0, axis=1):
+        """Buoyancy beta*(dens - ambient) on velocity component `axis` (0 = u, 1 = v, 2 = w) in vel_step (beta 0 = off)."""
+        self._ck(lib.sf_set_buoyancy(self._h, float(beta), float(ambient), int(axis)))
+
+    def vorticity_magnitude(self, u, v, w, dst):
+        self._ck(lib.sf_vorticity_magnitude(self._h, _fid(u), _fid(v), _fid(w), _fid(dst)))
+
+    def add_forces(self, u, v, w, dens, su, sv, sw):
+        self._ck(lib.sf_add_forces(self._h, _fid(u), _fid(v), _fid(w), _fid(dens), _fid(su), _fid(sv), _fid(sw)))
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

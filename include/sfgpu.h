@@ -135,6 +135,20 @@ int sf_diffuse(sf_ctx* ctx, int b, int x, int x0, double diff);
 int sf_advect(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w);
 int sf_project(sf_ctx* ctx, int u, int v, int w, int p, int div);
 
+/* External forces of docs/SPEC.md §8 (Fedkiw, Stam & Jensen, "Visual Simulation of Smoke", SIGGRAPH 2001).
+ * With a non-zero coefficient, vel_step first adds the forces of the state at entry to its sources (the x0 slots, or
+ * copies of the bound slots written into them), then runs as before; with both zero it is the §3 step exactly.
+ * Coefficients are per context and, like sf_set_coefficients, must be the same on every rank.
+ *   eps:  vorticity confinement strength (finite, >= 0; 0 = off, the default); the force is eps*h*(n x omega).
+ *   beta: buoyancy beta*(dens - ambient) added to velocity component `axis` (0 = u, 1 = v, 2 = w); finite; 0 = off. */
+int sf_set_vorticity_confinement(sf_ctx* ctx, double eps);
+int sf_set_buoyancy(sf_ctx* ctx, double beta, double ambient, int axis);
+/* The two passes singly. sf_vorticity_magnitude: dst = |curl(u, v, w)| on interior cells, then set_bnd(0, dst);
+ * dst must not be u, v or w. sf_add_forces: su, sv, sw += the forces of (u, v, w, dens) on interior cells, with the
+ * coefficients in force (a zero coefficient's term is not evaluated); all seven slots distinct. */
+int sf_vorticity_magnitude(sf_ctx* ctx, int u, int v, int w, int dst);
+int sf_add_forces(sf_ctx* ctx, int u, int v, int w, int dens, int su, int sv, int sw);
+
 /* Asynchronous frame output (the reference blocks on cudaDeviceSynchronize + cudaMemcpy +
  * per-value sprintf every output step, solver-unidyn.cu:475-487). sf_snapshot copies up to 4 fields into
  * context-owned snapshot buffers on the compute stream (device to device, ordered after everything issued
