@@ -35,7 +35,6 @@ class Solver final : public SolverBase {
         hipStream_t cs = nullptr;   // compute (interior planes, whole-field operators)
         hipStream_t bs = nullptr;   // boundary planes of a decomposed grid: runs beside the interior launch
         hipStream_t hs = nullptr;   // halo
-        hipStream_t cur = nullptr;  // where the launch being issued goes (cs or bs)
         hipEvent_t cs_mark = nullptr;
         hipEvent_t boundary_done = nullptr;
         hipEvent_t halo_done = nullptr;
@@ -48,6 +47,18 @@ class Solver final : public SolverBase {
         sfk::TracerRec<T>* tr_send[2] = {};
         sfk::TracerRec<T>* tr_recv[2] = {};
         int* tr_flag = nullptr;
+    };
+
+    // One launch of an operator as for_planes issues it: planes [kb, ke) of slab sl on stream st (sl.cs or sl.bs).
+    // The boundary launch of a decomposed grid covers the first and the last `split` interior planes in one grid:
+    // its logical plane t sits at kb + t + (t >= split ? gap : 0) (sfk::TileMap). Other launches: split = INT_MAX,
+    // gap = 0.
+    struct Launch {
+        Slab& sl;
+        hipStream_t st;
+        int kb, ke;
+        int split = INT_MAX, gap = 0;
+        bool is_split() const { return split != INT_MAX; }
     };
 
 public:
@@ -138,7 +149,6 @@ public:
             const unsigned ev_local = hipEventDisableTiming | (unsigned)hipEventDisableSystemFence;
             const unsigned ev_halo = ((nranks_ > 1 && !loopback_) || rccl_self_) ? (unsigned)hipEventDisableTiming : ev_local;
             SF_HIP(hipEventCreateWithFlags(&sl.cs_mark, ev_local));
-            sl.cur = sl.cs;
             {
                 // One slab per process (production): every halo is an RCCL message, and the chain
                 // boundary launch -> message -> next boundary launch is what limits a pair once the messages take as
@@ -254,11 +264,11 @@ public:
         int best_m = 0;
         for (int q = 0; q < 3; ++q) {
             trap_m_ = cand[q];
-            op_lin_solve<1>(x, x0, b0, a, c, 10);  // warm-up (first use of the communicator, caches)
+            op_lin_solve<1>(x, x0, b0, a, c, 10, false);  // warm-up (first use of the communicator, caches)
             drain();
             line_up();
             const auto t0 = std::chrono::steady_clock::now();
-            for (int r = 0; r < 3; ++r) op_lin_solve<1>(x, x0, b0, a, c, 20);
+            for (int r = 0; r < 3; ++r) op_lin_solve<1>(x, x0, b0, a, c, 20, false);
             drain();
             const double t = slowest(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
             if (q == 0 || t < 0.97 * best) {
@@ -271,17 +281,16 @@ public:
         // Same question for "u, v, w one field at a time" (Infinity-Cache resident, three small messages per pair)
         // against "three fields per launch" (one message of three times the size: the message latency is paid once):
         // the first wins when a pair is compute-bound, the second when the messages are the critical chain.
-        const double one = 3.0 * (double)(N_ + 2) * (N_ + 2) * nplanes_ * sizeof(T);
-        if (std::getenv("SF_SPLIT_FIELDS") == nullptr && one <= 0.9 * 256.0 * 1048576.0) {
+        if (std::getenv("SF_SPLIT_FIELDS") == nullptr && fits_ic(solve_bytes())) {
             const int vel[3] = {SF_U, SF_V, SF_W}, vel0[3] = {SF_U0, SF_V0, SF_W0}, b123[3] = {1, 2, 3};
             double t_split = 0;
             for (int q = 0; q < 2; ++q) {
                 split_fields_ = q == 0 ? 1 : 0;
-                op_lin_solve<3>(vel, vel0, b123, a, c, 4);
+                op_lin_solve<3>(vel, vel0, b123, a, c, 4, false);
                 drain();
                 line_up();
                 const auto t0 = std::chrono::steady_clock::now();
-                for (int r = 0; r < 2; ++r) op_lin_solve<3>(vel, vel0, b123, a, c, 20);
+                for (int r = 0; r < 2; ++r) op_lin_solve<3>(vel, vel0, b123, a, c, 20, false);
                 drain();
                 const double t = slowest(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
                 if (q == 0)
@@ -484,7 +493,7 @@ public:
         SF_REQUIRE(iters >= 0, "iters must be >= 0");
         SF_HIP(hipSetDevice(device_));
         const int xs[1] = {x}, x0s[1] = {x0}, bs[1] = {b};
-        op_lin_solve<1>(xs, x0s, bs, (T)a, (T)c, iters);
+        op_lin_solve<1>(xs, x0s, bs, (T)a, (T)c, iters, false);
     }
 
     void diffuse(int b, int x, int x0, double diff) override {
@@ -495,7 +504,7 @@ public:
         SF_HIP(hipSetDevice(device_));
         const int xs[1] = {x}, x0s[1] = {x0}, bs[1] = {b};
         const T a = diffusion_a((T)diff);
-        op_lin_solve<1>(xs, x0s, bs, a, T(1) + T(6) * a, K_);
+        op_lin_solve<1>(xs, x0s, bs, a, T(1) + T(6) * a, K_, false);
     }
 
     void advect(int b, int d, int d0, int u, int v, int w) override {
@@ -508,7 +517,7 @@ public:
         SF_REQUIRE(d != d0 && d != u && d != v && d != w, "advect: output must not alias an input");
         SF_HIP(hipSetDevice(device_));
         const int ds[1] = {d}, d0s[1] = {d0}, bs[1] = {b};
-        op_advect<1>(ds, d0s, bs, u, v, w);
+        op_advect<1>(ds, d0s, bs, u, v, w, false);
     }
 
     void project(int u, int v, int w, int p, int div) override {
@@ -667,10 +676,9 @@ public:
             for (int q = 0; q < 3; ++q) src[q] = bound_[q] >= 0 ? bound_[q] : vel0[q];
             op_add_forces(SF_U, SF_V, SF_W, SF_DENS, src, vel0);
         }
-        dead_ishell_ = dead;
         if (!forces && bound_[0] >= 0 && bound_[1] >= 0 && bound_[2] >= 0) {
             const int src[3] = {bound_[0], bound_[1], bound_[2]};
-            op_diffuse_src<3>(vel, vel0, b123, src, a, T(1) + T(6) * a, K_);
+            op_diffuse_src<3>(vel, vel0, b123, src, a, T(1) + T(6) * a, K_, dead);
         } else {
             for (int q = 0; q < 3; ++q)
                 if (!forces && bound_[q] >= 0) copy_field(vel0[q], bound_[q]);
@@ -678,17 +686,14 @@ public:
             swap_slots(SF_U0, SF_U);
             swap_slots(SF_V0, SF_V);
             swap_slots(SF_W0, SF_W);
-            op_lin_solve<3>(vel, vel0, b123, a, T(1) + T(6) * a, K_);
+            op_lin_solve<3>(vel, vel0, b123, a, T(1) + T(6) * a, K_, dead);
         }
-        dead_ishell_ = false;
         op_project(SF_U, SF_V, SF_W, SF_U0, SF_V0, dead, dead);
         swap_slots(SF_U0, SF_U);
         swap_slots(SF_V0, SF_V);
         swap_slots(SF_W0, SF_W);
         // the advected velocity goes straight into the second projection: same argument as for the diffused one
-        dead_ishell_ = dead;
-        op_advect<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0);
-        dead_ishell_ = false;
+        op_advect<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
         op_project(SF_U, SF_V, SF_W, SF_U0, SF_V0, dead, false);
     }
 
@@ -698,14 +703,14 @@ public:
         const T a = diffusion_a(diff_);
         if (bound_[3] >= 0) {
             const int src[1] = {bound_[3]};
-            op_diffuse_src<1>(x, x0, b0, src, a, T(1) + T(6) * a, K_);
+            op_diffuse_src<1>(x, x0, b0, src, a, T(1) + T(6) * a, K_, false);
         } else {
             op_add_source<1>(x, x0);
             swap_slots(SF_DENS0, SF_DENS);
-            op_lin_solve<1>(x, x0, b0, a, T(1) + T(6) * a, K_);
+            op_lin_solve<1>(x, x0, b0, a, T(1) + T(6) * a, K_, false);
         }
         swap_slots(SF_DENS0, SF_DENS);
-        op_advect<1>(x, x0, b0, SF_U, SF_V, SF_W);
+        op_advect<1>(x, x0, b0, SF_U, SF_V, SF_W, false);
     }
 
     void set_iters(int iters) override {
@@ -1068,7 +1073,7 @@ public:
 
     int lin_solve_launches(int iters) const override {
         int n = 0;
-        for (int it = 0; it < iters; ++n) it += sweeps_in_launch(it, iters, false);
+        for (int it = 0; it < iters; ++n) it += sweeps_in_launch(it, iters, false, false);
         return n;
     }
 
@@ -1317,8 +1322,8 @@ private:
                                 hipMemcpyDeviceToHost, sl.cs));
     }
 
-    // 1-D banded grid for the one-vector-per-thread kernels: fills block, returns the map and block count.
-    sfk::TileMap flat_map(int nplanes, dim3& block, unsigned& nblocks) const {
+    // 1-D banded grid of launch L for the one-vector-per-thread kernels: fills block, returns the map and block count.
+    sfk::TileMap flat_map(const Launch& L, dim3& block, unsigned& nblocks) const {
         // these kernels take their i+-1 values by loads, so a row tile may have any width: one tile per row up
         // to 256 vectors (no idle lanes for N = 324, 408, ...), 64-lane tiles beyond
         const int nvec = ceil_div(N_, W);
@@ -1333,14 +1338,14 @@ private:
         m.band = (m.gy >= 16) ? ceil_div(m.gy, 8) : 0;
         m.ishell_mem = 1;
         m.ishell_write = 1;
-        m.split = split_;
-        m.gap = gap_;
+        m.split = L.split;
+        m.gap = L.gap;
         const long per_plane = m.band > 0 ? (long)m.nxcd * m.gx * m.band : (long)m.gx * m.gy;
-        nblocks = (unsigned)(per_plane * nplanes);
+        nblocks = (unsigned)(per_plane * (L.ke - L.kb));
         return m;
     }
 
-    // Runs `launch(slab, kb, ke)` over the interior planes of every slab. With P > 1 the two
+    // Runs `launch(Launch)` over the interior planes of every slab. With P > 1 the two
     // slab-boundary planes go first, their completion is recorded, and the rest follows so that the
     // halo exchange issued by the caller overlaps the interior work.
     // Streams of a decomposed grid (P > 1). Per operator and slab:
@@ -1366,7 +1371,6 @@ private:
         bool write;
         int lo, hi;
     };
-    using AccFn = std::function<void(Slab&, int, int, std::vector<Acc>&)>;
     void trace_open() {
         const char* t = std::getenv("SF_TRACE_SCHEDULE");
         if (!t || !*t) return;
@@ -1443,50 +1447,52 @@ private:
         pending_join_ = false;
     }
 
-    template <class F>
-    void for_planes(F launch, int depth = 1, bool can_split = true, bool interior_reads_ghosts = false) {
+    // name, acc: the trace of the operator. acc(sl, a, b, lo, hi, out) appends its accesses over the planes [a, b) of
+    // one launch; [lo, hi) is that range widened by the shell plane a wall slab's launch also writes (wr_range).
+    // grow > 0 (lin_solve only): the boundary launch takes that many more planes per side than the last one did, so
+    // this interior launch reads nothing a boundary launch wrote since the last resync and the compute stream needs no
+    // cross-stream wait (see op_lin_solve).
+    template <class AccF, class F>
+    void for_planes(const char* name, AccF acc, F launch, int depth = 1, int grow = 0, bool interior_reads_ghosts = false) {
         // the exchange that follows ships G_ planes per side, so at least G_ planes per side must come out of
         // the boundary launch (whose completion the halo stream waits for), not out of the interior launch
         depth = std::max(depth, G_);
         const int kb = G_, ke = G_ + nzl_;
-        // trace: the accesses of this operator over the plane ranges one launch covers
         auto emit = [&](Slab& sl, hipStream_t st, int a0, int a1, int b0 = 0, int b1 = 0) {
-            if (!trace_ || !acc_fn_) return;
-            std::vector<Acc> acc;
-            acc_fn_(sl, a0, a1, acc);
-            if (b1 > b0) acc_fn_(sl, b0, b1, acc);
-            tr_op(acc_name_, sl, st, acc);
+            if (!trace_) return;
+            std::vector<Acc> out;
+            int lo, hi;
+            wr_range(sl, a0, a1, lo, hi);
+            acc(sl, a0, a1, lo, hi, out);
+            if (b1 > b0) {
+                wr_range(sl, b0, b1, lo, hi);
+                acc(sl, b0, b1, lo, hi, out);
+            }
+            tr_op(name, sl, st, out);
+        };
+        auto run = [&](Slab& sl, hipStream_t st, int a, int b) {
+            launch(Launch{sl, st, a, b});
+            emit(sl, st, a, b);
         };
         if (P_ == 1) {
-            slabs_[0].cur = slabs_[0].cs;
-            launch(slabs_[0], kb, ke);
-            emit(slabs_[0], slabs_[0].cs, kb, ke);
+            run(slabs_[0], slabs_[0].cs, kb, ke);
             SF_HIP(hipGetLastError());
             return;
         }
-        // trap_extra_ > 0 (lin_solve only): the boundary launch takes that many more planes per side than the last
-        // one did, so this interior launch reads nothing a boundary launch wrote since the last resync and the
-        // compute stream needs no cross-stream wait (see op_lin_solve)
-        const int extra = (can_split && nzl_ > 2 * (depth + trap_extra_) && split_enabled_ && !interior_reads_ghosts)
-                              ? trap_extra_ : 0;
-        const bool two_streams = can_split && nzl_ > 2 * depth && split_enabled_ && !interior_reads_ghosts;
+        const int extra = (nzl_ > 2 * (depth + grow) && split_enabled_ && !interior_reads_ghosts) ? grow : 0;
+        const bool two_streams = nzl_ > 2 * depth && split_enabled_ && !interior_reads_ghosts;
         if (!two_streams) join();
         depth += extra;
         for (Slab& sl : slabs_) {
             if (!two_streams) {
-                sl.cur = sl.cs;
                 if (nzl_ <= 2 * depth) {
-                    launch(sl, kb, ke);
-                    emit(sl, sl.cs, kb, ke);
+                    run(sl, sl.cs, kb, ke);
                     ev_record(sl, &Slab::boundary_done, sl.cs);
                 } else {
-                    launch(sl, kb, kb + depth);
-                    emit(sl, sl.cs, kb, kb + depth);
-                    launch(sl, ke - depth, ke);
-                    emit(sl, sl.cs, ke - depth, ke);
+                    run(sl, sl.cs, kb, kb + depth);
+                    run(sl, sl.cs, ke - depth, ke);
                     ev_record(sl, &Slab::boundary_done, sl.cs);
-                    launch(sl, kb + depth, ke - depth);
-                    emit(sl, sl.cs, kb + depth, ke - depth);
+                    run(sl, sl.cs, kb + depth, ke - depth);
                 }
                 continue;
             }
@@ -1496,25 +1502,18 @@ private:
             ev_record(sl, &Slab::cs_mark, sl.cs);
             st_wait(sl, sl.bs, sl, &Slab::cs_mark);
             // ONE launch over the first and the last `depth` interior planes (split plane range)
-            sl.cur = sl.bs;
-            split_ = depth;
-            gap_ = nzl_ - 2 * depth;
-            launch(sl, kb, kb + 2 * depth);
+            launch(Launch{sl, sl.bs, kb, kb + 2 * depth, depth, nzl_ - 2 * depth});
             emit(sl, sl.bs, kb, kb + depth, ke - depth, ke);
-            split_ = INT_MAX;
-            gap_ = 0;
             ev_record(sl, &Slab::boundary_done, sl.bs);
-            sl.cur = sl.cs;
-            launch(sl, kb + depth, ke - depth);
-            emit(sl, sl.cs, kb + depth, ke - depth);
+            run(sl, sl.cs, kb + depth, ke - depth);
         }
         SF_HIP(hipGetLastError());
     }
 
-    // Kernel launch on sl.cur.
-    template <class F, class... Args>
-    void launch_k(Slab& sl, F kernel, dim3 nblocks, unsigned nthreads, Args... args) {
-        hipLaunchKernelGGL(kernel, nblocks, dim3(nthreads), 0, sl.cur, args...);
+    // Launch of an operator kernel kernel(geom, args, kb, ke, rest...) for L.
+    template <class F, class Args, class... Rest>
+    void launch_k(const Launch& L, F kernel, dim3 nblocks, dim3 block, const Args& args, Rest... rest) {
+        hipLaunchKernelGGL(kernel, nblocks, block, 0, L.st, L.sl.geom, args, L.kb, L.ke, rest...);
     }
 
     // trace of one slab's share of a halo exchange on stream `st`: its low / high ghost planes are written from the last
@@ -1732,7 +1731,7 @@ private:
     // not take. SF_NT: 0 never / 1 always / 2 auto non-temporal stores. SF_ISHELL: 0 = always read+write the i-shell,
     // 1 = recompute it in intermediate sweeps (default).
     template <int NF, bool NT, int RJ, int RK>
-    void launch_rb(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool first, bool last) {
+    void launch_rb(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool first, bool last) {
         const int nvec = ceil_div(N_, W);
         int tx = 1;
         while (tx < nvec && tx < 64) tx <<= 1;
@@ -1744,35 +1743,40 @@ private:
         m.band = (m.gy >= 16) ? ceil_div(m.gy, 8) : 0;
         m.ishell_mem = (!ishell_skip_ || first) ? 1 : 0;
         m.ishell_write = (!ishell_skip_ || last) ? 1 : 0;
-        m.split = split_;
-        m.gap = gap_;
+        m.split = L.split;
+        m.gap = L.gap;
         const long per_plane = m.band > 0 ? (long)m.nxcd * m.gx * m.band : (long)m.gx * m.gy;
-        const long nblocks = per_plane * ceil_div(ke - kb, RK) * NF;
-        hipLaunchKernelGGL((sfk::jacobi_rb_kernel<T, NF, NT, RJ, RK>), dim3((unsigned)nblocks), dim3(tx, ty), 0,
-                           sl.cur, sl.geom, A, kb, ke, m);
+        const long nblocks = per_plane * ceil_div(L.ke - L.kb, RK) * NF;
+        launch_k(L, sfk::jacobi_rb_kernel<T, NF, NT, RJ, RK>, dim3((unsigned)nblocks), dim3(tx, ty), A, m);
     }
 
     template <int NF, bool NT>
-    void launch_rb_shape(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool first, bool last) {
+    void launch_rb_shape(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool first, bool last) {
         // measured (512^3 / 256^3 fp32): 2x2 blocks win once the sweep streams from HBM (286 vs 309 us),
         // 1x1 wins while x, x0, x' sit in the Infinity Cache (30.8 vs 34.0 us)
-        const bool blocks = NT && !(split_ != INT_MAX && split_ % 2 != 0);  // a plane block must not straddle the split
+        const bool blocks = NT && !(L.is_split() && L.split % 2 != 0);  // a plane block must not straddle the split
         if (blocks)
-            launch_rb<NF, NT, 2, 2>(sl, A, kb, ke, first, last);
+            launch_rb<NF, NT, 2, 2>(L, A, first, last);
         else
-            launch_rb<NF, NT, 1, 1>(sl, A, kb, ke, first, last);
+            launch_rb<NF, NT, 1, 1>(L, A, first, last);
     }
 
     template <int NF>
-    void launch_jacobi(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool first, bool last) {
-        // non-temporal stores pay once x, x0 and x' of all NF fields no longer fit the 256 MiB Infinity Cache
-        const bool nt = nt_mode_ == 1 ||
-                        (nt_mode_ == 2 && (size_t)field_elems_ * sizeof(T) * 3 * NF > ((size_t)384 << 20));
-        if (nt)
-            launch_rb_shape<NF, true>(sl, A, kb, ke, first, last);
+    void launch_jacobi(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool first, bool last) {
+        if (nt_stores(NF))
+            launch_rb_shape<NF, true>(L, A, first, last);
         else
-            launch_rb_shape<NF, false>(sl, A, kb, ke, first, last);
+            launch_rb_shape<NF, false>(L, A, first, last);
     }
+
+    // SF_NT: non-temporal stores never (0), always (1), or (2) once x, x0 and x' of the nf fields of a launch no longer
+    // fit the 256 MiB Infinity Cache
+    bool nt_stores(int nf) const {
+        return nt_mode_ == 1 || (nt_mode_ == 2 && (size_t)field_elems_ * sizeof(T) * 3 * nf > ((size_t)384 << 20));
+    }
+    // bytes of x, x0 and x' of one field of a solve, and whether a working set fits the 256 MiB Infinity Cache
+    double solve_bytes() const { return 3.0 * (double)(N_ + 2) * (N_ + 2) * nplanes_ * sizeof(T); }
+    static bool fits_ic(double bytes) { return bytes <= 0.9 * 256.0 * 1048576.0; }
 
     // Two fused sweeps (temporal blocking). Usable when a row fits one workgroup, N is a multiple of the
     // vector width and the grid is not decomposed (a second ghost plane would be needed).
@@ -1781,20 +1785,24 @@ private:
         return fuse2_ && (P_ == 1 || G_ >= 2) && N_ % W == 0 && N_ / W <= fuse_maxvec_;
     }
 
+    // field f of A as the arguments of a one-field launch
     template <int NF>
-    static sfk::JacobiArgs<T, 1> first_field(const sfk::JacobiArgs<T, NF>& A) {
+    static sfk::JacobiArgs<T, 1> field_args(const sfk::JacobiArgs<T, NF>& A, int f) {
         sfk::JacobiArgs<T, 1> B;
-        B.x[0] = A.x[0];
-        B.x0[0] = A.x0[0];
-        B.xn[0] = A.xn[0];
-        B.b[0] = A.b[0];
+        B.x[0] = A.x[f];
+        B.x0[0] = A.x0[f];
+        B.xn[0] = A.xn[f];
+        B.x0out[0] = A.x0out[f];
+        B.b[0] = A.b[f];
         B.a = A.a;
         B.inv = A.inv;
+        B.dt = A.dt;
         return B;
     }
 
+    // x_zero: the iterate is zero (implicit-zero first pair of project's lin_solve)
     template <int NF, bool NT, int RJ, int RK, bool SRC = false>
-    void launch_fused2(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool first, bool last) {
+    void launch_fused2(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool first, bool last, bool x_zero) {
         const int nvec = N_ / W;
         sfk::TileMap m{};
         // row strips per 256-thread workgroup: packed densely (strip = nvec lanes; rows then start anywhere inside a
@@ -1811,8 +1819,8 @@ private:
         m.band = (m.gy >= 16) ? ceil_div(m.gy, 8) : 0;
         m.ishell_mem = (!ishell_skip_ || first) ? 1 : 0;
         m.ishell_write = (!ishell_skip_ || last) ? 1 : 0;
-        m.split = split_;
-        m.gap = gap_;
+        m.split = L.split;
+        m.gap = L.gap;
         // rows that neither fill whole waves nor divide one: the seam-free overlapped mapping (SF_OVL: 0 never,
         // 1 for such rows (default), 2 for every width)
         // ... and rows wider than two waves, where it also beats one row strip per workgroup (1024^3 fp32: 2026 vs
@@ -1833,8 +1841,7 @@ private:
         // vectors the early lines evict the j / k reuse from the 4 MB L2 (1024^3 fp32 ran 8 % slower, 512^3 fp64 5-15 %).
         {
             const int per_xcd_round = m.band > 0 ? m.band : m.gy;
-            const double ws = 3.0 * NF * (double)(N_ + 2) * (N_ + 2) * nplanes_ * sizeof(T);
-            if (per_xcd_round <= 48 && nvec <= 128 && ws > 0.9 * 256.0 * 1048576.0)
+            if (per_xcd_round <= 48 && nvec <= 128 && !fits_ic(NF * solve_bytes()))
                 m.pf_dz = std::max(1, (32 + per_xcd_round / 2) / std::max(1, per_xcd_round));
             else
                 m.pf_dz = 0;
@@ -1842,44 +1849,42 @@ private:
         m.strip_shift = (m.strip & (m.strip - 1)) == 0 ? __builtin_ctz((unsigned)m.strip) : -1;
         m.nvec_magic = nvec > 1 ? 0xFFFFFFFFu / (unsigned)nvec + 1u : 0u;
         const dim3 nb(m.band > 0 ? (unsigned)m.nxcd : (unsigned)m.gy, m.band > 0 ? (unsigned)m.band : 1u,
-                      (unsigned)(ceil_div(ke - kb, RK) * NF));
+                      (unsigned)(ceil_div(L.ke - L.kb, RK) * NF));
         const bool xlds = m.strip % 64 != 0 && 64 % m.strip != 0;
         if constexpr (!SRC) {
-            if (NF == 1 && x_is_zero_) {  // implicit-zero first pair of project's lin_solve
+            if (NF == 1 && x_zero) {
                 if (ovl)
-                    launch_k(sl, sfk::jacobi2_kernel<T, 1, NT, RJ, RK, false, true, true>, nb, 256u, sl.geom, first_field(A),
-                             kb, ke, m);
+                    launch_k(L, sfk::jacobi2_kernel<T, 1, NT, RJ, RK, false, true, true>, nb, 256u, field_args(A, 0), m);
                 else if (xlds)
-                    launch_k(sl, sfk::jacobi2_kernel<T, 1, NT, RJ, RK, true, true>, nb, 256u, sl.geom, first_field(A), kb, ke,
-                             m);
+                    launch_k(L, sfk::jacobi2_kernel<T, 1, NT, RJ, RK, true, true>, nb, 256u, field_args(A, 0), m);
                 else
-                    launch_k(sl, sfk::jacobi2_kernel<T, 1, NT, RJ, RK, false, true>, nb, 256u, sl.geom, first_field(A), kb,
-                             ke, m);
+                    launch_k(L, sfk::jacobi2_kernel<T, 1, NT, RJ, RK, false, true>, nb, 256u, field_args(A, 0), m);
                 return;
             }
         }
         if (ovl)
-            launch_k(sl, sfk::jacobi2_kernel<T, NF, NT, RJ, RK, false, false, true, SRC>, nb, 256u, sl.geom, A, kb, ke, m);
+            launch_k(L, sfk::jacobi2_kernel<T, NF, NT, RJ, RK, false, false, true, SRC>, nb, 256u, A, m);
         else if (xlds)
-            launch_k(sl, sfk::jacobi2_kernel<T, NF, NT, RJ, RK, true, false, false, SRC>, nb, 256u, sl.geom, A, kb, ke, m);
+            launch_k(L, sfk::jacobi2_kernel<T, NF, NT, RJ, RK, true, false, false, SRC>, nb, 256u, A, m);
         else
-            launch_k(sl, sfk::jacobi2_kernel<T, NF, NT, RJ, RK, false, false, false, SRC>, nb, 256u, sl.geom, A, kb, ke, m);
+            launch_k(L, sfk::jacobi2_kernel<T, NF, NT, RJ, RK, false, false, false, SRC>, nb, 256u, A, m);
     }
 
     // k-marching S-sweep kernel (sfk::jacobi_sk_kernel): the plain passes of a solve (iterate already swept once, so its
-    // i-shell is recomputed in registers) on plane ranges long enough to march. SF_MARCH=0 switches it off.
-    bool can_march_k(int nplanes, bool first) const {
+    // i-shell is recomputed in registers) on plane ranges long enough to march, never in a split boundary launch
+    // (split) or over a zero iterate (x_zero). SF_MARCH=0 switches it off.
+    bool can_march_k(int nplanes, bool first, bool x_zero, bool split) const {
         // small grids do not fill the chip with workgroups of 32-48 rows (128^3: 9.0 vs 4.3 us/sweep)
-        return march_k_ != 0 && !first && ishell_skip_ && split_ == INT_MAX && nplanes >= march_min_planes_ &&
-               !x_is_zero_ && (long)N_ * N_ * nplanes >= march_min_cells_;
+        return march_k_ != 0 && !first && ishell_skip_ && !split && nplanes >= march_min_planes_ && !x_zero &&
+               (long)N_ * N_ * nplanes >= march_min_cells_;
     }
 
     // S fused sweeps with LDS halo exchange (sfk::jacobi_sk_kernel). Same eligibility as the two-sweep marching kernel;
     // three sweeps only on an undecomposed grid (a slab boundary would need three ghost planes).
     // (two-sweep launches — slab interiors with two ghost planes, remainders — only pay on large grids: at 256^3 the
     // register-blocked pair kernel takes 49 us, the marching kernel 67; at 512^3 437 against 365)
-    bool can_sk(int nplanes, bool first, int sweeps = 3) const {
-        return can_march_k(nplanes, first) && (sweeps >= 3 || (long)N_ * N_ * nplanes >= sk2_min_cells_);
+    bool can_sk(int nplanes, bool first, bool x_zero, bool split, int sweeps = 3) const {
+        return can_march_k(nplanes, first, x_zero, split) && (sweeps >= 3 || (long)N_ * N_ * nplanes >= sk2_min_cells_);
     }
 
     int sk_chunks(int ncb, int np, int S) const {
@@ -1909,7 +1914,7 @@ private:
     static constexpr int SK4_TJ = sizeof(T) == 4 ? 2 : 5, SK4_NW = sizeof(T) == 4 ? 16 : 8;
     static constexpr int SK4F_TJ = 4, SK4F_NW = 8;
     template <bool NT, int S, int TJ, int NW, int FIRST = 0, int NF = 1>
-    void launch_sk_cfg(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool last) {
+    void launch_sk_cfg(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool last) {
         constexpr int WL = W / 2;  // 8 bytes per lane
         constexpr int V = NW * TJ - 2 * S, P = 64 - 2 * ((S + WL - 1) / WL);
         const int nvec = N_ / WL;
@@ -1919,66 +1924,57 @@ private:
         m.ncb = (int)ceil_div(items, (long)P);
         m.band = ceil_div(m.ncb, 8);
         m.nvec_magic = nvec > 1 ? 0xFFFFFFFFu / (unsigned)nvec + 1u : 0u;
-        const int np = ke - kb;
+        const int np = L.ke - L.kb;
         int nchunk;
-        if (split_ != INT_MAX) {
-            // boundary launch of a decomposed grid: the first and the last `split_` interior planes as two chunks
+        if (L.is_split()) {
+            // boundary launch of a decomposed grid: the first and the last `split` interior planes as two chunks
             nchunk = 2;
-            m.gap = gap_;
+            m.gap = L.gap;
         } else {
             // One workgroup per CU at a time (LDS, registers): time ~ (workgroups per CU, rounded up) x (steps per
             // chunk: kc + 2S-2, plus start-up).
             nchunk = sk_chunks(m.ncb * NF, np, S);  // (NF fields in one grid: NF times the column blocks)
         }
-        m.kc = split_ != INT_MAX ? split_ : ceil_div(np, nchunk);
+        m.kc = L.is_split() ? L.split : ceil_div(np, nchunk);
         nchunk = ceil_div(np, m.kc);
         dim3 nb(8u, (unsigned)m.band, (unsigned)(nchunk * NF));
         if constexpr (FIRST != 0) {  // a first pass is never the last one (sk_first_ok)
-            launch_k(sl, sfk::jacobi_sk_kernel<T, NF, WL, NT, S, TJ, NW, false, FIRST>, nb, 64u * NW, sl.geom, A, kb, ke, m);
+            launch_k(L, sfk::jacobi_sk_kernel<T, NF, WL, NT, S, TJ, NW, false, FIRST>, nb, 64u * NW, A, m);
         } else if constexpr (NF > 1) {  // (fields in one grid: plain passes only, launch_sk)
-            launch_k(sl, sfk::jacobi_sk_kernel<T, NF, WL, NT, S, TJ, NW, false>, nb, 64u * NW, sl.geom, A, kb, ke, m);
+            launch_k(L, sfk::jacobi_sk_kernel<T, NF, WL, NT, S, TJ, NW, false>, nb, 64u * NW, A, m);
         } else {
             if (last)
-                launch_k(sl, sfk::jacobi_sk_kernel<T, 1, WL, NT, S, TJ, NW, true>, nb, 64u * NW, sl.geom, A, kb, ke, m);
+                launch_k(L, sfk::jacobi_sk_kernel<T, 1, WL, NT, S, TJ, NW, true>, nb, 64u * NW, A, m);
             else
-                launch_k(sl, sfk::jacobi_sk_kernel<T, 1, WL, NT, S, TJ, NW, false>, nb, 64u * NW, sl.geom, A, kb, ke, m);
+                launch_k(L, sfk::jacobi_sk_kernel<T, 1, WL, NT, S, TJ, NW, false>, nb, 64u * NW, A, m);
         }
     }
 
     // First pass of a solve through the marching kernel (four sweeps; sfk::SkFirst): mode 1 caller data, 2 folded
-    // add_source, 3 zero iterate. One launch per field.
+    // add_source, 3 zero iterate. One launch per field, or one for all NF with mode 2 in a batched solve (batch).
     template <int NF>
-    void launch_sk_first(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, int mode) {
-        const bool nt = nt_mode_ == 1 ||
-                        (nt_mode_ == 2 && (size_t)field_elems_ * sizeof(T) * 3 * NF > ((size_t)384 << 20));
+    void launch_sk_first(const Launch& L, const sfk::JacobiArgs<T, NF>& A, int mode, bool batch) {
+        const bool nt = nt_stores(NF);
         // (tiles: SK4F_* for the passes that read the caller's i-shell, SK4_* for the zero-iterate pass, see above)
         constexpr int TJ0 = SK4F_TJ, NWF = SK4F_NW, TJ3 = SK4_TJ, NW4 = SK4_NW;
         if constexpr (NF > 1) {
-            if (mode == 2 && fields_in_one_grid()) {
-                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 2, NF>(sl, A, kb, ke, false);
-                else launch_sk_cfg<false, 4, TJ0, NWF, 2, NF>(sl, A, kb, ke, false);
+            if (mode == 2 && batch) {
+                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 2, NF>(L, A, false);
+                else launch_sk_cfg<false, 4, TJ0, NWF, 2, NF>(L, A, false);
                 return;
             }
         }
         for (int f = 0; f < NF; ++f) {
-            sfk::JacobiArgs<T, 1> B;
-            B.x[0] = A.x[f];
-            B.x0[0] = A.x0[f];
-            B.xn[0] = A.xn[f];
-            B.x0out[0] = A.x0out[f];
-            B.b[0] = A.b[f];
-            B.a = A.a;
-            B.inv = A.inv;
-            B.dt = A.dt;
+            const sfk::JacobiArgs<T, 1> B = field_args(A, f);
             if (mode == 1) {
-                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 1>(sl, B, kb, ke, false);
-                else launch_sk_cfg<false, 4, TJ0, NWF, 1>(sl, B, kb, ke, false);
+                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 1>(L, B, false);
+                else launch_sk_cfg<false, 4, TJ0, NWF, 1>(L, B, false);
             } else if (mode == 2) {
-                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 2>(sl, B, kb, ke, false);
-                else launch_sk_cfg<false, 4, TJ0, NWF, 2>(sl, B, kb, ke, false);
+                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 2>(L, B, false);
+                else launch_sk_cfg<false, 4, TJ0, NWF, 2>(L, B, false);
             } else {
-                if (nt) launch_sk_cfg<true, 4, TJ3, NW4, 3>(sl, B, kb, ke, false);
-                else launch_sk_cfg<false, 4, TJ3, NW4, 3>(sl, B, kb, ke, false);
+                if (nt) launch_sk_cfg<true, 4, TJ3, NW4, 3>(L, B, false);
+                else launch_sk_cfg<false, 4, TJ3, NW4, 3>(L, B, false);
             }
         }
     }
@@ -1994,14 +1990,8 @@ private:
     // The NF fields of a batched solve (u, v, w of a diffusion) as ONE marching grid on an undecomposed slab: NF times
     // the column blocks let the launch fill the chip with NF times fewer, longer chunks — a chunk pays 2(S-1) warm-up
     // planes whatever its length (256^3: 3 chunks of 86 planes instead of 10 of 26 per field: 92 instead of 96 steps per
-    // workgroup; plain pass 51.3 against 53.3 us per field, folded-source first pass 74 against 86).
-    struct BatchScope {  // sets batch_now_ for the launches of one solve
-        bool& flag;
-        bool saved;
-        BatchScope(bool& f, bool v) : flag(f), saved(f) { flag = v; }
-        ~BatchScope() { flag = saved; }
-    };
-    bool fields_in_one_grid() const { return P_ == 1 && split_ == INT_MAX && split_fields_ != 2 && batch_now_; }
+    // workgroup; plain pass 51.3 against 53.3 us per field, folded-source first pass 74 against 86). Only on one
+    // undecomposed slab (P_ == 1), so never in a split boundary launch.
     // ... which the solve only asks for when every pass is a four-sweep marching launch (K a multiple of four on a
     // grid the kernel takes): a pair-kernel pass over three fields at once would leave the Infinity Cache. And only
     // where it was measured to pay (same-box A/B of the full fp32 K = 20 step, ms, fields apart / in one grid; `one` =
@@ -2015,86 +2005,71 @@ private:
         if (!(P_ == 1 && split_fields_ != 2 && K % 4 == 0 && K >= 4 && sk_first_ && march_k_ != 0 && sk_s_ >= 4 &&
               can_fuse2() && ishell_skip_ && nzl_ >= march_min_planes_ && (long)N_ * N_ * nzl_ >= march_min_cells_))
             return false;
-        const double one = 3.0 * (double)(N_ + 2) * (N_ + 2) * nplanes_ * sizeof(T);  // x, x0, x' of one field
-        const double mb = one / 1048576.0;
+        const double mb = solve_bytes() / 1048576.0;
         if (split_fields_ == 1 && !((mb >= 75.0 && mb <= 125.0) || (mb >= 170.0 && mb <= 2048.0))) return false;
         return continued || K >= 8;
     }
+    // Solve the NF fields of a solve one after the other? x, x0 and x' of ONE field fit the 256 MiB Infinity Cache where
+    // those of NF fields together do not: every pair after the first then stays out of HBM (256^3 fp32: 3 x 50.8 us
+    // against 175.9 us per pair of three fields). Independent fields: same results.
+    bool solve_apart(int K, bool continued) const {
+        return split_fields_ == 2 || (split_fields_ == 1 && fits_ic(solve_bytes()) && !batch_march(K, continued));
+    }
 
+    // batch: a batched solve (batch_march) whose passes go as one grid for all NF fields
     template <int NF, int S>
-    void launch_sk(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool last) {
+    void launch_sk(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool last, bool batch) {
         SF_REQUIRE(ishell_skip_ && march_k_ != 0, "internal: marching launch while SF_ISHELL=0 / SF_MARCH=0");
-        const bool nt = nt_mode_ == 1 ||
-                        (nt_mode_ == 2 && (size_t)field_elems_ * sizeof(T) * 3 * NF > ((size_t)384 << 20));
+        const bool nt = nt_stores(NF);
         if constexpr (NF > 1 && S == 4) {
-            if (!last && fields_in_one_grid()) {
-                if (nt) launch_sk_cfg<true, S, SK4_TJ, SK4_NW, 0, NF>(sl, A, kb, ke, false);
-                else launch_sk_cfg<false, S, SK4_TJ, SK4_NW, 0, NF>(sl, A, kb, ke, false);
+            if (!last && batch) {
+                if (nt) launch_sk_cfg<true, S, SK4_TJ, SK4_NW, 0, NF>(L, A, false);
+                else launch_sk_cfg<false, S, SK4_TJ, SK4_NW, 0, NF>(L, A, false);
                 return;
             }
         }
         for (int f = 0; f < NF; ++f) {  // one launch per field (fields are independent)
-            sfk::JacobiArgs<T, 1> B;
-            B.x[0] = A.x[f];
-            B.x0[0] = A.x0[f];
-            B.xn[0] = A.xn[f];
-            B.b[0] = A.b[f];
-            B.a = A.a;
-            B.inv = A.inv;
+            const sfk::JacobiArgs<T, 1> B = field_args(A, f);
             // Tile: SK4_* at S = 4 (above); six rows x eight waves at S <= 3. Four levels hold 17 planes of rows per
             // lane (x 3, x0 5, three intermediate levels x 3). (A spill in the wall workgroups alone doubles a launch
             // at 256^3, where every workgroup runs at once and the slowest one is the launch.)
             constexpr int TJ0 = S == 4 ? SK4_TJ : 6, NW0 = S == 4 ? SK4_NW : 8;
             if (nt)
-                launch_sk_cfg<true, S, TJ0, NW0>(sl, B, kb, ke, last);
+                launch_sk_cfg<true, S, TJ0, NW0>(L, B, last);
             else
-                launch_sk_cfg<false, S, TJ0, NW0>(sl, B, kb, ke, last);
+                launch_sk_cfg<false, S, TJ0, NW0>(L, B, last);
         }
-    }
-
-    template <int NF>
-    void launch_jacobi_s(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool last, int sweeps) {
-        if (sweeps == 4)
-            launch_sk<NF, 4>(sl, A, kb, ke, last);
-        else
-            launch_sk<NF, 3>(sl, A, kb, ke, last);
     }
 
     template <int NF, bool SRC = false>
-    void launch_jacobi2(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool first, bool last) {
-        const bool nt = nt_mode_ == 1 ||
-                        (nt_mode_ == 2 && (size_t)field_elems_ * sizeof(T) * 3 * NF > ((size_t)384 << 20));
+    void launch_jacobi2(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool first, bool last, bool x_zero) {
         if constexpr (!SRC) {
-            if (can_sk(ke - kb, first, 2)) {
-                launch_sk<NF, 2>(sl, A, kb, ke, last);
+            if (can_sk(L.ke - L.kb, first, x_zero, L.is_split(), 2)) {
+                launch_sk<NF, 2>(L, A, last, false);
                 return;
             }
         }
-        if (nt)
-            launch_fused2_shape<NF, true, SRC>(sl, A, kb, ke, first, last);
-        else
-            launch_fused2_shape<NF, false, SRC>(sl, A, kb, ke, first, last);
-    }
-
-    template <int NF, bool NT, bool SRC = false>
-    void launch_fused2_shape(Slab& sl, const sfk::JacobiArgs<T, NF>& A, int kb, int ke, bool first, bool last) {
         // 2x2 output vectors per thread: measured best of 1x1, 2x1, 1x2, 2x2, 4x2 (4x2 spills)
-        launch_fused2<NF, NT, 2, 2, SRC>(sl, A, kb, ke, first, last);
+        if (nt_stores(NF))
+            launch_fused2<NF, true, 2, 2, SRC>(L, A, first, last, x_zero);
+        else
+            launch_fused2<NF, false, 2, 2, SRC>(L, A, first, last, x_zero);
     }
 
     // Sweeps fused into the launch that starts at iteration `it` of a K-sweep solve: 3 where the S-sweep kernel is in
     // use (never the first pass of a solve, whose iterate is caller data / zero / a source; a remainder of four goes
-    // as 2 + 2), else 2 where pairs can be fused, else 1.
-    int sweeps_in_launch(int it, int K, bool continued, int extra = 0) const {
+    // as 2 + 2), else 2 where pairs can be fused, else 1. x_zero: the pass's iterate is zero; extra: the growth of its
+    // boundary launch (for_planes).
+    int sweeps_in_launch(int it, int K, bool continued, bool x_zero, int extra = 0) const {
         const bool pair = can_fuse2() && it + 2 <= K;
         const int left = K - it;
         if (it == 0 && !continued && sk_first_ok(K)) return 4;
         // (the marching kernel leaves the i-shell implicit between passes: with SF_ISHELL=0 — every pass reads it from
         // memory — it must not run at all, on one slab or many. Round 2 checked that for P_ == 1 only, and a
         // decomposed solve mixed marching passes with pair passes that read a stale i-shell.)
-        bool marching = pair && (it > 0 || continued) && march_k_ != 0 && ishell_skip_ && !x_is_zero_ && sk_s_ >= 3 &&
+        bool marching = pair && (it > 0 || continued) && march_k_ != 0 && ishell_skip_ && !x_zero && sk_s_ >= 3 &&
                         left >= 3;
-        if (marching && P_ == 1) marching = can_sk(nzl_, false);
+        if (marching && P_ == 1) marching = can_sk(nzl_, false, x_zero, false);
         // S sweeps per pass need S ghost planes on a decomposed grid, the two-stream schedule, and an interior launch
         // [G+S+extra, ...) the marching kernel takes (the boundary launch always goes through it: there is no other
         // kernel of that depth)
@@ -2113,26 +2088,23 @@ private:
     // must not straddle the split of a boundary launch, so with three ghost planes it takes four planes per side
     int pair_depth() const { return G_ >= 3 ? 4 : 2; }
 
-    // K Jacobi sweeps on NF fields at once; scratch buffers are swapped into the slots.
+    // K Jacobi sweeps on NF fields at once; scratch buffers are swapped into the slots. dead_ishell: nothing reads the
+    // result's i-shell, so the last pass leaves it unwritten. x_zero: the iterate is zero (project's pressure).
+    // continued: the first pass of this solve has run already (op_diffuse_src).
     template <int NF>
-    void op_lin_solve(const int (&x)[NF], const int (&x0)[NF], const int (&b)[NF], T a, T c, int K,
+    void op_lin_solve(const int (&x)[NF], const int (&x0)[NF], const int (&b)[NF], T a, T c, int K, bool dead_ishell,
                       bool x_zero = false, bool continued = false) {
         static_assert(NF <= NSCRATCH, "not enough scratch buffers");
         if constexpr (NF > 1) {
-            // x, x0 and x' of ONE field fit the 256 MiB Infinity Cache where those of NF fields together do not:
-            // solving the fields one after the other then keeps every pair after the first out of HBM (256^3 fp32:
-            // 3 x 50.8 us against 175.9 us per pair of three fields). Independent fields: same results.
-            const double one = 3.0 * (double)(N_ + 2) * (N_ + 2) * nplanes_ * sizeof(T);
-            const bool fits = one <= 0.9 * 256.0 * 1048576.0;
-            if (split_fields_ == 2 || (split_fields_ == 1 && fits && !batch_march(K, continued))) {
+            if (solve_apart(K, continued)) {
                 for (int f = 0; f < NF; ++f) {
                     const int xf[1] = {x[f]}, x0f[1] = {x0[f]}, bf[1] = {b[f]};
-                    op_lin_solve<1>(xf, x0f, bf, a, c, K, x_zero, continued);
+                    op_lin_solve<1>(xf, x0f, bf, a, c, K, dead_ishell, x_zero, continued);
                 }
                 return;
             }
         }
-        BatchScope batch_scope(batch_now_, NF > 1 && batch_march(K, continued));
+        const bool batch = NF > 1 && batch_march(K, continued);
         const T inv = T(1) / c;
         for (Slab& sl : slabs_)
             for (int f = 0; f < NF; ++f) {
@@ -2157,8 +2129,8 @@ private:
             const bool pair = can_fuse2() && it + 2 <= K;
             // three sweeps per pass where the S-sweep kernel is in use (never the first pass of a solve, whose iterate
             // is caller data; a remainder of four goes as 2 + 2)
-            x_is_zero_ = x_zero && it == 0 && pair;  // the first fused pair then loads no x at all
-            const int step = sweeps_in_launch(it, K, continued, 0);
+            const bool zero_pair = x_zero && it == 0 && pair;  // the first fused pair then loads no x at all
+            const int step = sweeps_in_launch(it, K, continued, zero_pair);
             const int depth0 = std::max(step == 2 ? pair_depth() : step, G_);  // boundary depth without growth
             int extra = 0;
             {
@@ -2167,58 +2139,52 @@ private:
                 const int d = dprev + (inject_trap_bug_ ? step : std::max(step, sprev));  // where its interior launch would start
                 bool cont = pair && P_ > 1 && G_ >= 2 && trap_m_ > 1 && tj > 0 && tj < trap_m_ && d >= depth0 &&
                             nzl_ > 2 * d + 2;
-                if (cont && step >= 3 && sweeps_in_launch(it, K, continued, d - depth0) != step) cont = false;
+                if (cont && step >= 3 && sweeps_in_launch(it, K, continued, zero_pair, d - depth0) != step) cont = false;
                 if (cont && step == 2 && (d & 1)) cont = false;  // plane pairs: even boundary depth
                 if (!cont) tj = 0;
                 extra = cont ? d - depth0 : 0;
                 dprev = depth0 + extra;
                 sprev = step;
             }
-            const bool triple = step >= 3;  // three or four sweeps: the marching kernel
-            // the pass that writes the i-shell: the last one, unless nothing will read that shell (dead_ishell_)
-            const bool last = it + step == K && !dead_ishell_;
-            trap_extra_ = extra;
+            // the pass that writes the i-shell: the last one, unless nothing will read that shell (dead_ishell)
+            const bool last = it + step == K && !dead_ishell;
+            const bool first = it == 0 && !continued;
             ++tj;
-            if (trace_) {
-                acc_name_ = step == 4 ? "jacobi4" : (step == 3 ? "jacobi3" : (step == 2 ? "jacobi2" : "jacobi1"));
-                acc_fn_ = [&, step](Slab& sl, int a, int b, std::vector<Acc>& acc) {
-                    int lo, hi;
-                    wr_range(sl, a, b, lo, hi);
-                    for (int f = 0; f < NF; ++f) {
-                        if (!x_is_zero_) acc.push_back({sl.field[x[f]], false, a - step, b + step});
-                        acc.push_back({sl.field[x0[f]], false, a - (step - 1), b + (step - 1)});
-                        acc.push_back({sl.scratch[f], true, lo, hi});
-                    }
-                };
-            }
-            for_planes([&](Slab& sl, int kb, int ke) {
-                sfk::JacobiArgs<T, NF> A;
+            const char* name = step == 4 ? "jacobi4" : (step == 3 ? "jacobi3" : (step == 2 ? "jacobi2" : "jacobi1"));
+            auto accesses = [&](Slab& sl, int a, int b, int lo, int hi, std::vector<Acc>& acc) {
                 for (int f = 0; f < NF; ++f) {
-                    A.x[f] = sl.field[x[f]];
-                    A.x0[f] = sl.field[x0[f]];
-                    A.xn[f] = sl.scratch[f];
+                    if (!zero_pair) acc.push_back({sl.field[x[f]], false, a - step, b + step});
+                    acc.push_back({sl.field[x0[f]], false, a - (step - 1), b + (step - 1)});
+                    acc.push_back({sl.scratch[f], true, lo, hi});
+                }
+            };
+            for_planes(name, accesses, [&](const Launch& L) {
+                sfk::JacobiArgs<T, NF> A{};
+                for (int f = 0; f < NF; ++f) {
+                    A.x[f] = L.sl.field[x[f]];
+                    A.x0[f] = L.sl.field[x0[f]];
+                    A.xn[f] = L.sl.scratch[f];
                     A.b[f] = b[f];
                 }
                 A.a = a;
                 A.inv = inv;
-                if (it == 0 && !continued && step == 4)
-                    launch_sk_first<NF>(sl, A, kb, ke, x_zero ? 3 : 1);
-                else if (triple)
-                    launch_jacobi_s<NF>(sl, A, kb, ke, last, step);
+                if (first && step == 4)
+                    launch_sk_first<NF>(L, A, x_zero ? 3 : 1, batch);
+                else if (step == 4)  // three or four sweeps (the rest of the solve): the marching kernel
+                    launch_sk<NF, 4>(L, A, last, batch);
+                else if (step == 3)
+                    launch_sk<NF, 3>(L, A, last, batch);
                 else if (pair)
-                    launch_jacobi2<NF>(sl, A, kb, ke, it == 0 && !continued, last);
+                    launch_jacobi2<NF>(L, A, first, last, zero_pair);
                 else
-                    launch_jacobi<NF>(sl, A, kb, ke, it == 0 && !continued, last);
-            }, step == 2 ? pair_depth() : step, true);
-            acc_fn_ = nullptr;
+                    launch_jacobi<NF>(L, A, first, last);
+            }, step == 2 ? pair_depth() : step, extra);
             // the new iterate becomes the field; the old buffer becomes scratch
             for (Slab& sl : slabs_)
                 for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
             exchange<NF>(x);
             it += step;
         }
-        trap_extra_ = 0;
-        x_is_zero_ = false;
     }
 
     // Right-hand side x + dt*src of a folded add_source on the G-1 ghost planes next to the slab on either side (an
@@ -2267,24 +2233,23 @@ private:
     // fills from the (current) ghost planes of x and src.
     template <int NF>
     void op_diffuse_src(const int (&x)[NF], const int (&x0)[NF], const int (&b)[NF], const int (&src)[NF], T a, T c,
-                        int K) {
+                        int K, bool dead_ishell) {
         if (!(fuse_src_ && can_fuse2() && K >= 2)) {
             op_add_source_bound<NF>(x, x0, src);
             for (int f = 0; f < NF; ++f) swap_slots(x0[f], x[f]);
-            op_lin_solve<NF>(x, x0, b, a, c, K);
+            op_lin_solve<NF>(x, x0, b, a, c, K, dead_ishell);
             return;
         }
         if constexpr (NF > 1) {
-            const double one = 3.0 * (double)(N_ + 2) * (N_ + 2) * nplanes_ * sizeof(T);
-            if (split_fields_ == 2 || (split_fields_ == 1 && one <= 0.9 * 256.0 * 1048576.0 && !batch_march(K, false))) {
+            if (solve_apart(K, false)) {
                 for (int f = 0; f < NF; ++f) {
                     const int xf[1] = {x[f]}, x0f[1] = {x0[f]}, bf[1] = {b[f]}, sf[1] = {src[f]};
-                    op_diffuse_src<1>(xf, x0f, bf, sf, a, c, K);
+                    op_diffuse_src<1>(xf, x0f, bf, sf, a, c, K, dead_ishell);
                 }
                 return;
             }
         }
-        BatchScope batch_scope(batch_now_, NF > 1 && batch_march(K, false));
+        const bool batch = NF > 1 && batch_march(K, false);
         const T inv = T(1) / c;
         for (Slab& sl : slabs_)
             for (int f = 0; f < NF; ++f) {
@@ -2292,69 +2257,46 @@ private:
                 ensure(sl, x0[f]);
                 ensure(sl, src[f]);
             }
-        const int sreach = sk_first_ok(K) ? 4 : 2;  // sweeps of the first pass = its reach in planes
-        if (trace_) {
-            acc_name_ = "jacobi_src";
-            acc_fn_ = [&, sreach](Slab& sl, int a, int b, std::vector<Acc>& acc) {
-                int lo, hi;
-                wr_range(sl, a, b, lo, hi);
-                for (int f = 0; f < NF; ++f) {
-                    acc.push_back({sl.field[src[f]], false, a - sreach, b + sreach});
-                    acc.push_back({sl.field[x[f]], false, a - (sreach - 1), b + (sreach - 1)});
-                    acc.push_back({sl.scratch[f], true, lo, hi});
-                    acc.push_back({sl.field[x0[f]], true, a, b});
-                }
-            };
-        }
-        if (sk_first_ok(K)) {
-            // the same pass as four sweeps of the marching kernel (undecomposed grid): rhs formed per plane as it
-            // arrives, stored for the later launches
-            for_planes([&](Slab& sl, int kb, int ke) {
-                sfk::JacobiArgs<T, NF> A;
-                for (int f = 0; f < NF; ++f) {
-                    A.x[f] = sl.field[src[f]];
-                    A.x0[f] = sl.field[x[f]];
-                    A.xn[f] = sl.scratch[f];
-                    A.x0out[f] = sl.field[x0[f]];
-                    A.b[f] = b[f];
-                }
-                A.a = a;
-                A.inv = inv;
-                A.dt = dt_;
-                launch_sk_first<NF>(sl, A, kb, ke, 2);
-            }, 4, true);
-            acc_fn_ = nullptr;
-            rhs_on_ghost_planes<NF>(x, x0, src, 4);
-            for (Slab& sl : slabs_)
-                for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
-            exchange<NF>(x);
-            op_lin_solve<NF>(x, x0, b, a, c, K - 4, false, true);
-            return;
-        }
-        for_planes([&](Slab& sl, int kb, int ke) {
-            sfk::JacobiArgs<T, NF> A;
+        // four: the same pass as four sweeps of the marching kernel (rhs formed per plane as it arrives, stored for the
+        // later launches), else a fused pair
+        const bool four = sk_first_ok(K);
+        const int sreach = four ? 4 : 2;  // sweeps of the first pass = its reach in planes
+        const int depth = four ? 4 : pair_depth();
+        auto accesses = [&](Slab& sl, int a, int b, int lo, int hi, std::vector<Acc>& acc) {
             for (int f = 0; f < NF; ++f) {
-                A.x[f] = sl.field[src[f]];    // iterate = the source (Stam's initial guess)
-                A.x0[f] = sl.field[x[f]];     // the field before add_source
-                A.xn[f] = sl.scratch[f];
-                A.x0out[f] = sl.field[x0[f]];  // right-hand side x + dt*src for the later pairs
+                acc.push_back({sl.field[src[f]], false, a - sreach, b + sreach});
+                acc.push_back({sl.field[x[f]], false, a - (sreach - 1), b + (sreach - 1)});
+                acc.push_back({sl.scratch[f], true, lo, hi});
+                acc.push_back({sl.field[x0[f]], true, a, b});
+            }
+        };
+        for_planes("jacobi_src", accesses, [&](const Launch& L) {
+            sfk::JacobiArgs<T, NF> A{};
+            for (int f = 0; f < NF; ++f) {
+                A.x[f] = L.sl.field[src[f]];    // iterate = the source (Stam's initial guess)
+                A.x0[f] = L.sl.field[x[f]];     // the field before add_source
+                A.xn[f] = L.sl.scratch[f];
+                A.x0out[f] = L.sl.field[x0[f]];  // right-hand side x + dt*src for the later passes
                 A.b[f] = b[f];
             }
             A.a = a;
             A.inv = inv;
             A.dt = dt_;
-            launch_jacobi2<NF, true>(sl, A, kb, ke, true, K == 2 && !dead_ishell_);
-        }, pair_depth(), true);
-        acc_fn_ = nullptr;
-        rhs_on_ghost_planes<NF>(x, x0, src, pair_depth());
+            if (four)
+                launch_sk_first<NF>(L, A, 2, batch);
+            else
+                launch_jacobi2<NF, true>(L, A, true, K == 2 && !dead_ishell, false);
+        }, depth);
+        rhs_on_ghost_planes<NF>(x, x0, src, depth);
         for (Slab& sl : slabs_)
             for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
         exchange<NF>(x);
-        op_lin_solve<NF>(x, x0, b, a, c, K - 2, false, true);
+        op_lin_solve<NF>(x, x0, b, a, c, K - sreach, dead_ishell, false, true);
     }
 
+    // dead_ishell: nothing reads the i-shell of the result, which is left unwritten
     template <int NF>
-    void op_advect(const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u, int v, int w) {
+    void op_advect(const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u, int v, int w, bool dead_ishell) {
         const T dt0 = dt_ * (T)N_;
         for (Slab& sl : slabs_) {
             for (int f = 0; f < NF; ++f) {
@@ -2365,21 +2307,17 @@ private:
             ensure(sl, v);
             ensure(sl, w);
         }
-        if (trace_) {
-            acc_name_ = "advect";
-            acc_fn_ = [&](Slab& sl, int a, int b_, std::vector<Acc>& acc) {
-                int lo, hi;
-                wr_range(sl, a, b_, lo, hi);
-                for (int f = 0; f < NF; ++f) {
-                    acc.push_back({sl.field[d0[f]], false, a - 1, b_ + 1});
-                    acc.push_back({sl.field[d[f]], true, lo, hi});
-                }
-                acc.push_back({sl.field[u], false, a, b_});
-                acc.push_back({sl.field[v], false, a, b_});
-                acc.push_back({sl.field[w], false, a, b_});
-            };
-        }
-        for_planes([&](Slab& sl, int kb, int ke) {
+        auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            for (int f = 0; f < NF; ++f) {
+                acc.push_back({sl.field[d0[f]], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[d[f]], true, lo, hi});
+            }
+            acc.push_back({sl.field[u], false, a, b_});
+            acc.push_back({sl.field[v], false, a, b_});
+            acc.push_back({sl.field[w], false, a, b_});
+        };
+        for_planes("advect", accesses, [&](const Launch& L) {
+            Slab& sl = L.sl;
             sfk::AdvectArgs<T, NF> A;
             for (int f = 0; f < NF; ++f) {
                 A.d[f] = sl.field[d[f]];
@@ -2391,10 +2329,10 @@ private:
             A.w = sl.field[w];
             A.dt0 = dt0;
             A.flag = sl.d_flag;
-            A.skip_ishell = dead_ishell_ ? 1 : 0;
+            A.skip_ishell = dead_ishell ? 1 : 0;
             dim3 block;
             unsigned nblocks;
-            const sfk::TileMap m = flat_map(ke - kb, block, nblocks);
+            const sfk::TileMap m = flat_map(L, block, nblocks);
             if (advect_row_ >= 2 || (advect_row_ == 1 && NF >= 2)) {
                 // one cell per lane for the three velocity components. fp32: the i0+1 samples from the neighbour lane
                 // (256^3 245 -> 171 us, 512^3 1628 -> 1217; with own (i0, i0+1) pair loads 215 / 1537). fp64: own pair
@@ -2402,17 +2340,14 @@ private:
                 // (fp32 79 vs 88 / 113, fp64 130 vs 150 / 129). SF_ADVECT_ROW = 0 never, 2 / 3 always the sharing /
                 // the pair form.
                 const int wpr = ceil_div(N_, 64);
-                const long waves = (long)wpr * N_ * (ke - kb);
+                const long waves = (long)wpr * N_ * (L.ke - L.kb);
                 if (advect_row_ == 3 || (advect_row_ == 1 && sizeof(T) == 8))
-                    hipLaunchKernelGGL((sfk::advect_row_kernel<T, NF, true>), dim3((unsigned)ceil_div(waves, 4L)),
-                                       dim3(256), 0, sl.cur, sl.geom, A, kb, ke, wpr);
+                    launch_k(L, sfk::advect_row_kernel<T, NF, true>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
                 else
-                    hipLaunchKernelGGL((sfk::advect_row_kernel<T, NF>), dim3((unsigned)ceil_div(waves, 4L)), dim3(256), 0,
-                                       sl.cur, sl.geom, A, kb, ke, wpr);
+                    launch_k(L, sfk::advect_row_kernel<T, NF>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
             } else
-                hipLaunchKernelGGL((sfk::advect_kernel<T, NF>), dim3(nblocks), block, 0, sl.cur, sl.geom, A, kb, ke, m);
-        }, 1, true, /*interior_reads_ghosts=*/true);  // a long back-trace may reach a ghost plane from any plane
-        acc_fn_ = nullptr;
+                launch_k(L, sfk::advect_kernel<T, NF>, dim3(nblocks), block, A, m);
+        }, 1, 0, /*interior_reads_ghosts=*/true);  // a long back-trace may reach a ghost plane from any plane
         exchange<NF>(d);
     }
 
@@ -2451,24 +2386,18 @@ private:
                 tr_whole("zero_p", sl, {}, {sl.field[p]});
             }
         }
-        if (trace_) {
-            acc_name_ = "project_div";
-            acc_fn_ = [&](Slab& sl, int a, int b_, std::vector<Acc>& acc) {
-                int lo, hi;
-                wr_range(sl, a, b_, lo, hi);
-                acc.push_back({sl.field[u], false, a, b_});
-                acc.push_back({sl.field[v], false, a, b_});
-                acc.push_back({sl.field[w], false, a - 1, b_ + 1});
-                acc.push_back({sl.field[div], true, lo, hi});
-            };
-        }
-        for_planes([&](Slab& sl, int kb, int ke) {
+        auto div_acc = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            acc.push_back({sl.field[u], false, a, b_});
+            acc.push_back({sl.field[v], false, a, b_});
+            acc.push_back({sl.field[w], false, a - 1, b_ + 1});
+            acc.push_back({sl.field[div], true, lo, hi});
+        };
+        for_planes("project_div", div_acc, [&](const Launch& L) {
             dim3 block;
             unsigned nblocks;
-            const sfk::TileMap m = flat_map(ke - kb, block, nblocks);
-            hipLaunchKernelGGL((sfk::project_div_kernel<T>), dim3(nblocks), block, 0, sl.cur, sl.geom, args(sl), kb, ke, m);
+            const sfk::TileMap m = flat_map(L, block, nblocks);
+            launch_k(L, sfk::project_div_kernel<T>, dim3(nblocks), block, args(L.sl), m);
         });
-        acc_fn_ = nullptr;
         // div's ghost planes are exchanged although a single sweep reads div at cell centres only: the fused
         // sweep pair evaluates its first sweep on the first ghost plane and needs x0 = div there, and div is left
         // in the v0 slot, where the caller may use it as the next step's source / initial guess (all G planes).
@@ -2476,34 +2405,26 @@ private:
         const int dv[1] = {div};
         exchange<1>(dv);
         const int ps[1] = {p}, b0[1] = {0};
-        dead_ishell_ = dead_p;
-        op_lin_solve<1>(ps, dv, b0, T(1), T(6), K_, implicit_zero);
-        dead_ishell_ = false;
-        if (trace_) {
-            acc_name_ = "project_sub";
-            acc_fn_ = [&](Slab& sl, int a, int b_, std::vector<Acc>& acc) {
-                int lo, hi;
-                wr_range(sl, a, b_, lo, hi);
-                acc.push_back({sl.field[p], false, a - 1, b_ + 1});
-                for (int q : {u, v, w}) {
-                    acc.push_back({sl.field[q], false, a, b_});
-                    acc.push_back({sl.field[q], true, lo, hi});
-                }
-            };
-        }
-        for_planes([&](Slab& sl, int kb, int ke) {
+        op_lin_solve<1>(ps, dv, b0, T(1), T(6), K_, dead_p, implicit_zero);
+        auto sub_acc = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            acc.push_back({sl.field[p], false, a - 1, b_ + 1});
+            for (int q : {u, v, w}) {
+                acc.push_back({sl.field[q], false, a, b_});
+                acc.push_back({sl.field[q], true, lo, hi});
+            }
+        };
+        for_planes("project_sub", sub_acc, [&](const Launch& L) {
             dim3 block;
             unsigned nblocks;
-            const sfk::TileMap m = flat_map(ke - kb, block, nblocks);
-            hipLaunchKernelGGL((sfk::project_sub_kernel<T>), dim3(nblocks), block, 0, sl.cur, sl.geom, args(sl), kb, ke, m);
+            const sfk::TileMap m = flat_map(L, block, nblocks);
+            launch_k(L, sfk::project_sub_kernel<T>, dim3(nblocks), block, args(L.sl), m);
         });
-        acc_fn_ = nullptr;
         const int uvw[3] = {u, v, w};
         exchange<3>(uvw);
     }
 
     // ---- external forces (SPEC §8) ------------------------------------------------------------------------------
-    sfk::ForceArgs<T> force_args() const {
+    sfk::ForceArgs<T> force_args(const Launch& L) const {
         const T Nf = (T)N_;
         const T h = T(1) / Nf;
         sfk::ForceArgs<T> A{};
@@ -2513,8 +2434,8 @@ private:
         A.amb = amb_;
         A.tiny = (T)1e-20;
         A.axis = axis_;
-        A.split = split_;
-        A.gap = gap_;
+        A.split = L.split;
+        A.gap = L.gap;
         A.wpr = ceil_div(N_, 64);
         return A;
     }
@@ -2524,35 +2445,27 @@ private:
     void op_vorticity(int u, int v, int w, int mag) {
         for (Slab& sl : slabs_)
             for (int f : {u, v, w, mag}) ensure(sl, f);
-        if (trace_) {
-            acc_name_ = "vorticity";
-            acc_fn_ = [&](Slab& sl, int a, int b_, std::vector<Acc>& acc) {
-                int lo, hi;
-                wr_range(sl, a, b_, lo, hi);
-                acc.push_back({sl.field[u], false, a - 1, b_ + 1});
-                acc.push_back({sl.field[v], false, a - 1, b_ + 1});
-                acc.push_back({sl.field[w], false, a, b_});
-                acc.push_back({sl.field[mag], true, lo, hi});
-            };
-        }
-        for_planes([&](Slab& sl, int kb, int ke) {
-            sfk::ForceArgs<T> A = force_args();
-            A.u = sl.field[u];
-            A.v = sl.field[v];
-            A.w = sl.field[w];
-            A.mag = sl.field[mag];
-            hipLaunchKernelGGL((sfk::vorticity_mag_kernel<T>), dim3(force_blocks(ke - kb)), dim3(256), 0, sl.cur, sl.geom,
-                               A, kb, ke);
+        auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            acc.push_back({sl.field[u], false, a - 1, b_ + 1});
+            acc.push_back({sl.field[v], false, a - 1, b_ + 1});
+            acc.push_back({sl.field[w], false, a, b_});
+            acc.push_back({sl.field[mag], true, lo, hi});
+        };
+        for_planes("vorticity", accesses, [&](const Launch& L) {
+            sfk::ForceArgs<T> A = force_args(L);
+            A.u = L.sl.field[u];
+            A.v = L.sl.field[v];
+            A.w = L.sl.field[w];
+            A.mag = L.sl.field[mag];
+            launch_k(L, sfk::vorticity_mag_kernel<T>, dim3(force_blocks(L.ke - L.kb)), 256u, A);
         });
-        acc_fn_ = nullptr;
         const int m[1] = {mag};
         exchange<1>(m);
     }
 
     template <bool VORT, bool BUOY, bool BOUND>
-    void launch_forces(Slab& sl, const sfk::ForceArgs<T>& A, int kb, int ke) {
-        hipLaunchKernelGGL((sfk::add_forces_kernel<T, VORT, BUOY, BOUND>), dim3(force_blocks(ke - kb)), dim3(256), 0, sl.cur,
-                           sl.geom, A, kb, ke);
+    void launch_forces(const Launch& L, const sfk::ForceArgs<T>& A) {
+        launch_k(L, sfk::add_forces_kernel<T, VORT, BUOY, BOUND>, dim3(force_blocks(L.ke - L.kb)), 256u, A);
     }
 
     // add_forces(u, v, w, dens, src -> dst): dst_a = src_a + f_a on interior cells, src's shells copied where dst is
@@ -2572,28 +2485,24 @@ private:
             for (Slab& sl : slabs_) sl.field[MAG_SLOT] = sl.scratch[0];
             op_vorticity(u, v, w, MAG_SLOT);
         }
-        if (trace_) {
-            acc_name_ = "add_forces";
-            acc_fn_ = [&, vort, buoy](Slab& sl, int a, int b_, std::vector<Acc>& acc) {
-                int lo, hi;
-                wr_range(sl, a, b_, lo, hi);
-                if (vort) {
-                    acc.push_back({sl.field[u], false, a - 1, b_ + 1});
-                    acc.push_back({sl.field[v], false, a - 1, b_ + 1});
-                    acc.push_back({sl.field[w], false, a, b_});
-                    acc.push_back({sl.field[MAG_SLOT], false, a - 1, b_ + 1});
-                }
-                if (buoy) acc.push_back({sl.field[dens], false, a, b_});
-                for (int c = 0; c < 3; ++c) {
-                    const bool copy = src[c] != dst[c];  // shells copied too (wall planes on the end slabs)
-                    if (!(vort || copy || c == axis_)) continue;
-                    acc.push_back({sl.field[src[c]], false, copy ? lo : a, copy ? hi : b_});
-                    acc.push_back({sl.field[dst[c]], true, copy ? lo : a, copy ? hi : b_});
-                }
-            };
-        }
-        for_planes([&](Slab& sl, int kb, int ke) {
-            sfk::ForceArgs<T> A = force_args();
+        auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            if (vort) {
+                acc.push_back({sl.field[u], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[v], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[w], false, a, b_});
+                acc.push_back({sl.field[MAG_SLOT], false, a - 1, b_ + 1});
+            }
+            if (buoy) acc.push_back({sl.field[dens], false, a, b_});
+            for (int c = 0; c < 3; ++c) {
+                const bool copy = src[c] != dst[c];  // shells copied too (wall planes on the end slabs)
+                if (!(vort || copy || c == axis_)) continue;
+                acc.push_back({sl.field[src[c]], false, copy ? lo : a, copy ? hi : b_});
+                acc.push_back({sl.field[dst[c]], true, copy ? lo : a, copy ? hi : b_});
+            }
+        };
+        for_planes("add_forces", accesses, [&](const Launch& L) {
+            Slab& sl = L.sl;
+            sfk::ForceArgs<T> A = force_args(L);
             A.u = sl.field[u];
             A.v = sl.field[v];
             A.w = sl.field[w];
@@ -2604,13 +2513,12 @@ private:
                 A.dst[a] = sl.field[dst[a]];
             }
             if (vort && buoy)
-                bound ? launch_forces<true, true, true>(sl, A, kb, ke) : launch_forces<true, true, false>(sl, A, kb, ke);
+                bound ? launch_forces<true, true, true>(L, A) : launch_forces<true, true, false>(L, A);
             else if (vort)
-                bound ? launch_forces<true, false, true>(sl, A, kb, ke) : launch_forces<true, false, false>(sl, A, kb, ke);
+                bound ? launch_forces<true, false, true>(L, A) : launch_forces<true, false, false>(L, A);
             else
-                bound ? launch_forces<false, true, true>(sl, A, kb, ke) : launch_forces<false, true, false>(sl, A, kb, ke);
+                bound ? launch_forces<false, true, true>(L, A) : launch_forces<false, true, false>(L, A);
         });
-        acc_fn_ = nullptr;
         // the sources' ghost planes: the fused first sweep of diffuse evaluates on the first ghost plane and reads x0
         // and the initial iterate there (see op_project)
         exchange<3>(dst);
@@ -2621,33 +2529,28 @@ private:
     int N_, K_, device_;
     int L_ = 1, nranks_ = 1, rank_ = 0, P_ = 1, G_ = 1;
     int fuse_maxvec_ = 512, ovl_mode_ = 1;  // fuse_maxvec_: widest row (vectors) the fused kernels take
-    int trap_m_ = 4, trap_extra_ = 0, split_fields_ = 1, tuned_trap_ = -1, tuned_split_ = -1;
+    int trap_m_ = 4, split_fields_ = 1, tuned_trap_ = -1, tuned_split_ = -1;
     int bound_[4] = {-1, -1, -1, -1};  // resident source slots (sf_bind_sources)
     bool pending_join_ = false, split_enabled_ = true, graphs_ = false;
     std::vector<GraphEntry> graph_cache_;
-    int split_ = INT_MAX, gap_ = 0;  // plane-range split of the launch being issued (for_planes)
     T dt_{}, diff_{}, visc_{};
     T eps_{}, beta_{}, amb_{};  // forces of SPEC §8 (0: off)
     int axis_ = 1;
     int num_cu_ = 256;
     int nzl_ = 0, lead_ = 0, px_ = 0, nplanes_ = 0, nt_mode_ = 2;
     int advect_row_ = 1;  // 0 gather form always, 1 one cell per lane for the three velocity components, 2 / 3 always
-    bool dead_ishell_ = false;      // the solve being issued may leave its result's i-shell unwritten
     bool dead_ishell_opt_ = true;   // SF_ISHELL=2 switches the dead-shell elision off (1: on, 0: every sweep writes it)
-    bool ishell_skip_ = true, zero_skip_ = true, x_is_zero_ = false, fuse_src_ = true;
+    bool ishell_skip_ = true, zero_skip_ = true, fuse_src_ = true;
     bool fuse2_ = true;
     int march_k_ = 1, march_min_planes_ = 12;
     long march_min_cells_ = 2500000, sk2_min_cells_ = 60000000;
     int sk_s_ = 4;
     bool sk_first_ = true;
-    bool batch_now_ = false;  // the running solve launches its NF fields as one marching grid (batch_march)
     long plane_ = 0, field_elems_ = 0, pad_front_ = 0, pad_back_ = 0;
     std::vector<Slab> slabs_;
     FILE* trace_ = nullptr;  // SF_TRACE_SCHEDULE
     bool inject_trap_bug_ = false;
     std::map<const void*, int> buf_ids_;
-    AccFn acc_fn_;           // accesses of the operator being issued through for_planes (trace only)
-    const char* acc_name_ = "op";
     long xchg_seq_ = 0;
     ncclComm_t comm_ = nullptr;
     bool loopback_ = false, rccl_self_ = false;
