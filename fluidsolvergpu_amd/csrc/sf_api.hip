@@ -141,6 +141,12 @@ int sf_diffuse(sf_ctx* ctx, int b, int x, int x0, double diff) {
 int sf_advect(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w) {
     return guarded(ctx, [&](SolverBase& s) { s.advect(b, d, d0, u, v, w); });
 }
+int sf_advect_maccormack(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w) {
+    return guarded(ctx, [&](SolverBase& s) { s.advect_maccormack(b, d, d0, u, v, w); });
+}
+int sf_set_advection(sf_ctx* ctx, int velocity_scheme, int density_scheme) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_advection(velocity_scheme, density_scheme); });
+}
 int sf_project(sf_ctx* ctx, int u, int v, int w, int p, int div) {
     return guarded(ctx, [&](SolverBase& s) { s.project(u, v, w, p, div); });
 }

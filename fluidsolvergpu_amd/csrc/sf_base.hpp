@@ -76,6 +76,8 @@ public:
     virtual void lin_solve(int b, int x, int x0, double a, double c, int iters) = 0;
     virtual void diffuse(int b, int x, int x0, double diff) = 0;
     virtual void advect(int b, int d, int d0, int u, int v, int w) = 0;
+    virtual void advect_maccormack(int b, int d, int d0, int u, int v, int w) = 0;
+    virtual void set_advection(int velocity_scheme, int density_scheme) = 0;
     virtual void project(int u, int v, int w, int p, int div) = 0;
     virtual void vorticity_magnitude(int u, int v, int w, int dst) = 0;
     virtual void add_forces(int u, int v, int w, int dens, int su, int sv, int sw) = 0;

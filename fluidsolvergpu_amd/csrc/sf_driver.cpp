@@ -24,9 +24,11 @@
 //
 //   sf_driver [--n 64] [--steps 20] [--iters 20] [--dtype f32|f64] [--every 10] [--out DIR]
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
-//             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1]
+//             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
+// --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
+// (default: first-order semi-Lagrangian for both, the §3 step).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -62,6 +64,7 @@ struct Options {
     int n = 64, steps = 20, iters = 20, every = 10, device = 0, slabs = 1, tracers = 0;
     double vorticity = 0.0, buoyancy = 0.0, ambient = 0.0;
     int buoyancy_axis = 1;
+    int advect_vel = SF_ADVECT_SEMI_LAGRANGIAN, advect_dens = SF_ADVECT_SEMI_LAGRANGIAN;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
     int rank = 0, world = 1, local_rank = 0;
@@ -160,6 +163,15 @@ static Options parse(int argc, char** argv) {
         else if (s == "--buoyancy") o.buoyancy = atof(next());
         else if (s == "--ambient") o.ambient = atof(next());
         else if (s == "--buoyancy-axis") o.buoyancy_axis = atoi(next());
+        else if (s == "--maccormack") {
+            const std::string which = next();
+            if (which != "vel" && which != "dens" && which != "both") {
+                fprintf(stderr, "--maccormack takes vel, dens or both, not %s\n", which.c_str());
+                exit(2);
+            }
+            if (which != "dens") o.advect_vel = SF_ADVECT_MACCORMACK;
+            if (which != "vel") o.advect_dens = SF_ADVECT_MACCORMACK;
+        }
         // rehearsal of ONE rank's share on a one-GPU box: the geometry, buffers, launches and frame file of rank
         // --rank of --world, halo messages replaced by device-local copies (SF_FLAG_LOOPBACK_HALO), no communicator
         else if (s == "--loopback") o.loopback = true;
@@ -307,6 +319,7 @@ static int run(const Options& o) {
     // forces (SPEC §8): added by every vel_step to copies of the bound sources
     SF_CHECK_RETURN(sf_set_vorticity_confinement(g_ctx, o.vorticity));
     SF_CHECK_RETURN(sf_set_buoyancy(g_ctx, o.buoyancy, o.ambient, o.buoyancy_axis));
+    SF_CHECK_RETURN(sf_set_advection(g_ctx, o.advect_vel, o.advect_dens));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

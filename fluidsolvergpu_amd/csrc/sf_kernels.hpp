@@ -1936,6 +1936,233 @@ __global__ void __launch_bounds__(256) advect_row_kernel(Geom g, AdvectArgs<T, N
 }
 
 // ---------------------------------------------------------------------------------------------
+// advect_mc: second pass of the limited MacCormack scheme (SPEC §9 step 2) + fused set_bnd. `hat` is the first-order
+// advect of d0 (pass 1, shells and ghost planes included). Per cell: the forward trace of advect gives the eight d0
+// samples whose min / max bound the result, the reverse trace (the same expressions with +dt0) interpolates hat into
+// `bar`, and d = clamp(hat + half*(d0 - bar), mn, mx), or hat where either trace was clamped at a wall. Both traces
+// come from one load of (u, v, w); NF fields share them.
+// Algorithmic traffic: 3 (velocity) + 2 NF (d0 and hat, assuming reuse) + NF (write) words per cell on top of pass 1
+// (vel_step: d0 is the velocity, 9 words on advect's 6; dens_step: 6 on 5).
+template <class T, int NF>
+struct AdvectMcArgs {
+    T* d[NF];
+    const T* d0[NF];
+    const T* hat[NF];
+    int b[NF];
+    const T* u;
+    const T* v;
+    const T* w;
+    T dt0;
+    int* flag;        // set to 1 if either trace left the planes this slab stores
+    int skip_ishell;  // as AdvectArgs::skip_ishell
+};
+
+// One trace of SPEC §3 advect from the unclamped position (x, y, z): weights, the offset of sample (i0, j0, k0),
+// whether a clamp fired (SPEC §9 cf / cr) and whether k0 / k0+1 fall outside the slab's stored planes (then clamped
+// into them for memory safety, as advect does).
+template <class T>
+struct McTrace {
+    T s1, t1, r1;
+    long p00;
+    bool clamped, outside;
+};
+template <class T>
+__device__ __forceinline__ McTrace<T> mc_trace(const Geom& g, T x, T y, T z) {
+    const int N = g.N;
+    const T lo = T(0.5), hi = (T)N + T(0.5);
+    McTrace<T> t;
+    t.clamped = (x < lo) | (x > hi) | (y < lo) | (y > hi) | (z < lo) | (z > hi);  // (lo < hi: the same six outcomes)
+    if (x < lo) x = lo;
+    if (x > hi) x = hi;
+    if (y < lo) y = lo;
+    if (y > hi) y = hi;
+    if (z < lo) z = lo;
+    if (z > hi) z = hi;
+    int ia = (x == x) ? (int)x : 0;
+    int ja = (y == y) ? (int)y : 0;
+    int ka = (z == z) ? (int)z : 0;
+    ia = ia < 0 ? 0 : (ia > N ? N : ia);
+    ja = ja < 0 ? 0 : (ja > N ? N : ja);
+    ka = ka < 0 ? 0 : (ka > N ? N : ka);
+    t.s1 = x - (T)ia;
+    t.t1 = y - (T)ja;
+    t.r1 = z - (T)ka;
+    int kla = ka - g.kg0;  // local plane of k0; k1 = kla + 1 must also be stored
+    t.outside = kla < 0 || kla > g.np - 2;
+    kla = kla < 0 ? 0 : (kla > g.np - 2 ? g.np - 2 : kla);
+    t.p00 = row0(g, ja, kla) + ia;  // (i0,j0,k0); +plane: k1; +px: j1
+    return t;
+}
+
+// SPEC §9 select forms (they fix the result for signed zeros and NaN)
+template <class T>
+__device__ __forceinline__ T mc_min(T p, T q) {
+    return q < p ? q : p;
+}
+template <class T>
+__device__ __forceinline__ T mc_max(T p, T q) {
+    return q > p ? q : p;
+}
+
+// The cell's result from its samples: a0[c] / a1[c] the d0 samples at i0 / i0+1 of the forward trace, h0 / h1 the hat
+// samples of the reverse trace R, corner c = (j0,k0), (j0,k1), (j1,k0), (j1,k1).
+template <class T>
+__device__ __forceinline__ T mc_cell(const T (&a0)[4], const T (&a1)[4], const T (&h0)[4], const T (&h1)[4],
+                                     const McTrace<T>& R, T hatq, T d0q, bool fallback) {
+    const T mn = mc_min(mc_min(mc_min(a0[0], a0[1]), mc_min(a0[2], a0[3])),
+                        mc_min(mc_min(a1[0], a1[1]), mc_min(a1[2], a1[3])));
+    const T mx = mc_max(mc_max(mc_max(a0[0], a0[1]), mc_max(a0[2], a0[3])),
+                        mc_max(mc_max(a1[0], a1[1]), mc_max(a1[2], a1[3])));
+    const T s1 = R.s1, t1 = R.t1, r1 = R.r1;
+    const T s0 = T(1) - s1, t0 = T(1) - t1, r0 = T(1) - r1;
+    const T bar = s0 * (t0 * (r0 * h0[0] + r1 * h0[1]) + t1 * (r0 * h0[2] + r1 * h0[3])) +
+                  s1 * (t0 * (r0 * h1[0] + r1 * h1[1]) + t1 * (r0 * h1[2] + r1 * h1[3]));
+    T r = hatq + T(0.5) * (d0q - bar);
+    if (r < mn) r = mn;
+    if (r > mx) r = mx;
+    if (fallback) r = hatq;
+    return r;
+}
+
+// Gather form: the cell-to-thread mapping of advect_kernel (W cells per thread, element-aligned (i0, i0+1) pair
+// loads). The traces of the W cells are taken once; then, field by field, the thread requests all its gathers
+// (4 corner pairs x W cells of d0 and of hat) before it consumes the first.
+template <class T, int NF>
+__global__ void __launch_bounds__(256) advect_mc_kernel(Geom g, AdvectMcArgs<T, NF> A, int kb, int ke, TileMap m) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    typedef T Pair __attribute__((ext_vector_type(2), aligned(sizeof(T))));
+    int i0, j, kl, nv;
+    if (!flat_cell<W>(g, m, kb, ke, i0, j, kl, nv)) return;
+    const long q = row0(g, j, kl) + i0;
+    const V uu = ldv(A.u + q), vv = ldv(A.v + q), ww = ldv(A.w + q);
+    const int kg = g.kg0 + kl;
+    // (cells past the row end trace from the padding: addresses stay inside the buffer, nothing of them is stored and
+    // they cannot raise the halo flag — as in advect_kernel)
+    McTrace<T> F[W], R[W];
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+        const T au = A.dt0 * uu[e], av = A.dt0 * vv[e], aw = A.dt0 * ww[e];
+        F[e] = mc_trace<T>(g, (T)(i0 + e) - au, (T)j - av, (T)kg - aw);
+        R[e] = mc_trace<T>(g, (T)(i0 + e) + au, (T)j + av, (T)kg + aw);
+        bad |= (e < nv) && (F[e].outside || R[e].outside);
+    }
+    const long off[4] = {0, g.plane, g.px, g.px + g.plane};
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const T* __restrict__ d0 = A.d0[f];
+        const T* __restrict__ hat = A.hat[f];
+        Pair CA[W][4], CH[W][4];
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                CA[e][c] = *reinterpret_cast<const Pair*>(d0 + F[e].p00 + off[c]);
+                CH[e][c] = *reinterpret_cast<const Pair*>(hat + R[e].p00 + off[c]);
+            }
+        const V dq = ldv(d0 + q), hq = ldv(hat + q);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            T a0[4], a1[4], h0[4], h1[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                a0[c] = CA[e][c][0];
+                a1[c] = CA[e][c][1];
+                h0[c] = CH[e][c][0];
+                h1[c] = CH[e][c][1];
+            }
+            out[e] = mc_cell<T>(a0, a1, h0, h1, R[e], hq[e], dq[e], F[e].clamped || R[e].clamped);
+        }
+        store_cells<T, W>(A.d[f], q - i0, i0, out, nv);
+        emit_shells<T, W>(A.d[f], g, A.b[f], i0, j, kl, out, nv, A.skip_ishell == 0);
+    }
+    if (bad) atomicOr(A.flag, 1);
+}
+
+// One cell per lane along i: the mapping of advect_row_kernel, for both traces. PAIRS = false (fp32): each lane loads
+// its four i0 samples of d0 (forward trace) and of hat (reverse trace) and takes the i0+1 samples from the next lane
+// by a DPP wave shift wherever that lane's trace landed one cell further in the same row; the others load their own
+// under an exec mask. PAIRS = true (fp64): own (i0, i0+1) pair loads. All 16 gathers per field of a lane are requested
+// before the first is consumed.
+template <class T, int NF, bool PAIRS = false>
+__global__ void __launch_bounds__(256) advect_mc_row_kernel(Geom g, AdvectMcArgs<T, NF> A, int kb, int ke, int wpr) {
+    typedef T Pair __attribute__((ext_vector_type(2), aligned(sizeof(T))));
+    const int lane = (int)threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + ((int)threadIdx.x >> 6));
+    const int N = g.N;
+    const int row = wv / wpr;  // (wave-uniform: scalar arithmetic)
+    if (row >= N * (ke - kb)) return;
+    const int seg = wv - row * wpr;
+    const int kq = row / N;
+    const int kl = kb + kq, j = 1 + row - kq * N;
+    const int i = 1 + seg * 64 + lane;
+    const bool ok = i <= N;
+    const int ic = ok ? i : N;  // lanes past the row end repeat its last cell and store nothing
+    const long q = row0(g, j, kl) + ic;
+    const int kg = g.kg0 + kl;
+    const T au = A.dt0 * A.u[q], av = A.dt0 * A.v[q], aw = A.dt0 * A.w[q];
+    const McTrace<T> F = mc_trace<T>(g, (T)ic - au, (T)j - av, (T)kg - aw);
+    const McTrace<T> R = mc_trace<T>(g, (T)ic + au, (T)j + av, (T)kg + aw);
+    const bool bad = ok && (F.outside || R.outside);
+    // does the next lane's trace land in the next cell of the same row? (lane 63 receives 0: never equal)
+    const bool shf = __builtin_bit_cast(long, lane_dn(__builtin_bit_cast(double, F.p00))) == F.p00 + 1;
+    const bool shr = __builtin_bit_cast(long, lane_dn(__builtin_bit_cast(double, R.p00))) == R.p00 + 1;
+    const long off[4] = {0, g.plane, g.px, g.px + g.plane};
+    T a0[NF][4], a1[NF][4] = {}, h0[NF][4], h1[NF][4] = {}, dq[NF], hq[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if constexpr (PAIRS) {
+                const Pair pa = *reinterpret_cast<const Pair*>(A.d0[f] + F.p00 + off[c]);
+                const Pair ph = *reinterpret_cast<const Pair*>(A.hat[f] + R.p00 + off[c]);
+                a0[f][c] = pa[0];
+                a1[f][c] = pa[1];
+                h0[f][c] = ph[0];
+                h1[f][c] = ph[1];
+            } else {
+                a0[f][c] = A.d0[f][F.p00 + off[c]];
+                h0[f][c] = A.hat[f][R.p00 + off[c]];
+            }
+        }
+        dq[f] = A.d0[f][q];
+        hq[f] = A.hat[f][q];
+    }
+    if (!PAIRS && !shf) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) a1[f][c] = A.d0[f][F.p00 + off[c] + 1];
+    }
+    if (!PAIRS && !shr) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) h1[f][c] = A.hat[f][R.p00 + off[c] + 1];
+    }
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        if constexpr (!PAIRS) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const T na = lane_dn(a0[f][c]), nh = lane_dn(h0[f][c]);
+                a1[f][c] = shf ? na : a1[f][c];
+                h1[f][c] = shr ? nh : h1[f][c];
+            }
+        }
+        T out[1];
+        out[0] = mc_cell<T>(a0[f], a1[f], h0[f], h1[f], R, hq[f], dq[f], F.clamped || R.clamped);
+        if (ok) {
+            A.d[f][q] = out[0];
+            emit_shells<T, 1>(A.d[f], g, A.b[f], i, j, kl, out, 1, A.skip_ishell == 0);
+        }
+    }
+    if (bad) atomicOr(A.flag, 1);
+}
+
+// ---------------------------------------------------------------------------------------------
 // project, first half: div = c_div*((du + dv) + dw), set_bnd(0, div). p is zeroed by the caller
 // (hipMemsetAsync over the whole field, which also covers set_bnd(0,p) and the ghost planes).
 template <class T>

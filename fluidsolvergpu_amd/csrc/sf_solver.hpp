@@ -23,11 +23,14 @@ class Solver final : public SolverBase {
     // internal slot for |curl u| of the forces (SPEC §8) while they are issued: it aliases scratch[0], which no solve
     // holds at that point, and is null otherwise (exchange() addresses fields by slot)
     static constexpr int MAG_SLOT = SF_NUM_FIELDS;
+    // internal slots for `hat`, the first-order result inside advect_mc (SPEC §9): HAT_SLOT + f aliases scratch[f] for
+    // the duration of op_advect_mc (no solve and no force pass runs inside it) and is null otherwise
+    static constexpr int HAT_SLOT = SF_NUM_FIELDS;
 
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
         sfk::Geom geom{};
-        T* field[SF_NUM_FIELDS + 1] = {};
+        T* field[SF_NUM_FIELDS + NSCRATCH] = {};
         T* scratch[NSCRATCH] = {};
         T* snap[4] = {};               // snapshot buffers for asynchronous output
         hipStream_t os = nullptr;      // output (copy) stream
@@ -520,6 +523,23 @@ public:
         op_advect<1>(ds, d0s, bs, u, v, w, false);
     }
 
+    // SPEC §9 advect_mc
+    void advect_maccormack(int b, int d, int d0, int u, int v, int w) override {
+        for (int f : {d, d0, u, v, w}) check_field(f);
+        check_b(b);
+        SF_REQUIRE(d != d0 && d != u && d != v && d != w, "advect_maccormack: output must not alias an input");
+        SF_HIP(hipSetDevice(device_));
+        const int ds[1] = {d}, d0s[1] = {d0}, bs[1] = {b};
+        op_advect_mc<1>(ds, d0s, bs, u, v, w, false);
+    }
+
+    void set_advection(int velocity_scheme, int density_scheme) override {
+        for (int s : {velocity_scheme, density_scheme})
+            SF_REQUIRE(s == SF_ADVECT_SEMI_LAGRANGIAN || s == SF_ADVECT_MACCORMACK, "advection scheme must be 0 or 1");
+        mc_vel_ = velocity_scheme;
+        mc_dens_ = density_scheme;
+    }
+
     void project(int u, int v, int w, int p, int div) override {
         const int all[5] = {u, v, w, p, div};
         for (int a = 0; a < 5; ++a) {
@@ -584,6 +604,7 @@ public:
         T dt, diff, visc;
         T eps, beta, amb;  // forces (SPEC §8): their scalars are baked into the captured launches
         int axis;
+        int mc_vel, mc_dens;  // advection schemes (SPEC §9): they decide which launches are captured
         int bound[4];
         hipGraphExec_t exec;
     };
@@ -614,6 +635,7 @@ public:
         for (GraphEntry& e : graph_cache_)
             if (e.op == op && e.K == K_ && e.dt == dt_ && e.diff == diff_ && e.visc == visc_ && same_bits(e.eps, eps_) &&
                 same_bits(e.beta, beta_) && same_bits(e.amb, amb_) && e.axis == axis_ &&
+                e.mc_vel == mc_vel_ && e.mc_dens == mc_dens_ &&
                 std::equal(e.bound, e.bound + 4, bound_) && e.before == before) {
                 SF_HIP(hipGraphLaunch(e.exec, sl.cs));
                 apply_state(e.after);
@@ -642,6 +664,8 @@ public:
         e.beta = beta_;
         e.amb = amb_;
         e.axis = axis_;
+        e.mc_vel = mc_vel_;
+        e.mc_dens = mc_dens_;
         std::copy(bound_, bound_ + 4, e.bound);
         SF_HIP(hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0));
         SF_HIP(hipGraphDestroy(graph));
@@ -693,7 +717,10 @@ public:
         swap_slots(SF_V0, SF_V);
         swap_slots(SF_W0, SF_W);
         // the advected velocity goes straight into the second projection: same argument as for the diffused one
-        op_advect<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
+        if (mc_vel_ == SF_ADVECT_MACCORMACK)
+            op_advect_mc<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
+        else
+            op_advect<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
         op_project(SF_U, SF_V, SF_W, SF_U0, SF_V0, dead, false);
     }
 
@@ -710,7 +737,10 @@ public:
             op_lin_solve<1>(x, x0, b0, a, T(1) + T(6) * a, K_, false);
         }
         swap_slots(SF_DENS0, SF_DENS);
-        op_advect<1>(x, x0, b0, SF_U, SF_V, SF_W, false);
+        if (mc_dens_ == SF_ADVECT_MACCORMACK)
+            op_advect_mc<1>(x, x0, b0, SF_U, SF_V, SF_W, false);
+        else
+            op_advect<1>(x, x0, b0, SF_U, SF_V, SF_W, false);
     }
 
     void set_iters(int iters) override {
@@ -2351,6 +2381,77 @@ private:
         exchange<NF>(d);
     }
 
+    // SPEC §9 advect_mc: pass 1 is op_advect into `hat` (every shell written, ghost planes exchanged: pass 2 reads hat
+    // wherever advect reads d0), pass 2 the limited correction into d. dead_ishell applies to d only.
+    template <int NF>
+    void op_advect_mc(const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u, int v, int w, bool dead_ishell) {
+        static_assert(NF <= NSCRATCH, "not enough scratch buffers");
+        const T dt0 = dt_ * (T)N_;
+        for (Slab& sl : slabs_) {
+            for (int f = 0; f < NF; ++f) {
+                ensure(sl, d[f]);
+                ensure(sl, d0[f]);
+            }
+            for (int f : {u, v, w}) ensure(sl, f);
+        }
+        // hat lives in the scratch buffers, addressed through the HAT slots while this operator is issued (op_advect and
+        // exchange take slots). The solves swap scratch pointers with slots, so the alias is taken afresh on every call
+        // and dropped on every way out.
+        struct HatSlots {
+            std::vector<Slab>& slabs;
+            explicit HatSlots(std::vector<Slab>& s) : slabs(s) {
+                for (Slab& sl : slabs)
+                    for (int f = 0; f < NF; ++f) sl.field[HAT_SLOT + f] = sl.scratch[f];
+            }
+            ~HatSlots() {
+                for (Slab& sl : slabs)
+                    for (int f = 0; f < NF; ++f) sl.field[HAT_SLOT + f] = nullptr;
+            }
+        } hat_slots(slabs_);
+        int hat[NF];
+        for (int f = 0; f < NF; ++f) hat[f] = HAT_SLOT + f;
+        op_advect<NF>(hat, d0, b, u, v, w, false);
+        auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            for (int f = 0; f < NF; ++f) {
+                acc.push_back({sl.field[d0[f]], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[hat[f]], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[d[f]], true, lo, hi});
+            }
+            for (int q : {u, v, w}) acc.push_back({sl.field[q], false, a, b_});
+        };
+        for_planes("advect_mc", accesses, [&](const Launch& L) {
+            Slab& sl = L.sl;
+            sfk::AdvectMcArgs<T, NF> A;
+            for (int f = 0; f < NF; ++f) {
+                A.d[f] = sl.field[d[f]];
+                A.d0[f] = sl.field[d0[f]];
+                A.hat[f] = sl.field[hat[f]];
+                A.b[f] = b[f];
+            }
+            A.u = sl.field[u];
+            A.v = sl.field[v];
+            A.w = sl.field[w];
+            A.dt0 = dt0;
+            A.flag = sl.d_flag;
+            A.skip_ishell = dead_ishell ? 1 : 0;
+            // the cell-to-lane mappings of op_advect, chosen the same way (SF_ADVECT_ROW as there)
+            if (advect_row_ >= 2 || (advect_row_ == 1 && NF >= 2)) {
+                const int wpr = ceil_div(N_, 64);
+                const long waves = (long)wpr * N_ * (L.ke - L.kb);
+                if (advect_row_ == 3 || (advect_row_ == 1 && sizeof(T) == 8))
+                    launch_k(L, sfk::advect_mc_row_kernel<T, NF, true>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
+                else
+                    launch_k(L, sfk::advect_mc_row_kernel<T, NF>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
+            } else {
+                dim3 block;
+                unsigned nblocks;
+                const sfk::TileMap m = flat_map(L, block, nblocks);
+                launch_k(L, sfk::advect_mc_kernel<T, NF>, dim3(nblocks), block, A, m);
+            }
+        }, 1, 0, /*interior_reads_ghosts=*/true);  // either trace may reach a ghost plane from any plane
+        exchange<NF>(d);
+    }
+
     // mirror_u: u's i-shell was left unwritten by the solve before (b = 1: mirrored in project_div); dead_p: nothing reads
     // p after this projection (its slot is overwritten before anyone looks), so the solve leaves p's i-shell unwritten
     // and project_sub mirrors it. Both false for the public sf_project().
@@ -2536,6 +2637,7 @@ private:
     T dt_{}, diff_{}, visc_{};
     T eps_{}, beta_{}, amb_{};  // forces of SPEC §8 (0: off)
     int axis_ = 1;
+    int mc_vel_ = SF_ADVECT_SEMI_LAGRANGIAN, mc_dens_ = SF_ADVECT_SEMI_LAGRANGIAN;  // advection schemes (SPEC §9)
     int num_cu_ = 256;
     int nzl_ = 0, lead_ = 0, px_ = 0, nplanes_ = 0, nt_mode_ = 2;
     int advect_row_ = 1;  // 0 gather form always, 1 one cell per lane for the three velocity components, 2 / 3 always

@@ -23,6 +23,7 @@ FIELD_IDS = {"u": 0, "v": 1, "w": 2, "u0": 3, "v0": 4, "w0": 5, "dens": 6, "dens
 FIELD_NAMES = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
 NCCL_ID_BYTES = 128
 SF_FLAG_LOOPBACK_HALO, SF_FLAG_RCCL_SELF = 1, 2
+SF_ADVECT_SEMI_LAGRANGIAN, SF_ADVECT_MACCORMACK = 0, 1
 TRANSPORTS = ("none", "copy", "rccl", "rccl-self", "loopback")
 
 # every symbol include/sfgpu.h declares (tests check that the library exports all of them)
@@ -35,6 +36,7 @@ ABI_SYMBOLS = (
     "sf_tracers_set", "sf_tracers_advect", "sf_tracers_get", "sf_bind_sources", "sf_transport_info", "sf_snapshot_read_planes",
     "sf_tracers_owned", "sf_tracers_get_owned", "sf_tracers_set_capacity",
     "sf_set_vorticity_confinement", "sf_set_buoyancy", "sf_vorticity_magnitude", "sf_add_forces",
+    "sf_set_advection", "sf_advect_maccormack",
 )
 
 
@@ -74,6 +76,8 @@ lib.sf_vorticity_magnitude.argtypes = [_ctx] + [C.c_int] * 4
 lib.sf_add_forces.argtypes = [_ctx] + [C.c_int] * 7
 lib.sf_set_vorticity_confinement.argtypes = [_ctx, C.c_double]
 lib.sf_set_buoyancy.argtypes = [_ctx, C.c_double, C.c_double, C.c_int]
+lib.sf_set_advection.argtypes = [_ctx, C.c_int, C.c_int]
+lib.sf_advect_maccormack.argtypes = [_ctx] + [C.c_int] * 6
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -247,6 +251,14 @@ class FluidSolver:
 
     def add_forces(self, u, v, w, dens, su, sv, sw):
         self._ck(lib.sf_add_forces(self._h, _fid(u), _fid(v), _fid(w), _fid(dens), _fid(su), _fid(sv), _fid(sw)))
+
+    # -- MacCormack advection (docs/SPEC.md §9) -----------------------------------------------
+    def set_advection(self, velocity=SF_ADVECT_SEMI_LAGRANGIAN, density=SF_ADVECT_SEMI_LAGRANGIAN):
+        """Advection scheme of vel_step / dens_step: SF_ADVECT_SEMI_LAGRANGIAN (the default) or SF_ADVECT_MACCORMACK."""
+        self._ck(lib.sf_set_advection(self._h, int(velocity), int(density)))
+
+    def advect_maccormack(self, b, d, d0, u, v, w):
+        self._ck(lib.sf_advect_maccormack(self._h, int(b), _fid(d), _fid(d0), _fid(u), _fid(v), _fid(w)))
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

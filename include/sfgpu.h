@@ -149,6 +149,19 @@ int sf_set_buoyancy(sf_ctx* ctx, double beta, double ambient, int axis);
 int sf_vorticity_magnitude(sf_ctx* ctx, int u, int v, int w, int dst);
 int sf_add_forces(sf_ctx* ctx, int u, int v, int w, int dens, int su, int sv, int sw);
 
+/* MacCormack advection of docs/SPEC.md §9 (Selle, Fedkiw, Kim, Liu & Rossignac, "An Unconditionally Stable MacCormack
+ * Method", J. Sci. Comput. 2008): second order, built from two first-order advects and limited to the extrema of the
+ * cells the back-trace interpolates; first order wherever a trace was clamped at a wall.
+ * sf_set_advection selects the scheme vel_step uses for its three advects and dens_step for its one. Both default
+ * to SF_ADVECT_SEMI_LAGRANGIAN, the §3 step exactly; any other value is SF_ERR_INVALID. The choice is per context
+ * and, like sf_set_coefficients, must be the same on every rank. On a decomposed grid the condition of sf_advect
+ * (|dt*N*w| < 1, else SF_ERR_HALO_EXCEEDED at the next sf_sync) holds for both traces. */
+enum sf_advection { SF_ADVECT_SEMI_LAGRANGIAN = 0, SF_ADVECT_MACCORMACK = 1 };
+int sf_set_advection(sf_ctx* ctx, int velocity_scheme, int density_scheme);
+/* The operator singly: d = advect_mc(b, d0; u, v, w) with the context's dt, set_bnd(b, d) included. As with
+ * sf_advect the output must not alias an input. */
+int sf_advect_maccormack(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w);
+
 /* Asynchronous frame output (the reference blocks on cudaDeviceSynchronize + cudaMemcpy +
  * per-value sprintf every output step, solver-unidyn.cu:475-487). sf_snapshot copies up to 4 fields into
  * context-owned snapshot buffers on the compute stream (device to device, ordered after everything issued
