@@ -212,6 +212,12 @@ int sf_tracers_get_owned(sf_ctx* ctx, int* ids, void* xyz, void* dens_sample, vo
 int sf_tracers_set_capacity(sf_ctx* ctx, int per_direction) {
     return guarded(ctx, [&](SolverBase& s) { s.tracers_set_capacity(per_direction); });
 }
+int sf_reduce(sf_ctx* ctx, int op, int field, double* out) {
+    return guarded(ctx, [&](SolverBase& s) { s.reduce(op, field, out); });
+}
+int sf_diagnostics_get(sf_ctx* ctx, sf_diagnostics* out) {
+    return guarded(ctx, [&](SolverBase& s) { s.diagnostics(out); });
+}
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });
 }

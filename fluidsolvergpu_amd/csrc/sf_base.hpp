@@ -102,6 +102,8 @@ public:
     virtual void tracers_set_capacity(int per_direction) = 0;
     virtual int tracers_owned() = 0;
     virtual void tracers_get_owned(int* ids, void* xyz, void* dens, void* speed) = 0;
+    virtual void reduce(int op, int field, double* out) = 0;
+    virtual void diagnostics(sf_diagnostics* out) = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

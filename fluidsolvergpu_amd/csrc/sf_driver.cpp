@@ -25,10 +25,16 @@
 //   sf_driver [--n 64] [--steps 20] [--iters 20] [--dtype f32|f64] [--every 10] [--out DIR]
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
+//             [--monitor M]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
 // (default: first-order semi-Lagrangian for both, the §3 step).
+// --monitor M: after every M-th step (t = 0, M, 2M, ... as --every counts) rank 0 prints one line
+//   monitor step=<t> mass=<g> kinetic=<g> max_div=<g> cfl=<g> nonfinite=<n>
+// from sf_diagnostics_get (docs/SPEC.md §10; %.17g, so the doubles read back exactly; every rank holds the same
+// numbers). A state with nonfinite > 0 ends the run: an error naming the step, exit status 3. Without --monitor the
+// driver issues exactly the calls it issued before the option existed.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -61,7 +67,7 @@ static sf_ctx* g_ctx = nullptr;
     }
 
 struct Options {
-    int n = 64, steps = 20, iters = 20, every = 10, device = 0, slabs = 1, tracers = 0;
+    int n = 64, steps = 20, iters = 20, every = 10, device = 0, slabs = 1, tracers = 0, monitor = 0;
     double vorticity = 0.0, buoyancy = 0.0, ambient = 0.0;
     int buoyancy_axis = 1;
     int advect_vel = SF_ADVECT_SEMI_LAGRANGIAN, advect_dens = SF_ADVECT_SEMI_LAGRANGIAN;
@@ -163,6 +169,13 @@ static Options parse(int argc, char** argv) {
         else if (s == "--buoyancy") o.buoyancy = atof(next());
         else if (s == "--ambient") o.ambient = atof(next());
         else if (s == "--buoyancy-axis") o.buoyancy_axis = atoi(next());
+        else if (s == "--monitor") {
+            o.monitor = atoi(next());
+            if (o.monitor < 1) {
+                fprintf(stderr, "--monitor takes a step count >= 1\n");
+                exit(2);
+            }
+        }
         else if (s == "--maccormack") {
             const std::string which = next();
             if (which != "vel" && which != "dens" && which != "both") {
@@ -393,6 +406,22 @@ static int run(const Options& o) {
         SF_CHECK_RETURN(sf_timer_stop(g_ctx, &elapsedTime));
         total_ms += elapsedTime;
         if (!o.quiet && talk) std::cout << "done.\nElapsed kernel time: " << elapsedTime << " ms\n";
+
+        if (o.monitor > 0 && t % o.monitor == 0) {
+            sf_diagnostics d;
+            SF_CHECK_RETURN(sf_diagnostics_get(g_ctx, &d));  // collective: every rank calls it, rank 0 talks
+            if (talk) {
+                printf("monitor step=%d mass=%.17g kinetic=%.17g max_div=%.17g cfl=%.17g nonfinite=%lld\n", t, d.mass,
+                       d.kinetic, d.max_div, d.cfl, d.nonfinite);
+                fflush(stdout);
+            }
+            if (d.nonfinite > 0) {
+                if (talk)
+                    fprintf(stderr, "Error: %lld cells are not finite after step %d: the run has blown up\n", d.nonfinite, t);
+                if (writer.joinable()) writer.join();
+                exit(3);
+            }
+        }
 
         if (o.every > 0 && t % o.every == 0) {
             const int frame = t / o.every;

@@ -2735,4 +2735,217 @@ static __global__ void __launch_bounds__(256) copy16_kernel(const float4* __rest
     if (q < n) dst[q] = src[q];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reductions and diagnostics (docs/SPEC.md §10). The order of every sum is part of the SPEC, so nothing here uses an
+// atomic, and nothing depends on the launch geometry: one wave owns one row (j, k) and is the SPEC's 64 lane
+// accumulators — lane l takes the 16-byte vectors l, l + 64, ... of the row in increasing i, the accumulators are
+// folded by halving across the wave (DPP within a row of 16 lanes, ds_bpermute across), and lane 0 stores the row's
+// record. fold_rows_kernel then folds the N row records of a plane by halving through LDS. The per-plane records go
+// to the host, which adds them in global k order (Solver::finish_records).
+// Loads are unconditional: a lane past the row end loads the row's last vector and its terms are replaced by the
+// identity of the fold (+0.0 for a sum: every accumulator starts at +0.0 and so is never -0; the start value for a
+// select), so there is no branch round a memory operation.
+enum { RED_SUM = 0, RED_SUM_SQ = 1, RED_MIN = 2, RED_MAX = 3, RED_MAX_ABS = 4, RED_COUNT_NONFINITE = 5 };
+constexpr int DIAG_NV = 10;  // values per row / plane record of the diagnostics pass (order: Solver::diagnostics)
+
+// lane l receives the 32-bit value of lane l + OFF (only lanes whose source exists are used)
+template <int OFF>
+__device__ __forceinline__ int lane_plus(int v) {
+    if constexpr (OFF < 16)
+        return __builtin_amdgcn_mov_dpp(v, 0x100 + OFF, 0xf, 0xf, true);  // row_shl:OFF
+    else
+        return __shfl_down(v, OFF, 64);
+}
+template <int OFF>
+__device__ __forceinline__ float lane_plus(float v) {
+    return __builtin_bit_cast(float, lane_plus<OFF>(__builtin_bit_cast(int, v)));
+}
+template <int OFF>
+__device__ __forceinline__ double lane_plus(double v) {
+    const long long b = __builtin_bit_cast(long long, v);
+    const int lo = lane_plus<OFF>((int)(b & 0xffffffffLL)), hi = lane_plus<OFF>((int)(b >> 32));
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
+}
+
+// SPEC §10 selects: a candidate that is not finite is never taken
+template <class S>
+__device__ __forceinline__ S sel_min(S m, S v) {
+    return (isfinite(v) && v < m) ? v : m;
+}
+template <class S>
+__device__ __forceinline__ S sel_max(S m, S v) {
+    return (isfinite(v) && v > m) ? v : m;
+}
+
+struct FoldSum {
+    template <class S> __device__ __forceinline__ S operator()(S a, S b) const { return a + b; }
+};
+struct FoldMin {
+    template <class S> __device__ __forceinline__ S operator()(S a, S b) const { return b < a ? b : a; }
+};
+struct FoldMax {
+    template <class S> __device__ __forceinline__ S operator()(S a, S b) const { return b > a ? b : a; }
+};
+
+// c[l] = op(c[l], c[l + 32]), then + 16, ... + 1: lane 0 ends with the fold of all 64 lanes
+template <class S, class Op>
+__device__ __forceinline__ S wave_fold(S c, Op op) {
+    c = op(c, lane_plus<32>(c));
+    c = op(c, lane_plus<16>(c));
+    c = op(c, lane_plus<8>(c));
+    c = op(c, lane_plus<4>(c));
+    c = op(c, lane_plus<2>(c));
+    c = op(c, lane_plus<1>(c));
+    return c;
+}
+
+// Wave -> row (j, local plane) of the slab's nzl interior planes; false for waves past the last row (whole waves).
+__device__ __forceinline__ bool reduce_row(const Geom& g, int& j, int& p) {
+    const int row = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + ((int)threadIdx.x >> 6));
+    if (row >= g.N * g.nzl) return false;
+    p = row / g.N;
+    j = 1 + row - p * g.N;
+    return true;
+}
+// Start cell of the lane's m-th vector, clamped to the row's last vector for the load (i0c); the cells i0 + e <= N count.
+template <int W>
+__device__ __forceinline__ void reduce_vec(const Geom& g, int m, int& i0, int& i0c) {
+    i0 = 1 + W * (((int)threadIdx.x & 63) + 64 * m);
+    const int last = 1 + ((g.N - 1) / W) * W;
+    i0c = i0 < last ? i0 : last;
+}
+
+// rows: [value][plane 0..nzl-1][npad] doubles; a row's record sits at column j - 1
+__device__ __forceinline__ long rec_at(const Geom& g, int npad, int v, int p, int j) {
+    return ((long)v * g.nzl + p) * npad + (j - 1);
+}
+
+template <class T, int OP>
+__global__ void __launch_bounds__(256) reduce_rows_kernel(Geom g, const T* __restrict__ x, double* __restrict__ rows,
+                                                          int npad) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const long r = row0(g, j, g.G + p);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    double cs = 0.0;
+    T cm = OP == RED_MIN ? (T)INFINITY : (OP == RED_MAX ? (T)-INFINITY : T(0));
+    int cn = 0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type xv = ldv(x + r + i0c);
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const bool ok = i0 + e <= g.N;
+            const T v = xv[e];
+            if constexpr (OP == RED_SUM) cs = cs + (ok ? (double)v : 0.0);
+            if constexpr (OP == RED_SUM_SQ) cs = cs + (ok ? (double)v * (double)v : 0.0);
+            if constexpr (OP == RED_MIN) cm = ok ? sel_min(cm, v) : cm;
+            if constexpr (OP == RED_MAX) cm = ok ? sel_max(cm, v) : cm;
+            if constexpr (OP == RED_MAX_ABS) cm = ok ? sel_max(cm, fabs(v)) : cm;
+            if constexpr (OP == RED_COUNT_NONFINITE) cn += (ok && !isfinite(v)) ? 1 : 0;
+        }
+    }
+    double out;
+    if constexpr (OP == RED_SUM || OP == RED_SUM_SQ) out = wave_fold(cs, FoldSum());
+    else if constexpr (OP == RED_MIN) out = (double)wave_fold(cm, FoldMin());
+    else if constexpr (OP == RED_COUNT_NONFINITE) out = (double)wave_fold(cn, FoldSum());
+    else out = (double)wave_fold(cm, FoldMax());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = out;
+}
+
+template <class T>
+struct DiagArgs {
+    const T* u;
+    const T* v;
+    const T* w;
+    const T* dens;
+    T c_div, dt0;
+};
+
+// One pass over u, v, w, dens: the ten values of SPEC §10 "state diagnostics" per row. The j and k neighbours of the
+// divergence are 16-byte loads of the rows next door (lines the neighbouring waves fetch anyway: L2), u's i-1 / i+W
+// are two scalar loads of lines this wave has.
+template <class T>
+__global__ void __launch_bounds__(256) diag_rows_kernel(Geom g, DiagArgs<T> A, double* __restrict__ rows, int npad) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const long r = row0(g, j, g.G + p);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    double mass = 0.0, kin = 0.0, sp2 = 0.0;
+    T dmin = (T)INFINITY, dmax = (T)-INFINITY, dv = T(0), cx = T(0), cy = T(0), cz = T(0);
+    int bad = 0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V uc = ldv(A.u + q), vc = ldv(A.v + q), wc = ldv(A.w + q), dc = ldv(A.dens + q);
+        const T um = A.u[q - 1], up = A.u[q + W];
+        const V vm = ldv(A.v + q - g.px), vp = ldv(A.v + q + g.px);
+        const V wm = ldv(A.w + q - g.plane), wp = ldv(A.w + q + g.plane);
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const bool ok = i0 + e <= g.N;
+            const T left = (e == 0) ? um : uc[e - 1];
+            const T right = (e == W - 1) ? up : uc[e + 1];
+            const T d = fabs(A.c_div * (((right - left) + (vp[e] - vm[e])) + (wp[e] - wm[e])));
+            const double ud = (double)uc[e], vd = (double)vc[e], wd = (double)wc[e];
+            const double s2 = (ud * ud + vd * vd) + wd * wd;
+            mass = mass + (ok ? (double)dc[e] : 0.0);
+            kin = kin + (ok ? s2 : 0.0);
+            sp2 = ok ? sel_max(sp2, s2) : sp2;
+            dmin = ok ? sel_min(dmin, dc[e]) : dmin;
+            dmax = ok ? sel_max(dmax, dc[e]) : dmax;
+            dv = ok ? sel_max(dv, d) : dv;
+            cx = ok ? sel_max(cx, fabs(A.dt0 * uc[e])) : cx;
+            cy = ok ? sel_max(cy, fabs(A.dt0 * vc[e])) : cy;
+            cz = ok ? sel_max(cz, fabs(A.dt0 * wc[e])) : cz;
+            bad += (ok && !(isfinite(uc[e]) && isfinite(vc[e]) && isfinite(wc[e]) && isfinite(dc[e]))) ? 1 : 0;
+        }
+    }
+    double out[DIAG_NV];
+    out[0] = wave_fold(mass, FoldSum());
+    out[1] = wave_fold(kin, FoldSum());
+    out[2] = (double)wave_fold(bad, FoldSum());
+    out[3] = (double)wave_fold(dmin, FoldMin());
+    out[4] = (double)wave_fold(dmax, FoldMax());
+    out[5] = wave_fold(sp2, FoldMax());
+    out[6] = (double)wave_fold(dv, FoldMax());
+    out[7] = (double)wave_fold(cx, FoldMax());
+    out[8] = (double)wave_fold(cy, FoldMax());
+    out[9] = (double)wave_fold(cz, FoldMax());
+    if (((int)threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int v = 0; v < DIAG_NV; ++v) rows[rec_at(g, npad, v, p, j)] = out[v];
+    }
+}
+
+// Plane partial: the N row records of (value blockIdx.y, plane blockIdx.x), padded to npad (a power of two <= 2048)
+// with the fold's identity, folded by halving. Values below nsum are sums, the next nmin minima, the rest maxima.
+// planes: [plane][nv] doubles.
+static __global__ void __launch_bounds__(256) fold_rows_kernel(const double* __restrict__ rows, double* __restrict__ planes,
+                                                               int N, int npad, int nsum, int nmin) {
+    __shared__ double a[2048];
+    const int p = (int)blockIdx.x, v = (int)blockIdx.y, nv = (int)gridDim.y, t = (int)threadIdx.x;
+    const int kind = v < nsum ? 0 : (v < nsum + nmin ? 1 : 2);
+    const double ident = kind == 0 ? 0.0 : (kind == 1 ? (double)INFINITY : -(double)INFINITY);
+    const double* __restrict__ src = rows + ((long)v * gridDim.x + p) * npad;
+    for (int q = t; q < npad; q += 256) {
+        const double x = src[q < N ? q : N - 1];
+        a[q] = q < N ? x : ident;
+    }
+    __syncthreads();
+    for (int s = npad >> 1; s >= 1; s >>= 1) {
+        for (int q = t; q < s; q += 256) {
+            const double x = a[q], y = a[q + s];
+            a[q] = kind == 0 ? x + y : (kind == 1 ? (y < x ? y : x) : (y > x ? y : x));
+        }
+        __syncthreads();
+    }
+    if (t == 0) planes[(long)p * nv + v] = a[0];
+}
+
 }  // namespace sfk

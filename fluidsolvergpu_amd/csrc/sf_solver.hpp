@@ -7,7 +7,8 @@
 //     slab-boundary planes, then on the interior planes; the halo stream ships the boundary planes
 //     (device-to-device copy between slabs of the same process, RCCL send/recv grouped over xGMI
 //     between processes) while the interior sweep runs. No collective reduction exists anywhere in
-//     the step, only neighbour exchange.
+//     the step, only neighbour exchange; sf_reduce / sf_diagnostics_get (SPEC §10) are calls of
+//     their own that the step never makes.
 //   * fields are named slots holding device pointers, so SPEC's "swap" is a pointer swap.
 //   * there is NO CPU fallback: without a gfx950 device sf_create fails with SF_ERR_NO_DEVICE.
 #pragma once
@@ -50,6 +51,10 @@ class Solver final : public SolverBase {
         sfk::TracerRec<T>* tr_send[2] = {};
         sfk::TracerRec<T>* tr_recv[2] = {};
         int* tr_flag = nullptr;
+        // reductions (SPEC §10), allocated by the first sf_reduce / sf_diagnostics_get: row records
+        // [value][plane][rows_pad()] and plane records [plane][value]
+        double* red_rows = nullptr;
+        double* red_planes = nullptr;
     };
 
     // One launch of an operator as for_planes issues it: planes [kb, ke) of slab sl on stream st (sl.cs or sl.bs).
@@ -329,6 +334,8 @@ public:
             for (T*& f : sl.field) free_field(f);
             for (T*& f : sl.scratch) free_field(f);
             if (sl.d_flag) (void)hipFree(sl.d_flag);
+            if (sl.red_rows) (void)hipFree(sl.red_rows);
+            if (sl.red_planes) (void)hipFree(sl.red_planes);
             for (T*& f : sl.snap) free_field(f);
             if (sl.os) (void)hipStreamDestroy(sl.os);
             if (sl.snap_done) (void)hipEventDestroy(sl.snap_done);
@@ -341,6 +348,8 @@ public:
         }
         if (t0_) (void)hipEventDestroy(t0_);
         if (t1_) (void)hipEventDestroy(t1_);
+        if (red_host_) (void)hipHostFree(red_host_);
+        if (red_gather_) (void)hipFree(red_gather_);
         tracers_free();
         if (copy_src_) (void)hipFree(copy_src_);
         if (copy_dst_) (void)hipFree(copy_dst_);
@@ -1101,6 +1110,75 @@ public:
         }
     }
 
+    // ---- reductions and diagnostics (SPEC §10) -------------------------------------------------------------------
+    // Both calls: row records (one wave per row) and plane records (one workgroup per plane and value) on each slab's
+    // compute stream, the plane records to pinned host memory, the fold over global k on the host. They synchronise.
+    void reduce(int op, int field, double* out) override {
+        SF_REQUIRE(out != nullptr, "null result pointer");
+        SF_REQUIRE(op >= SF_RED_SUM && op <= SF_RED_COUNT_NONFINITE, "reduce: op out of range");
+        check_field(field);
+        join();
+        SF_HIP(hipSetDevice(device_));
+        records_alloc();
+        const int npad = rows_pad();
+        const unsigned nblocks = (unsigned)ceil_div((long)N_ * nzl_, 4L);
+        for (Slab& sl : slabs_) {
+            const T* x = ensure(sl, field);
+            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom, x, sl.red_rows, npad); };
+            switch (op) {
+                case SF_RED_SUM: go(sfk::reduce_rows_kernel<T, sfk::RED_SUM>); break;
+                case SF_RED_SUM_SQ: go(sfk::reduce_rows_kernel<T, sfk::RED_SUM_SQ>); break;
+                case SF_RED_MIN: go(sfk::reduce_rows_kernel<T, sfk::RED_MIN>); break;
+                case SF_RED_MAX: go(sfk::reduce_rows_kernel<T, sfk::RED_MAX>); break;
+                case SF_RED_MAX_ABS: go(sfk::reduce_rows_kernel<T, sfk::RED_MAX_ABS>); break;
+                default: go(sfk::reduce_rows_kernel<T, sfk::RED_COUNT_NONFINITE>); break;
+            }
+            tr_records("reduce_rows", sl, {{x, false, G_, G_ + nzl_}});
+        }
+        const bool sum = op == SF_RED_SUM || op == SF_RED_SUM_SQ || op == SF_RED_COUNT_NONFINITE;
+        const int nsum = sum ? 1 : 0, nmin = op == SF_RED_MIN ? 1 : 0;
+        double r[1];
+        finish_records(1, nsum, nmin, r);
+        *out = r[0];
+    }
+
+    void diagnostics(sf_diagnostics* out) override {
+        SF_REQUIRE(out != nullptr, "null result pointer");
+        join();
+        SF_HIP(hipSetDevice(device_));
+        records_alloc();
+        const int npad = rows_pad();
+        const unsigned nblocks = (unsigned)ceil_div((long)N_ * nzl_, 4L);
+        for (Slab& sl : slabs_) {
+            sfk::DiagArgs<T> A;
+            A.u = sl.field[SF_U];
+            A.v = sl.field[SF_V];
+            A.w = sl.field[SF_W];
+            A.dens = sl.field[SF_DENS];
+            A.c_div = T(-0.5) * (T(1) / (T)N_);
+            A.dt0 = dt_ * (T)N_;
+            hipLaunchKernelGGL(sfk::diag_rows_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom, A, sl.red_rows, npad);
+            tr_records("diag_rows", sl, {{A.u, false, G_, G_ + nzl_}, {A.v, false, G_, G_ + nzl_},
+                                         {A.w, false, G_ - 1, G_ + nzl_ + 1}, {A.dens, false, G_, G_ + nzl_}});
+        }
+        // record order of sfk::diag_rows_kernel: 0 mass, 1 kinetic sum, 2 nonfinite (sums), 3 dens_min (minimum),
+        // 4 dens_max, 5 max speed^2, 6 max_div, 7..9 cfl_x, y, z (maxima)
+        double r[sfk::DIAG_NV];
+        finish_records(sfk::DIAG_NV, 3, 1, r);
+        const double n3 = (double)N_ * (double)N_ * (double)N_;
+        out->mass = r[0];
+        out->kinetic = (0.5 * r[1]) / n3;
+        out->nonfinite = (long long)r[2];
+        out->dens_min = r[3];
+        out->dens_max = r[4];
+        out->max_speed = std::sqrt(r[5]);
+        out->max_div = r[6];
+        out->cfl_x = r[7];
+        out->cfl_y = r[8];
+        out->cfl_z = r[9];
+        out->cfl = std::max(std::max(r[7], r[8]), r[9]);
+    }
+
     int lin_solve_launches(int iters) const override {
         int n = 0;
         for (int it = 0; it < iters; ++n) it += sweeps_in_launch(it, iters, false, false);
@@ -1463,6 +1541,74 @@ private:
     void wr_range(const Slab& sl, int kb, int ke, int& lo, int& hi) const {
         lo = (sl.geom.wall_lo && kb == G_) ? kb - 1 : kb;
         hi = (sl.geom.wall_hi && ke == G_ + nzl_) ? ke + 1 : ke;
+    }
+
+    // ---- reductions (SPEC §10) ---------------------------------------------------------------------------------
+    // rows of a plane padded to the next power of two: the width of the plane partial's halving fold
+    int rows_pad() const {
+        int n = 1;
+        while (n < N_) n *= 2;
+        return n;
+    }
+    void records_alloc() {
+        SF_REQUIRE(rows_pad() <= 2048, "reductions take N <= 2048");
+        if (red_host_) return;
+        const size_t nv = sfk::DIAG_NV;
+        for (Slab& sl : slabs_) {
+            SF_HIP(hipMalloc(&sl.red_rows, nv * nzl_ * (size_t)rows_pad() * sizeof(double)));
+            SF_HIP(hipMalloc(&sl.red_planes, nv * nzl_ * sizeof(double)));
+        }
+        if (comm_) SF_HIP(hipMalloc(&red_gather_, nv * N_ * sizeof(double)));
+        SF_HIP(hipHostMalloc(&red_host_, nv * N_ * sizeof(double), hipHostMallocDefault));
+    }
+    // trace of a row kernel on the slab's compute stream: its field reads, and the row records it writes
+    void tr_records(const char* name, const Slab& sl, std::vector<Acc> acc) {
+        SF_HIP(hipGetLastError());
+        if (!trace_) return;
+        acc.push_back({sl.red_rows, true, 0, nplanes_});
+        tr_op(name, sl, sl.cs, acc);
+    }
+    // Row records -> plane records -> host -> (all ranks' records) -> the fold over global k. Values below nsum are
+    // sums, the next nmin minima, the rest maxima. Leaves every compute stream idle.
+    void finish_records(int nv, int nsum, int nmin, double* out) {
+        const int npad = rows_pad();
+        const size_t per_slab = (size_t)nzl_ * nv;
+        for (Slab& sl : slabs_) {
+            hipLaunchKernelGGL(sfk::fold_rows_kernel, dim3(nzl_, nv), dim3(256), 0, sl.cs, sl.red_rows, sl.red_planes, N_,
+                               npad, nsum, nmin);
+            SF_HIP(hipGetLastError());
+            tr_op("fold_rows", sl, sl.cs, {{sl.red_rows, false, 0, nplanes_}, {sl.red_planes, true, 0, nplanes_}});
+            SF_HIP(hipMemcpyAsync(red_host_ + sl.gid * per_slab, sl.red_planes, per_slab * sizeof(double),
+                                  hipMemcpyDeviceToHost, sl.cs));
+            tr_op("records_out", sl, sl.cs, {{sl.red_planes, false, 0, nplanes_}});
+        }
+        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        if (comm_) {
+            // the plane record is the unit that crosses ranks: every rank ends with all N of them and folds them itself
+            Slab& s0 = slabs_[0];
+            const size_t cnt = (size_t)L_ * per_slab, off = (size_t)rank_ * cnt;
+            SF_HIP(hipMemcpyAsync(red_gather_ + off, red_host_ + off, cnt * sizeof(double), hipMemcpyHostToDevice, s0.cs));
+            SF_NCCL(ncclGroupStart());
+            SF_NCCL(ncclAllGather(red_gather_ + off, red_gather_, cnt, ncclDouble, comm_, s0.cs));
+            SF_NCCL(ncclGroupEnd());
+            ++rccl_groups_;
+            tr_op("records_allgather", s0, s0.cs, {{red_gather_, false, 0, nplanes_}, {red_gather_, true, 0, nplanes_}});
+            SF_HIP(hipMemcpyAsync(red_host_, red_gather_, (size_t)nranks_ * cnt * sizeof(double), hipMemcpyDeviceToHost,
+                                  s0.cs));
+            SF_HIP(hipStreamSynchronize(s0.cs));
+        }
+        // a loopback context stands for one rank of several and has nobody to gather from: its own planes only
+        const bool own_only = nranks_ > 1 && !comm_;
+        const int k0 = own_only ? rank_ * L_ * nzl_ : 0, k1 = own_only ? k0 + L_ * nzl_ : N_;
+        for (int v = 0; v < nv; ++v) {
+            const bool sum = v < nsum, mn = !sum && v < nsum + nmin;
+            double t = sum ? 0.0 : (mn ? (double)INFINITY : -(double)INFINITY);
+            for (int k = k0; k < k1; ++k) {
+                const double x = red_host_[(size_t)k * nv + v];
+                t = sum ? t + x : (mn ? (x < t ? x : t) : (x > t ? x : t));
+            }
+            out[v] = sum ? t : t + 0.0;  // a zero minimum / maximum is +0
+        }
     }
 
     void join() {
@@ -2669,6 +2815,8 @@ private:
     void* copy_src_ = nullptr;
     void* copy_dst_ = nullptr;
     size_t copy_bytes_ = 0;
+    double* red_host_ = nullptr;    // pinned: the plane records of all N planes ([global k - 1][value])
+    double* red_gather_ = nullptr;  // device: the same, the all-gather's buffer (contexts with a communicator)
 };
 
 }  // namespace sfi

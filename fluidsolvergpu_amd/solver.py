@@ -24,6 +24,9 @@ FIELD_NAMES = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
 NCCL_ID_BYTES = 128
 SF_FLAG_LOOPBACK_HALO, SF_FLAG_RCCL_SELF = 1, 2
 SF_ADVECT_SEMI_LAGRANGIAN, SF_ADVECT_MACCORMACK = 0, 1
+SF_RED_SUM, SF_RED_SUM_SQ, SF_RED_MIN, SF_RED_MAX, SF_RED_MAX_ABS, SF_RED_COUNT_NONFINITE = range(6)
+REDUCE_OPS = {"sum": SF_RED_SUM, "sum_sq": SF_RED_SUM_SQ, "min": SF_RED_MIN, "max": SF_RED_MAX,
+              "max_abs": SF_RED_MAX_ABS, "count_nonfinite": SF_RED_COUNT_NONFINITE}
 TRANSPORTS = ("none", "copy", "rccl", "rccl-self", "loopback")
 
 # every symbol include/sfgpu.h declares (tests check that the library exports all of them)
@@ -37,6 +40,7 @@ ABI_SYMBOLS = (
     "sf_tracers_owned", "sf_tracers_get_owned", "sf_tracers_set_capacity",
     "sf_set_vorticity_confinement", "sf_set_buoyancy", "sf_vorticity_magnitude", "sf_add_forces",
     "sf_set_advection", "sf_advect_maccormack",
+    "sf_reduce", "sf_diagnostics_get",
 )
 
 
@@ -44,6 +48,12 @@ class SfParams(C.Structure):
     _fields_ = [("N", C.c_int), ("dtype", C.c_int), ("iters", C.c_int), ("dt", C.c_double),
                 ("diff", C.c_double), ("visc", C.c_double), ("device", C.c_int), ("nslabs_local", C.c_int),
                 ("rank", C.c_int), ("nranks", C.c_int), ("nccl_id", C.c_void_p), ("flags", C.c_int)]
+
+
+class SfDiagnostics(C.Structure):
+    """sf_diagnostics of include/sfgpu.h (docs/SPEC.md §10)."""
+    _fields_ = [(n, C.c_double) for n in ("mass", "dens_min", "dens_max", "kinetic", "max_speed", "max_div",
+                                          "cfl_x", "cfl_y", "cfl_z", "cfl")] + [("nonfinite", C.c_longlong)]
 
 
 _ctx = C.c_void_p
@@ -78,6 +88,8 @@ lib.sf_set_vorticity_confinement.argtypes = [_ctx, C.c_double]
 lib.sf_set_buoyancy.argtypes = [_ctx, C.c_double, C.c_double, C.c_int]
 lib.sf_set_advection.argtypes = [_ctx, C.c_int, C.c_int]
 lib.sf_advect_maccormack.argtypes = [_ctx] + [C.c_int] * 6
+lib.sf_reduce.argtypes = [_ctx, C.c_int, C.c_int, C.POINTER(C.c_double)]
+lib.sf_diagnostics_get.argtypes = [_ctx, C.POINTER(SfDiagnostics)]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -259,6 +271,22 @@ class FluidSolver:
 
     def advect_maccormack(self, b, d, d0, u, v, w):
         self._ck(lib.sf_advect_maccormack(self._h, int(b), _fid(d), _fid(d0), _fid(u), _fid(v), _fid(w)))
+
+    # -- reductions and diagnostics (docs/SPEC.md §10) ----------------------------------------
+    def reduce(self, op, field):
+        """One deterministic reduction over the interior cells of a field slot, as a float (a double's bits are those
+        of the SPEC for every decomposition). op: an SF_RED_* value or "sum", "sum_sq", "min", "max", "max_abs",
+        "count_nonfinite". Collective on several ranks; synchronises."""
+        out = C.c_double()
+        self._ck(lib.sf_reduce(self._h, REDUCE_OPS[op] if isinstance(op, str) else int(op), _fid(field), C.byref(out)))
+        return out.value
+
+    def diagnostics(self):
+        """State diagnostics of u, v, w, dens as a dict: mass, dens_min, dens_max, kinetic, max_speed, max_div, cfl_x,
+        cfl_y, cfl_z, cfl (floats) and nonfinite (int). Collective on several ranks; synchronises."""
+        d = SfDiagnostics()
+        self._ck(lib.sf_diagnostics_get(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in SfDiagnostics._fields_}
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

@@ -197,6 +197,48 @@ int sf_tracers_get_owned(sf_ctx* ctx, int* ids, void* xyz, void* dens_sample, vo
  * that are kept by the slab they leave and reported by sf_sync as SF_ERR_TRACER_OVERFLOW. */
 int sf_tracers_set_capacity(sf_ctx* ctx, int per_direction);
 
+/* Reductions and diagnostics of docs/SPEC.md §10: what the context can say about the state it holds without a
+ * download. Every result is a double whose bits are fixed by the SPEC — interior cells only, a double accumulator, a
+ * sum tree of row partials, plane partials and a total in global k order — so it is the same for every decomposition
+ * (nslabs_local, nranks), transport and SF_* switch, and equals the numpy reference tests/diagnostics_ref.py bit for
+ * bit. No float atomics anywhere.
+ *   - Collective: with nranks > 1 every rank calls them (like vel_step); the ranks all-gather their per-plane records
+ *     over the context's communicator and each folds all N of them, so every rank returns the same bits.
+ *     SF_FLAG_RCCL_SELF contexts send their records through the same collective on their one-rank communicator (it
+ *     counts as one group in sf_transport_info). SF_FLAG_LOOPBACK_HALO contexts have no communicator and reduce their
+ *     own planes only: meaningless, like their fields.
+ *   - Synchronising: both calls wait for the context's compute streams, like sf_timer_stop, and return the result to
+ *     the host. They issue no halo exchange (ghost planes are current after every operator and upload), write no
+ *     field, and change no later step by a bit. A step that never calls them issues exactly the launches it did.
+ *   - A bad op, a slot out of range or a NULL pointer is SF_ERR_INVALID; an SF_USER slot not yet used is allocated
+ *     (zeros) first, as elsewhere.
+ * sf_reduce(op, field): SUM and SUM_SQ add x and x*x (each converted to double first); MIN, MAX and MAX_ABS select
+ * among the FINITE cells only (NaN and +-inf are never taken) and return +inf, -inf and +0 when there is none — a zero
+ * result is always +0; COUNT_NONFINITE is the number of NaN / +-inf cells, as a double. A sum over a field that holds a
+ * NaN is a NaN (payload unspecified). */
+enum sf_reduce_op { SF_RED_SUM = 0, SF_RED_SUM_SQ = 1, SF_RED_MIN = 2, SF_RED_MAX = 3,
+                    SF_RED_MAX_ABS = 4, SF_RED_COUNT_NONFINITE = 5 };
+int sf_reduce(sf_ctx* ctx, int op, int field, double* out);
+
+/* One pass over SF_U, SF_V, SF_W, SF_DENS (docs/SPEC.md §10 "state diagnostics").
+ *   mass       sum of dens
+ *   dens_min, dens_max
+ *   kinetic    0.5 * sum((u^2 + v^2) + w^2) / N^3, squares and adds in double
+ *   max_speed  sqrt(max((u^2 + v^2) + w^2))
+ *   max_div    max |c_div*(((u[i+1]-u[i-1]) + (v[j+1]-v[j-1])) + (w[k+1]-w[k-1]))| with c_div = -0.5/N: SPEC §3's own
+ *              expression, evaluated in the context's precision, so it equals sf_reduce(SF_RED_MAX_ABS, div) of the div
+ *              slot sf_project leaves when run on the same velocity. The physical divergence (central differences
+ *              with h = 1/N) is max_div * N^2 in magnitude.
+ *   cfl_x, cfl_y, cfl_z   max |dt*N*u|, |dt*N*v|, |dt*N*w|: the product advect forms, in cells per step. cfl_z < 1 is
+ *              literally the condition of SPEC §4 under which a decomposed advect equals the undecomposed one (else
+ *              SF_ERR_HALO_EXCEEDED): test it BEFORE the step instead of learning of it afterwards.
+ *   cfl        the largest of the three
+ *   nonfinite  interior cells where any of the four fields is NaN or +-inf. Minima and maxima skip terms that are not
+ *              finite, so this count is how a blow-up shows. */
+typedef struct sf_diagnostics { double mass, dens_min, dens_max, kinetic, max_speed, max_div,
+                                cfl_x, cfl_y, cfl_z, cfl; long long nonfinite; } sf_diagnostics;
+int sf_diagnostics_get(sf_ctx* ctx, sf_diagnostics* out);
+
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);
 int sf_set_coefficients(sf_ctx* ctx, double dt, double diff, double visc);
@@ -234,7 +276,8 @@ int sf_schedule_info(const sf_ctx* ctx, int* trapezoid_pairs, int* measured);
 
 /* Which halo transport this context uses and how often it ran: *transport = 0 none (one slab), 1 device-local copy
  * kernel between logical slabs, 2 RCCL send/recv between processes, 3 RCCL send/recv to self (SF_FLAG_RCCL_SELF),
- * 4 loopback copies (SF_FLAG_LOOPBACK_HALO); *rccl_groups = ncclGroupEnd calls of the halo exchange issued so far. */
+ * 4 loopback copies (SF_FLAG_LOOPBACK_HALO); *rccl_groups = ncclGroupEnd calls issued so far: halo
+ * exchanges, tracer migrations and the record collectives of sf_reduce / sf_diagnostics_get (one each). */
 int sf_transport_info(const sf_ctx* ctx, int* transport, long* rccl_groups);
 
 #ifdef __cplusplus
