@@ -23,15 +23,16 @@ def sel_max(p, q):
     return np.where(q > p, q, p)
 
 
-def trace(vel, dt0, sign):
-    """One trace of every interior cell: ((i0, j0, k0), clamped). sign = -1: x = i - dt0*u (forward trace of §3),
-    +1: x = i + dt0*u (reverse trace). Indices as §3: (int)x, NaN -> 0, clamped into [0, N]."""
+def trace_positions(vel, dt0, sign):
+    """One trace of every interior cell: ((i0, j0, k0), clamped, (x, y, z)) with the clamped positions the weights are
+    taken from. sign = -1: x = i - dt0*u (forward trace of §3), +1: x = i + dt0*u (reverse trace). Indices as §3:
+    (int)x, NaN -> 0, clamped into [0, N]."""
     T = vel[0].dtype.type
     N = vel[0].shape[0] - 2
     lo, hi = T(0.5), T(N) + T(0.5)
     idx = np.arange(1, N + 1).astype(T)
     clamped = np.zeros((N, N, N), bool)
-    out = []
+    out, pos = [], []
     with np.errstate(invalid="ignore"):
         for ax, comp in enumerate(vel):  # ax 0: i (last array axis)
             shape = [1, 1, 1]
@@ -43,7 +44,36 @@ def trace(vel, dt0, sign):
             x = np.where(x > hi, hi, x)
             i0 = np.where(x == x, x, T(0)).astype(np.int64)
             out.append(np.clip(i0, 0, N))
-    return out, clamped
+            pos.append(x)
+    return out, clamped, pos
+
+
+def trace(vel, dt0, sign):
+    """((i0, j0, k0), clamped) of trace_positions."""
+    idx, clamped, _ = trace_positions(vel, dt0, sign)
+    return idx, clamped
+
+
+def next_cell_adjacent(idx):
+    """(N, N, N-1) bools [k-1, j-1, i-1], i = 1..N-1: the (i0, j0, k0) of cell i+1 is (i0+1, j0, k0) of cell i — the
+    condition under which a one-cell-per-lane kernel may take cell i's i0+1 samples from the lane of cell i+1."""
+    i0, j0, k0 = idx
+    return ((i0[:, :, 1:] == i0[:, :, :-1] + 1) & (j0[:, :, 1:] == j0[:, :, :-1]) & (k0[:, :, 1:] == k0[:, :, :-1]))
+
+
+def adjacency(u, v, w, dt, lanes=64):
+    """Fractions (forward, reverse) of the cells with a next lane in their wave (i < N, (i-1) % lanes != lanes-1) whose
+    next cell's trace is adjacent in the sense of next_cell_adjacent."""
+    T = u.dtype.type
+    N = u.shape[0] - 2
+    dt0 = T(dt) * T(N)
+    has_next = (np.arange(N - 1) % lanes) != lanes - 1
+    out = []
+    for sign in (-1, +1):
+        idx, _ = trace((u, v, w), dt0, sign)
+        adj = next_cell_adjacent(idx)[:, :, has_next]
+        out.append(float(adj.mean()) if adj.size else 0.0)
+    return tuple(out)
 
 
 def parts(b, d0, u, v, w, dt):
@@ -67,7 +97,8 @@ def parts(b, d0, u, v, w, dt):
                  sel_min(sel_min(a(1, 0, 0), a(1, 0, 1)), sel_min(a(1, 1, 0), a(1, 1, 1))))
     mx = sel_max(sel_max(sel_max(a(0, 0, 0), a(0, 0, 1)), sel_max(a(0, 1, 0), a(0, 1, 1))),
                  sel_max(sel_max(a(1, 0, 0), a(1, 0, 1)), sel_max(a(1, 1, 0), a(1, 1, 1))))
-    raw = hat[I] + T(0.5) * (d0[I] - bar[I])
+    with np.errstate(invalid="ignore"):
+        raw = hat[I] + T(0.5) * (d0[I] - bar[I])
     return {"hat": hat, "bar": bar[I], "mn": mn, "mx": mx, "raw": raw, "cf": cf, "cr": cr}
 
 

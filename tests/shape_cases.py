@@ -1,0 +1,133 @@
+"""The case table and the input builders shared by tests/test_shape_inputs_ref.py (CPU: the inputs discriminate) and
+tests/test_operator_shapes_gpu.py (GPU: forces, MacCormack, reductions at every shape and kernel form).
+
+Sizes: 1, 2, 3 (every interior cell is an edge and a corner), 5, 13, 31, 34 (less than a wave, ragged vectors), 64 (one
+full wave), 65 (one cell of a second wave; the plane fold pads to 128), 70, 130, 200 (two to four waves with a ragged
+last one). 260 and 324 (fp32) and 130, 200 (fp64) take the second trip of the SPEC §10 row partial (N > 64 W)."""
+import numpy as np
+
+DT = 0.1
+DTYPES = [np.float32, np.float64]
+SIZES = [1, 2, 3, 5, 13, 31, 34, 64, 65, 70, 130, 200]
+REDUCE_ONLY_F32 = [260, 324]
+SHAPES = [(N, dt) for N in SIZES for dt in DTYPES]
+REDUCE_SHAPES = SHAPES + [(N, np.float32) for N in REDUCE_ONLY_F32]
+DECOMPOSED = [(34, 2, "copy"), (34, 17, "rccl-self"), (65, 5, "copy"), (70, 2, "rccl-self"), (130, 2, "copy"),
+              (130, 5, "rccl-self"), (200, 4, "copy")]
+
+
+def second_trip(N, dtype):
+    """The SPEC §10 row partial takes m >= 1 (a lane adds more than one vector)."""
+    return N > 64 * (16 // np.dtype(dtype).itemsize)
+
+
+def dname(dtype):
+    return "f32" if np.dtype(dtype) == np.float32 else "f64"
+
+
+def smooth_flow(N):
+    """The velocity of test_parity_gpu.test_advect_smooth_flow: traces of up to 2.5 cells that vary slowly along a
+    row."""
+    k, j, i = np.meshgrid(*(np.arange(N + 2, dtype=np.float64),) * 3, indexing="ij")
+    amp = 2.5 / (DT * N)
+    u = amp * np.sin(2 * np.pi * i / N + 0.3) * np.cos(2 * np.pi * j / N)
+    v = amp * np.cos(2 * np.pi * (i + k) / N)
+    w = amp * np.sin(2 * np.pi * (j - i) / N + 1.1)
+    return u, v, w
+
+
+def mixed_flow(N, dtype, seed):
+    """(u, v, w): smooth_flow with, on one cell in sixteen, a normal perturbation of one cell (1 / (dt N) in velocity
+    units). Along a row most neighbouring cells land in neighbouring cells and a share does not; traces reach the walls
+    from a few cells away, and the roughness makes the limiter bite."""
+    rng = np.random.RandomState(seed)
+    out = []
+    for c in smooth_flow(N):
+        hit = rng.random_sample(c.shape) < 1.0 / 16.0
+        out.append((c + hit * rng.standard_normal(c.shape) / (DT * N)).astype(dtype))
+    return tuple(out)
+
+
+def mixed_flow_one_plane(N, dtype, seed):
+    """mixed_flow for decomposed contexts: w scaled so that |dt0 w| < 1 (one ghost plane, SPEC §4); u, v unchanged."""
+    u, v, w = mixed_flow(N, dtype, seed)
+    T = np.dtype(dtype).type
+    w = (w.astype(np.float64) * (0.95 / float(np.abs(T(DT) * T(N) * w).max()))).astype(dtype)
+    assert float(np.abs(T(DT) * T(N) * w).max()) < 1
+    return u, v, w
+
+
+def normal_field(N, dtype, seed, scale=1.0):
+    return (scale * np.random.RandomState(seed).standard_normal((N + 2,) * 3)).astype(dtype)
+
+
+def decades_field(N, dtype, seed):
+    """Magnitudes spread over five decades (test_diagnostics_gpu.test_every_op_and_the_struct_match_the_reference)."""
+    rng = np.random.RandomState(seed)
+    return (rng.standard_normal((N + 2,) * 3) * 10.0 ** rng.randint(-2, 3, (N + 2,) * 3)).astype(dtype)
+
+
+SPECIALS = (np.nan, np.inf, -np.inf, -0.0, 0.0)
+
+
+def special_values(x, rng, nonfinite=True):
+    """A copy of x with, planted in its interior: NaN, +inf, -inf, -0.0, +0.0 — each on the first and the last cell of a
+    row, on cells 64 and 65 where they exist, and on three random cells, every one in a row of its own choosing — and
+    runs of equal values (ties): runs of one repeated value, and a block of non-negative data in which four cells in ten
+    are zeros of either sign (-0 == +0 is the tie whose winner the SPEC §9 select forms fix). With nonfinite = False the
+    NaN and infinities are left out. The block is planted first and kept clear of NaN so that the cells around it stay
+    comparable."""
+    x = x.copy()
+    T = x.dtype.type
+    N = x.shape[0] - 2
+    side = min(N, 12)
+    o = [1 + rng.randint(0, N - side + 1) for _ in range(3)]
+    blk = tuple(slice(a, a + side) for a in o)
+    sub = np.abs(x[blk])
+    zero = rng.random_sample(sub.shape) < 0.4
+    sub[zero] = np.where(rng.random_sample(sub.shape) < 0.5, T(-0.0), T(0.0))[zero]
+    x[blk] = sub
+    inside = np.zeros(x.shape, bool)
+    inside[tuple(slice(max(a - 3, 0), a + side + 3) for a in o)] = True
+    columns = [1, N] + [c for c in (64, 65) if c < N]
+    def place(i, finite):
+        """A cell (k, j, i), i random if None; a non-finite value stays three cells clear of the block (N >= 20)."""
+        while True:
+            c = (1 + rng.randint(N), 1 + rng.randint(N), i if i is not None else 1 + rng.randint(N))
+            if finite or N < 20 or not inside[c]:
+                return c
+
+    for val in SPECIALS if nonfinite else SPECIALS[3:]:
+        for i in columns + [None] * 3:
+            x[place(i, np.isfinite(val))] = T(val)
+    for start in columns + [1 + rng.randint(N) for _ in range(3)]:  # runs of one repeated value
+        k, j = 1 + rng.randint(N), 1 + rng.randint(N)
+        a = max(1, min(start - 1, N - 3))
+        if not np.isfinite(x[k, j, a:min(a + 4, N + 1)]).all():
+            continue
+        x[k, j, a:min(a + 4, N + 1)] = x[k, j, a]
+    return x
+
+
+def forces_fields(N, dtype, seed):
+    """The 8 named fields for the SPEC §8 operators: standard-normal velocities, 0.2-normal everything else, and (N >= 8)
+    a block of zero velocity, inside which |omega| is uniform, its gradient zero and len = 0: there `tiny` alone keeps
+    1 / (len + tiny) finite."""
+    rng = np.random.RandomState(seed)
+    names = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
+    f = {n: (0.2 * rng.standard_normal((N + 2,) * 3)).astype(dtype) for n in names}
+    for n in ("u", "v", "w"):
+        f[n] = rng.standard_normal((N + 2,) * 3).astype(dtype)
+        if N >= 8:
+            f[n][2:9, 3:10, N - 7:N + 1] = 0  # up to the last cell of the rows it crosses
+    return f
+
+
+def zero_coefficient_inputs(N, dtype):
+    """forces_fields for the eps = 0 / beta = 0 cases of SPEC §8: -0 sources on every other interior cell of a row, NaN
+    in the velocity and in dens."""
+    f = forces_fields(N, dtype, 70 + N)
+    for n in ("u0", "v0", "w0"):
+        f[n][1:-1, 1:-1, 1:-1:2] = -0.0
+    f["v"][1, 1, 1] = f["u"][N, N, N] = f["dens"][1, N, 1] = np.nan
+    return f
