@@ -69,6 +69,35 @@ class Solver final : public SolverBase {
         bool is_split() const { return split != INT_MAX; }
     };
 
+    // The SF_* environment switches, each read once, here, when the context is created (defaults = production).
+    // SF_TRAP is read by the constructor (its default depends on the transport); SF_TRACE_SCHEDULE by trace_open().
+    struct Switches {
+        int nt = env_int("SF_NT", 2);           // non-temporal stores: 0 never, 1 always, 2 beyond the Infinity Cache
+        int ishell = env_int("SF_ISHELL", 1);   // 0 every sweep reads and writes the i-shell, 1 implicit between
+                                                // passes and left unwritten where nothing reads it, 2 implicit only
+        bool fuse2 = env_int("SF_FUSE2", 1) != 0;  // 0 single sweeps, 1 fused sweeps
+        int ghost = env_int("SF_GHOST", 4);     // most ghost planes per side of a slab
+        int advect_row = env_int("SF_ADVECT_ROW", 1);  // 0 gather form always, 1 one cell per lane for the three
+                                                       // velocity components, 2 / 3 always
+        bool zero_skip = env_int("SF_ZERO_SKIP", 1) != 0;  // project's first pair loads no (zero) pressure
+        bool split = env_int("SF_SPLIT", 1) != 0;  // boundary / interior launches of a slab on two streams
+        int ovl = env_int("SF_OVL", 1);         // overlapped row mapping of the pair kernel (launch_fused2)
+        int split_fields = env_int("SF_SPLIT_FIELDS", 1);  // 0 never, 1 when one field fits the Infinity Cache, 2 always
+        bool fuse_src = env_int("SF_FUSE_SRC", 1) != 0;  // fold add_source (bound sources) into diffuse's first pass
+        bool graph = env_int("SF_GRAPH", 0) != 0;
+        int halo_stream = env_int("SF_HALO_STREAM", 0);
+        bool autotune = env_int("SF_AUTOTUNE", 1) != 0;
+        int march = env_int("SF_MARCH", 1);     // 0: the register-blocked pair kernel everywhere
+        int march_minp = env_int("SF_MARCH_MINP", 12);
+        // Smallest launch the marching kernel takes: 2.5 M cells (~136^3; 6 M until round 3) — with 16 thin waves per
+        // workgroup it overtakes the pair kernel there (us per sweep of a 20-sweep solve, pair / marching: 128^3 4.4 /
+        // 5.8, 144^3 9.0 / 6.0, 160^3 10.6 / 6.3, 176^3 13.4 / 7.1), slab interiors included (one rank's share of the
+        // full step: 256^3 over 4 ranks 1.335 -> 1.147 ms, 384^3 over 8 ranks 1.806 -> 1.492).
+        long march_min_cells = (long)env_int("SF_MARCH_MINCELLS_K", 2500) * 1000L;
+        int sk_s = env_int("SF_SK_S", 4);       // most sweeps per marching pass
+        bool sk_first = env_int("SF_SK_FIRST", 1) != 0;  // first pass of a solve through the marching kernel
+    };
+
 public:
     explicit Solver(const sf_params& p) : N_(p.N), K_(p.iters), device_(p.device) {
         SF_REQUIRE(p.N >= 1, "N must be >= 1");
@@ -107,24 +136,15 @@ public:
         // two ghost planes per side let sweep pairs be fused across slab boundaries (one exchange per pair); grids
         // the fused kernel does not take (rows wider than 512 vectors, N not a multiple of W) keep one ghost plane
         // and exchange one plane per sweep
-        const bool fusable = env_int("SF_FUSE2", 1) != 0 && N_ % W == 0 && N_ / W <= fuse_maxvec_;
-        G_ = (P_ > 1 && nzl_ >= 2 && fusable && env_int("SF_GHOST", 4) >= 2) ? 2 : 1;
+        const bool fusable = sw_.fuse2 && N_ % W == 0 && N_ / W <= fuse_maxvec_;
+        G_ = (P_ > 1 && nzl_ >= 2 && fusable && sw_.ghost >= 2) ? 2 : 1;
         // three / four ghost planes where the marching kernel will run three / four sweeps per pass on the slab
-        // interiors (one exchange per pass): the interior launch [2G, nzl) must be long and large enough for it
-        {
-            const long min_cells = (long)env_int("SF_MARCH_MINCELLS_K", 2500) * 1000L;  // (march_min_cells_, below)
-            const int ghost_max = env_int("SF_GHOST", 4), smax = env_int("SF_SK_S", 4);
-            for (int gs = 3; gs <= 4; ++gs) {  // S = gs sweeps per exchange need gs ghost planes
-                const int interior = nzl_ - 2 * gs;
-                // (SF_ISHELL=0 — every sweep reads and writes the i-shell in memory — rules the marching kernel out in
-                // sweeps_in_launch(); the deeper ghost zone is kept all the same: the solve then runs pair launches of
-                // boundary depth pair_depth() on it, the schedule that K < 7 and remainders take by default)
-                if (G_ == gs - 1 && ghost_max >= gs && env_int("SF_MARCH", 1) != 0 &&
-                    smax >= gs && env_int("SF_SPLIT", 1) != 0 && interior >= env_int("SF_MARCH_MINP", 12) &&
-                    (long)N_ * N_ * interior >= min_cells)
-                    G_ = gs;
-            }
-        }
+        // interiors (one exchange per pass): the interior launch [2G, nzl) must be long and large enough for it.
+        // (SF_ISHELL=0 — every sweep reads and writes the i-shell in memory — rules the marching kernel out in
+        // march_takes(), hence march_fits() here: the deeper ghost zone is kept all the same and the solve then runs
+        // pair launches of boundary depth pair_depth() on it, the schedule that K < 7 and remainders take by default)
+        for (int gs = 3; gs <= 4; ++gs)  // S = gs sweeps per exchange need gs ghost planes
+            if (G_ == gs - 1 && sw_.ghost >= gs && sw_.sk_s >= gs && sw_.split && march_fits(nzl_ - 2 * gs)) G_ = gs;
         nplanes_ = nzl_ + 2 * G_;
         field_elems_ = plane_ * nplanes_ + 256;  // slack so whole-vector accesses never leave the buffer
         field_elems_ = (field_elems_ + W - 1) / W * W;
@@ -166,7 +186,7 @@ public:
                 // neighbours' buffers and stay on their own stream (SF_HALO_STREAM=2 shares there too: used by the
                 // parity tests to run the shared-stream ordering against the oracle). (A high-priority halo stream
                 // was measured in round 1: with logical slabs on one GPU the copy kernel pre-empts the sweeps, 2x slower.)
-                const int hmode = env_int("SF_HALO_STREAM", 0);  // 0 as described, 1 always separate, 2 always shared
+                const int hmode = sw_.halo_stream;  // 0 as described, 1 always separate, 2 always shared
                 if ((L_ == 1 && nranks_ > 1 && hmode == 0) || hmode == 2)
                     sl.hs = sl.bs;
                 else
@@ -194,16 +214,9 @@ public:
             SF_NCCL(ncclGetUniqueId(&id));
             SF_NCCL(ncclCommInitRank(&comm_, 1, id, 0));
         }
-        nt_mode_ = env_int("SF_NT", 2);  // non-temporal stores: 0 never, 1 always, 2 beyond the Infinity Cache
-        ishell_skip_ = env_int("SF_ISHELL", 1) != 0;
-        dead_ishell_opt_ = env_int("SF_ISHELL", 1) == 1;
-        fuse2_ = env_int("SF_FUSE2", 1) != 0;  // 0 single sweeps, 1 fused sweeps (default)
-        advect_row_ = env_int("SF_ADVECT_ROW", 1);
-        zero_skip_ = env_int("SF_ZERO_SKIP", 1) != 0;
-        split_enabled_ = env_int("SF_SPLIT", 1) != 0;
-        ovl_mode_ = env_int("SF_OVL", 1);
-        split_fields_ = env_int("SF_SPLIT_FIELDS", 1);  // 0 never, 1 when one field fits the Infinity Cache, 2 always
-        fuse_src_ = env_int("SF_FUSE_SRC", 1) != 0;  // fold add_source (bound sources) into diffuse's first pass
+        ishell_skip_ = sw_.ishell != 0;
+        dead_ishell_opt_ = sw_.ishell == 1;
+        split_fields_ = sw_.split_fields;
         // Trapezoid blocks shorten the interior chain (no cross-stream wait) but lengthen the boundary chain
         // B(j) -> halo(j) -> B(j+1), because B grows by two planes per side and pair. With halos that are copies on
         // this GPU the interior chain is the critical one (default 5 pairs per block); with RCCL messages over xGMI
@@ -211,19 +224,10 @@ public:
         // keeps B at its minimum size (0 = off) unless the measurement at the end of this constructor
         // (tune_schedule) says otherwise. SF_TRAP overrides and switches the measurement off.
         trap_m_ = env_int("SF_TRAP", (nranks_ > 1 || rccl_self_) ? 0 : 5);  // pairs per trapezoid block of a decomposed lin_solve (<= 1: off)
-        graphs_ = env_int("SF_GRAPH", 0) != 0 && P_ == 1;
-        march_k_ = env_int("SF_MARCH", 1);  // 0: the register-blocked pair kernel everywhere
-        march_min_planes_ = env_int("SF_MARCH_MINP", 12);
-        // Smallest launch the marching kernel takes: 2.5 M cells (~136^3; 6 M until round 3) — with 16 thin waves per
-        // workgroup it overtakes the pair kernel there (us per sweep of a 20-sweep solve, pair / marching: 128^3 4.4 /
-        // 5.8, 144^3 9.0 / 6.0, 160^3 10.6 / 6.3, 176^3 13.4 / 7.1), slab interiors included (one rank's share of the
-        // full step: 256^3 over 4 ranks 1.335 -> 1.147 ms, 384^3 over 8 ranks 1.806 -> 1.492).
-        march_min_cells_ = (long)env_int("SF_MARCH_MINCELLS_K", 2500) * 1000L;
-        sk2_min_cells_ = std::max(march_min_cells_ == 0 ? 0L : 60000000L, march_min_cells_);  // ~390^3
-        sk_s_ = env_int("SF_SK_S", 4);
-        sk_first_ = env_int("SF_SK_FIRST", 1) != 0;  // first pass of a solve through the marching kernel
+        graphs_ = sw_.graph && P_ == 1;
+        sk2_min_cells_ = std::max(sw_.march_min_cells == 0 ? 0L : 60000000L, sw_.march_min_cells);  // ~390^3
         SF_HIP(hipDeviceSynchronize());
-        if ((nranks_ > 1 || rccl_self_) && std::getenv("SF_TRAP") == nullptr && env_int("SF_AUTOTUNE", 1)) tune_schedule();
+        if ((nranks_ > 1 || rccl_self_) && std::getenv("SF_TRAP") == nullptr && sw_.autotune) tune_schedule();
         trace_open();
     }
 
@@ -1180,9 +1184,7 @@ public:
     }
 
     int lin_solve_launches(int iters) const override {
-        int n = 0;
-        for (int it = 0; it < iters; ++n) it += sweeps_in_launch(it, iters, false, false);
-        return n;
+        return (int)plan_solve(iters, false, false, false).size();
     }
 
     void schedule_info(int* trap, int* measured) const override {
@@ -1655,8 +1657,8 @@ private:
             SF_HIP(hipGetLastError());
             return;
         }
-        const int extra = (nzl_ > 2 * (depth + grow) && split_enabled_ && !interior_reads_ghosts) ? grow : 0;
-        const bool two_streams = nzl_ > 2 * depth && split_enabled_ && !interior_reads_ghosts;
+        const int extra = (nzl_ > 2 * (depth + grow) && sw_.split && !interior_reads_ghosts) ? grow : 0;
+        const bool two_streams = nzl_ > 2 * depth && sw_.split && !interior_reads_ghosts;
         if (!two_streams) join();
         depth += extra;
         for (Slab& sl : slabs_) {
@@ -1937,18 +1939,18 @@ private:
             launch_rb<NF, NT, 1, 1>(L, A, first, last);
     }
 
-    template <int NF>
-    void launch_jacobi(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool first, bool last) {
-        if (nt_stores(NF))
-            launch_rb_shape<NF, true>(L, A, first, last);
-        else
-            launch_rb_shape<NF, false>(L, A, first, last);
-    }
-
     // SF_NT: non-temporal stores never (0), always (1), or (2) once x, x0 and x' of the nf fields of a launch no longer
     // fit the 256 MiB Infinity Cache
     bool nt_stores(int nf) const {
-        return nt_mode_ == 1 || (nt_mode_ == 2 && (size_t)field_elems_ * sizeof(T) * 3 * nf > ((size_t)384 << 20));
+        return sw_.nt == 1 || (sw_.nt == 2 && (size_t)field_elems_ * sizeof(T) * 3 * nf > ((size_t)384 << 20));
+    }
+    // f(std::bool_constant<nt_stores(nf)>): the store form of a launch of nf fields as a compile-time constant
+    template <class F>
+    void with_nt(int nf, F f) const {
+        if (nt_stores(nf))
+            f(std::true_type{});
+        else
+            f(std::false_type{});
     }
     // bytes of x, x0 and x' of one field of a solve, and whether a working set fits the 256 MiB Infinity Cache
     double solve_bytes() const { return 3.0 * (double)(N_ + 2) * (N_ + 2) * nplanes_ * sizeof(T); }
@@ -1958,7 +1960,7 @@ private:
     // vector width and the grid is not decomposed (a second ghost plane would be needed).
     // (measured against single sweeps: +20 % at 512^3, +35 % at 256^3, +11 % at 1024^3 fp32, +15 % at 512^3 fp64)
     bool can_fuse2() const {
-        return fuse2_ && (P_ == 1 || G_ >= 2) && N_ % W == 0 && N_ / W <= fuse_maxvec_;
+        return sw_.fuse2 && (P_ == 1 || G_ >= 2) && N_ % W == 0 && N_ / W <= fuse_maxvec_;
     }
 
     // field f of A as the arguments of a one-field launch
@@ -2002,7 +2004,7 @@ private:
         // ... and rows wider than two waves, where it also beats one row strip per workgroup (1024^3 fp32: 2026 vs
         // 1986 us/sweep; the single-sweep kernel: 2207)
         // (a row strip must fit the 256 threads of a workgroup: beyond that only the overlapped mapping exists)
-        const bool ovl = ovl_mode_ == 2 || (ovl_mode_ == 1 && ((nvec % 64 != 0 && 64 % nvec != 0) || nvec > 128)) ||
+        const bool ovl = sw_.ovl == 2 || (sw_.ovl == 1 && ((nvec % 64 != 0 && 64 % nvec != 0) || nvec > 128)) ||
                          nvec > 256;
         if (ovl) {
             const int items = ceil_div(N_, RJ) * nvec;
@@ -2046,22 +2048,24 @@ private:
             launch_k(L, sfk::jacobi2_kernel<T, NF, NT, RJ, RK, false, false, false, SRC>, nb, 256u, A, m);
     }
 
-    // k-marching S-sweep kernel (sfk::jacobi_sk_kernel): the plain passes of a solve (iterate already swept once, so its
-    // i-shell is recomputed in registers) on plane ranges long enough to march, never in a split boundary launch
-    // (split) or over a zero iterate (x_zero). SF_MARCH=0 switches it off.
-    bool can_march_k(int nplanes, bool first, bool x_zero, bool split) const {
-        // small grids do not fill the chip with workgroups of 32-48 rows (128^3: 9.0 vs 4.3 us/sweep)
-        return march_k_ != 0 && !first && ishell_skip_ && !split && nplanes >= march_min_planes_ && !x_zero &&
-               (long)N_ * N_ * nplanes >= march_min_cells_;
+    // Does the marching kernel (sfk::jacobi_sk_kernel; SF_MARCH=0 switches it off) fit a launch of `planes` planes of
+    // this grid? The one place the size thresholds are compared. Small grids do not fill the chip with workgroups of
+    // 32-48 rows (128^3: 9.0 vs 4.3 us/sweep; the crossover: Switches::march_min_cells).
+    bool march_fits(int planes) const {
+        return sw_.march != 0 && planes >= sw_.march_minp && (long)N_ * N_ * planes >= sw_.march_min_cells;
     }
-
-    // S fused sweeps with LDS halo exchange (sfk::jacobi_sk_kernel). Same eligibility as the two-sweep marching kernel;
-    // three sweeps only on an undecomposed grid (a slab boundary would need three ghost planes).
-    // (two-sweep launches — slab interiors with two ghost planes, remainders — only pay on large grids: at 256^3 the
-    // register-blocked pair kernel takes 49 us, the marching kernel 67; at 512^3 437 against 365)
-    bool can_sk(int nplanes, bool first, bool x_zero, bool split, int sweeps = 3) const {
-        return can_march_k(nplanes, first, x_zero, split) && (sweeps >= 3 || (long)N_ * N_ * nplanes >= sk2_min_cells_);
+    // ... and may it run there? It leaves the i-shell implicit between passes: with SF_ISHELL=0 — every pass reads it
+    // from memory — it must not run at all, on one slab or many. (Round 2 checked that for P_ == 1 only, and a
+    // decomposed solve mixed marching passes with pair passes that read a stale i-shell.)
+    bool march_takes(int planes) const { return ishell_skip_ && march_fits(planes); }
+    // S sweeps per pass on a decomposed grid need S ghost planes, the two-stream schedule, and an interior launch
+    // [max(S, G) + extra, ...) (for_planes; extra: the growth of the boundary launch) the marching kernel takes (the
+    // boundary launch always goes through it: there is no other kernel of that depth)
+    bool march_takes_slab(int S, int extra) const {
+        return G_ >= S && sw_.split && march_takes(nzl_ - 2 * (std::max(S, G_) + extra));
     }
+    // an S-sweep marching pass of a solve on this context
+    bool march_pass(int S, int extra = 0) const { return P_ == 1 ? march_takes(nzl_) : march_takes_slab(S, extra); }
 
     int sk_chunks(int ncb, int np, int S) const {
         const int max_chunks = std::max(1, np / 8);
@@ -2126,42 +2130,48 @@ private:
         }
     }
 
-    // First pass of a solve through the marching kernel (four sweeps; sfk::SkFirst): mode 1 caller data, 2 folded
-    // add_source, 3 zero iterate. One launch per field, or one for all NF with mode 2 in a batched solve (batch).
+    // What the first pass of a solve takes as its iterate; the values are the FIRST argument of sfk::jacobi_sk_kernel
+    // (sfk::SkFirst). NONE: not a first pass — the iterate has been swept before and its i-shell is implicit.
+    enum class First : int { NONE = 0, CALLER = 1, SOURCE = 2, ZERO = 3 };  // caller data / folded add_source / zero
+
+    // One pass of a solve as plan_solve lays it out: `sweeps` fused sweeps per launch, then one exchange.
+    struct Pass {
+        int sweeps;        // 1 .. 4
+        int depth, extra;  // for_planes: planes per side of the boundary launch (before max(.., G)), trapezoid growth
+        First first;
+        bool last;         // the pass that writes the i-shell
+        bool batch;        // its marching launches take all fields of the solve as one grid (batch_march)
+        const char* name;  // trace op
+    };
+
+    // First pass of a solve through the marching kernel (four sweeps). One launch per field, or one for all NF of a
+    // folded-source pass in a batched solve (batch).
     template <int NF>
-    void launch_sk_first(const Launch& L, const sfk::JacobiArgs<T, NF>& A, int mode, bool batch) {
-        const bool nt = nt_stores(NF);
+    void launch_sk_first(const Launch& L, const sfk::JacobiArgs<T, NF>& A, First first, bool batch) {
         // (tiles: SK4F_* for the passes that read the caller's i-shell, SK4_* for the zero-iterate pass, see above)
-        constexpr int TJ0 = SK4F_TJ, NWF = SK4F_NW, TJ3 = SK4_TJ, NW4 = SK4_NW;
-        if constexpr (NF > 1) {
-            if (mode == 2 && batch) {
-                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 2, NF>(L, A, false);
-                else launch_sk_cfg<false, 4, TJ0, NWF, 2, NF>(L, A, false);
-                return;
+        with_nt(NF, [&](auto nt) {
+            constexpr bool NT = decltype(nt)::value;
+            if constexpr (NF > 1) {
+                if (first == First::SOURCE && batch) {
+                    launch_sk_cfg<NT, 4, SK4F_TJ, SK4F_NW, int(First::SOURCE), NF>(L, A, false);
+                    return;
+                }
             }
-        }
-        for (int f = 0; f < NF; ++f) {
-            const sfk::JacobiArgs<T, 1> B = field_args(A, f);
-            if (mode == 1) {
-                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 1>(L, B, false);
-                else launch_sk_cfg<false, 4, TJ0, NWF, 1>(L, B, false);
-            } else if (mode == 2) {
-                if (nt) launch_sk_cfg<true, 4, TJ0, NWF, 2>(L, B, false);
-                else launch_sk_cfg<false, 4, TJ0, NWF, 2>(L, B, false);
-            } else {
-                if (nt) launch_sk_cfg<true, 4, TJ3, NW4, 3>(L, B, false);
-                else launch_sk_cfg<false, 4, TJ3, NW4, 3>(L, B, false);
+            for (int f = 0; f < NF; ++f) {
+                const sfk::JacobiArgs<T, 1> B = field_args(A, f);
+                if (first == First::CALLER)
+                    launch_sk_cfg<NT, 4, SK4F_TJ, SK4F_NW, int(First::CALLER)>(L, B, false);
+                else if (first == First::SOURCE)
+                    launch_sk_cfg<NT, 4, SK4F_TJ, SK4F_NW, int(First::SOURCE)>(L, B, false);
+                else
+                    launch_sk_cfg<NT, 4, SK4_TJ, SK4_NW, int(First::ZERO)>(L, B, false);
             }
-        }
+        });
     }
-    // May the FIRST pass of a K-sweep solve go through the marching kernel? Undecomposed grid, four-sweep launches
-    // enabled, a grid the kernel takes, and sweeps left over afterwards (no i-shell-writing variant of a first pass).
-    bool sk_first_ok(int K) const {
-        if (!(sk_first_ && march_k_ != 0 && sk_s_ >= 4 && can_fuse2() && ishell_skip_ && K >= 7)) return false;
-        if (P_ == 1) return nzl_ >= march_min_planes_ && (long)N_ * N_ * nzl_ >= march_min_cells_;
-        const int interior = nzl_ - 2 * std::max(4, G_);  // slabs: four ghost planes and an interior launch the kernel takes
-        return G_ >= 4 && split_enabled_ && interior >= march_min_planes_ && (long)N_ * N_ * interior >= march_min_cells_;
-    }
+    // May the FIRST pass of a K-sweep solve go through the marching kernel? Four-sweep launches enabled, a grid the
+    // kernel takes (slabs: four ghost planes and an interior launch it takes), and sweeps left over afterwards (no
+    // i-shell-writing variant of a first pass).
+    bool sk_first_ok(int K) const { return sw_.sk_first && sw_.sk_s >= 4 && can_fuse2() && K >= 7 && march_pass(4); }
 
     // The NF fields of a batched solve (u, v, w of a diffusion) as ONE marching grid on an undecomposed slab: NF times
     // the column blocks let the launch fill the chip with NF times fewer, longer chunks — a chunk pays 2(S-1) warm-up
@@ -2177,9 +2187,10 @@ private:
     // 49.6 / 49.8 (chunks are long anyway); fp64: 144^3 (76 MB) 1.579 / 1.409; 176^3 (137 MB) 2.048 / 2.162; 192^3
     // (178 MB) 2.662 / 2.646; 256^3 (403 MB) 4.60 / 4.32; 320^3 7.89 / 7.75. Hence two windows in bytes, whatever the
     // precision: 75..125 MB and 170 MB..2 GB.
+    // K: the sweeps still to run; continued: a first pass (folded source) has run already.
     bool batch_march(int K, bool continued) const {
-        if (!(P_ == 1 && split_fields_ != 2 && K % 4 == 0 && K >= 4 && sk_first_ && march_k_ != 0 && sk_s_ >= 4 &&
-              can_fuse2() && ishell_skip_ && nzl_ >= march_min_planes_ && (long)N_ * N_ * nzl_ >= march_min_cells_))
+        if (!(P_ == 1 && split_fields_ != 2 && K % 4 == 0 && K >= 4 && sw_.sk_first && sw_.sk_s >= 4 && can_fuse2() &&
+              march_takes(nzl_)))
             return false;
         const double mb = solve_bytes() / 1048576.0;
         if (split_fields_ == 1 && !((mb >= 75.0 && mb <= 125.0) || (mb >= 170.0 && mb <= 2048.0))) return false;
@@ -2188,178 +2199,189 @@ private:
     // Solve the NF fields of a solve one after the other? x, x0 and x' of ONE field fit the 256 MiB Infinity Cache where
     // those of NF fields together do not: every pair after the first then stays out of HBM (256^3 fp32: 3 x 50.8 us
     // against 175.9 us per pair of three fields). Independent fields: same results.
-    bool solve_apart(int K, bool continued) const {
-        return split_fields_ == 2 || (split_fields_ == 1 && fits_ic(solve_bytes()) && !batch_march(K, continued));
+    bool solve_apart(int K) const {
+        return split_fields_ == 2 || (split_fields_ == 1 && fits_ic(solve_bytes()) && !batch_march(K, false));
     }
 
-    // batch: a batched solve (batch_march) whose passes go as one grid for all NF fields
+    // S sweeps of the marching kernel on an iterate swept before. batch: as in Pass.
     template <int NF, int S>
     void launch_sk(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool last, bool batch) {
-        SF_REQUIRE(ishell_skip_ && march_k_ != 0, "internal: marching launch while SF_ISHELL=0 / SF_MARCH=0");
-        const bool nt = nt_stores(NF);
-        if constexpr (NF > 1 && S == 4) {
-            if (!last && batch) {
-                if (nt) launch_sk_cfg<true, S, SK4_TJ, SK4_NW, 0, NF>(L, A, false);
-                else launch_sk_cfg<false, S, SK4_TJ, SK4_NW, 0, NF>(L, A, false);
-                return;
+        SF_REQUIRE(ishell_skip_ && sw_.march != 0, "internal: marching launch while SF_ISHELL=0 / SF_MARCH=0");
+        // Tile: SK4_* at S = 4 (above); six rows x eight waves at S <= 3. Four levels hold 17 planes of rows per
+        // lane (x 3, x0 5, three intermediate levels x 3). (A spill in the wall workgroups alone doubles a launch
+        // at 256^3, where every workgroup runs at once and the slowest one is the launch.)
+        constexpr int TJ0 = S == 4 ? SK4_TJ : 6, NW0 = S == 4 ? SK4_NW : 8;
+        with_nt(NF, [&](auto nt) {
+            constexpr bool NT = decltype(nt)::value;
+            if constexpr (NF > 1 && S == 4) {
+                if (!last && batch) {
+                    launch_sk_cfg<NT, S, TJ0, NW0, 0, NF>(L, A, false);
+                    return;
+                }
             }
-        }
-        for (int f = 0; f < NF; ++f) {  // one launch per field (fields are independent)
-            const sfk::JacobiArgs<T, 1> B = field_args(A, f);
-            // Tile: SK4_* at S = 4 (above); six rows x eight waves at S <= 3. Four levels hold 17 planes of rows per
-            // lane (x 3, x0 5, three intermediate levels x 3). (A spill in the wall workgroups alone doubles a launch
-            // at 256^3, where every workgroup runs at once and the slowest one is the launch.)
-            constexpr int TJ0 = S == 4 ? SK4_TJ : 6, NW0 = S == 4 ? SK4_NW : 8;
-            if (nt)
-                launch_sk_cfg<true, S, TJ0, NW0>(L, B, last);
+            for (int f = 0; f < NF; ++f)  // one launch per field (fields are independent)
+                launch_sk_cfg<NT, S, TJ0, NW0>(L, field_args(A, f), last);
+        });
+    }
+
+    // The launch of pass p of a solve on the plane range L: the whole choice of kernel form.
+    template <int NF>
+    void launch_pass(const Launch& L, const sfk::JacobiArgs<T, NF>& A, const Pass& p) {
+        const bool first = p.first != First::NONE;
+        const int np = L.ke - L.kb;
+        if (p.sweeps >= 3) {  // the marching kernel (pass_sweeps has asked march_pass)
+            if (first)
+                launch_sk_first<NF>(L, A, p.first, p.batch);
+            else if (p.sweeps == 4)
+                launch_sk<NF, 4>(L, A, p.last, p.batch);
             else
-                launch_sk_cfg<false, S, TJ0, NW0>(L, B, last);
+                launch_sk<NF, 3>(L, A, p.last, p.batch);
+        } else if (p.sweeps == 2 && !first && !L.is_split() && march_takes(np) && (long)N_ * N_ * np >= sk2_min_cells_) {
+            // two-sweep launches — slab interiors with two ghost planes, remainders — go through the marching kernel
+            // on large grids only: at 256^3 the register-blocked pair kernel takes 49 us, the marching kernel 67; at
+            // 512^3 437 against 365. Never a first pass (iterate in memory, zero or a source) or a split boundary launch.
+            launch_sk<NF, 2>(L, A, p.last, false);
+        } else if (p.sweeps == 2) {
+            // 2x2 output vectors per thread: measured best of 1x1, 2x1, 1x2, 2x2, 4x2 (4x2 spills)
+            with_nt(NF, [&](auto nt) {
+                if (p.first == First::SOURCE)
+                    launch_fused2<NF, decltype(nt)::value, 2, 2, true>(L, A, true, p.last, false);
+                else
+                    launch_fused2<NF, decltype(nt)::value, 2, 2>(L, A, first, p.last, p.first == First::ZERO);
+            });
+        } else {
+            with_nt(NF, [&](auto nt) { launch_rb_shape<NF, decltype(nt)::value>(L, A, first, p.last); });
         }
     }
 
-    template <int NF, bool SRC = false>
-    void launch_jacobi2(const Launch& L, const sfk::JacobiArgs<T, NF>& A, bool first, bool last, bool x_zero) {
-        if constexpr (!SRC) {
-            if (can_sk(L.ke - L.kb, first, x_zero, L.is_split(), 2)) {
-                launch_sk<NF, 2>(L, A, last, false);
-                return;
-            }
-        }
-        // 2x2 output vectors per thread: measured best of 1x1, 2x1, 1x2, 2x2, 4x2 (4x2 spills)
-        if (nt_stores(NF))
-            launch_fused2<NF, true, 2, 2, SRC>(L, A, first, last, x_zero);
-        else
-            launch_fused2<NF, false, 2, 2, SRC>(L, A, first, last, x_zero);
-    }
-
-    // Sweeps fused into the launch that starts at iteration `it` of a K-sweep solve: 3 where the S-sweep kernel is in
-    // use (never the first pass of a solve, whose iterate is caller data / zero / a source; a remainder of four goes
-    // as 2 + 2), else 2 where pairs can be fused, else 1. x_zero: the pass's iterate is zero; extra: the growth of its
-    // boundary launch (for_planes).
-    int sweeps_in_launch(int it, int K, bool continued, bool x_zero, int extra = 0) const {
+    // Sweeps fused into the pass that starts at iteration `it` of a K-sweep solve: 4 or 3 where the marching kernel
+    // takes it — a first pass (iterate = caller data, zero or a source) only as four sweeps under sk_first_ok; remainders
+    // of 5 and 6 go as 3 + 2 and 3 + 3; a remainder of 4 without four-sweep launches as 2 + 2 — else 2 where pairs
+    // can be fused, else 1. extra: the growth of its boundary launch (for_planes).
+    int pass_sweeps(int it, int K, bool first, int extra) const {
         const bool pair = can_fuse2() && it + 2 <= K;
         const int left = K - it;
-        if (it == 0 && !continued && sk_first_ok(K)) return 4;
-        // (the marching kernel leaves the i-shell implicit between passes: with SF_ISHELL=0 — every pass reads it from
-        // memory — it must not run at all, on one slab or many. Round 2 checked that for P_ == 1 only, and a
-        // decomposed solve mixed marching passes with pair passes that read a stale i-shell.)
-        bool marching = pair && (it > 0 || continued) && march_k_ != 0 && ishell_skip_ && !x_zero && sk_s_ >= 3 &&
-                        left >= 3;
-        if (marching && P_ == 1) marching = can_sk(nzl_, false, x_zero, false);
-        // S sweeps per pass need S ghost planes on a decomposed grid, the two-stream schedule, and an interior launch
-        // [G+S+extra, ...) the marching kernel takes (the boundary launch always goes through it: there is no other
-        // kernel of that depth)
-        auto slab_ok = [&](int S) {
-            const int interior = nzl_ - 2 * (std::max(S, G_) + extra);  // for_planes: depth = max(S, G) + extra
-            return P_ == 1 || (G_ >= S && split_enabled_ && interior >= march_min_planes_ &&
-                               (long)N_ * N_ * interior >= march_min_cells_);
-        };
-        // four sweeps per pass; remainders of 5 and 6 go as 3 + 2 and 3 + 3; without four-sweep launches a remainder of
-        // 4 goes as 2 + 2
-        if (marching && sk_s_ >= 4 && left >= 4 && left != 5 && left != 6 && slab_ok(4)) return 4;
-        if (marching && left != 4 && slab_ok(3)) return 3;
+        if (first) return sk_first_ok(K) ? 4 : (pair ? 2 : 1);
+        const bool march = pair && sw_.sk_s >= 3 && left >= 3;
+        if (march && sw_.sk_s >= 4 && left >= 4 && left != 5 && left != 6 && march_pass(4, extra)) return 4;
+        if (march && left != 4 && march_pass(3, extra)) return 3;
         return pair ? 2 : 1;
     }
     // boundary depth of a two-sweep launch: the register-blocked pair kernel works on plane pairs, and a plane block
     // must not straddle the split of a boundary launch, so with three ghost planes it takes four planes per side
     int pair_depth() const { return G_ >= 3 ? 4 : 2; }
 
-    // K Jacobi sweeps on NF fields at once; scratch buffers are swapped into the slots. dead_ishell: nothing reads the
-    // result's i-shell, so the last pass leaves it unwritten. x_zero: the iterate is zero (project's pressure).
-    // continued: the first pass of this solve has run already (op_diffuse_src).
+    // The passes of a K-sweep solve. source: the first pass folds add_source in (op_diffuse_src); x_zero: the iterate
+    // is zero (project's pressure); dead_ishell: nothing reads the result's i-shell, so no pass writes it. Reads what
+    // the constructor (and tune_schedule) set, launches nothing.
+    //
+    // Trapezoid blocks. Decomposed grid, fused pairs: a cross-stream wait in front of every interior launch costs
+    // ~10 us of idle GPU per pair (measured: tools/evgap.hip, profiles of tools/rank_share.py). So the boundary launch
+    // grows by two planes per side and pair ("trapezoid") for trap_m_ pairs: interior launch j then covers planes
+    // [G+2+2j, ...) and reads only what interior launch j-1 wrote (planes [G+2j, ...)), back to back on the compute
+    // stream, while boundary launch j (planes [G, G+2+2j), on its own stream, after interior j-1 and halo j-1) feeds
+    // the halo exchange. Every trap_m_ pairs the interior snaps back and waits for the boundary once. Same arithmetic
+    // on every plane whichever launch computes it: results do not change.
+    // With S sweeps per launch the growth is S planes per side: if interior launch j-1 started D planes into the slab,
+    // launch j starts D + max(S_j, S_{j-1}) planes in (S_j = its sweeps). S_j: it reads only what interior launch j-1
+    // wrote. S_{j-1}: it WRITES the buffer that was the input of launch j-1, which boundary launch j-1 (another
+    // stream, possibly still running) reads up to D + S_{j-1} planes in — a four-sweep launch followed by a
+    // three-sweep one raced there until this was the maximum. Its boundary launch takes those planes.
+    std::vector<Pass> plan_solve(int K, bool source, bool x_zero, bool dead_ishell) const {
+        std::vector<Pass> plan;
+        bool batch = batch_march(K, false);
+        int tj = 0, dprev = 0, sprev = 0;  // passes in the trapezoid block so far; depth and sweeps of the pass before
+        for (int it = 0; it < K;) {
+            const bool pair = can_fuse2() && it + 2 <= K;
+            Pass p{};
+            // (a zero iterate is implicit in a fused pair or a marching pass only: the first pair then loads no x at all)
+            p.first = it > 0 ? First::NONE : (source ? First::SOURCE : (x_zero && pair ? First::ZERO : First::CALLER));
+            p.sweeps = pass_sweeps(it, K, it == 0, 0);
+            p.depth = p.sweeps == 2 ? pair_depth() : p.sweeps;
+            const int depth0 = std::max(p.depth, G_);  // boundary depth without growth
+            // where its interior launch would start if it continued the trapezoid block
+            // (inject_trap_bug_: SF_TRACE_SCHEDULE's ",inject=trap" — the round-2 race, for the checker's own test)
+            const int d = dprev + (inject_trap_bug_ ? p.sweeps : std::max(p.sweeps, sprev));
+            bool cont = pair && P_ > 1 && G_ >= 2 && trap_m_ > 1 && tj > 0 && tj < trap_m_ && d >= depth0 && nzl_ > 2 * d + 2;
+            if (cont && p.sweeps >= 3 && pass_sweeps(it, K, it == 0, d - depth0) != p.sweeps) cont = false;  // interior too short
+            if (cont && p.sweeps == 2 && (d & 1)) cont = false;  // plane pairs: even boundary depth
+            p.extra = cont ? d - depth0 : 0;
+            dprev = depth0 + p.extra;
+            sprev = p.sweeps;
+            tj = cont ? tj + 1 : 1;
+            p.last = it + p.sweeps == K && !dead_ishell;
+            p.batch = batch;
+            p.name = source && it == 0 ? "jacobi_src"
+                                       : (p.sweeps == 4 ? "jacobi4" : (p.sweeps == 3 ? "jacobi3" : (p.sweeps == 2 ? "jacobi2" : "jacobi1")));
+            plan.push_back(p);
+            it += p.sweeps;
+            if (p.first == First::SOURCE) {
+                // the passes after a folded source form a solve of their own: a new trapezoid block, batched by their
+                // own count (K = 6: a pair, then one batched four-sweep pass)
+                tj = 0;
+                batch = batch_march(K - it, true);
+            }
+        }
+        return plan;
+    }
+
+    // K Jacobi sweeps on NF fields at once; scratch buffers are swapped into the slots. dead_ishell, x_zero: see
+    // plan_solve. src: diffuse with add_source folded in (op_diffuse_src) — the first pass reads the source as its
+    // iterate and the field x before add_source, forms x + dt*src in registers and stores it to the x0 slot's buffer
+    // (whose old content is dead) for the later passes.
     template <int NF>
     void op_lin_solve(const int (&x)[NF], const int (&x0)[NF], const int (&b)[NF], T a, T c, int K, bool dead_ishell,
-                      bool x_zero = false, bool continued = false) {
+                      bool x_zero = false, const int (*src)[NF] = nullptr) {
         static_assert(NF <= NSCRATCH, "not enough scratch buffers");
         if constexpr (NF > 1) {
-            if (solve_apart(K, continued)) {
+            if (solve_apart(K)) {
                 for (int f = 0; f < NF; ++f) {
-                    const int xf[1] = {x[f]}, x0f[1] = {x0[f]}, bf[1] = {b[f]};
-                    op_lin_solve<1>(xf, x0f, bf, a, c, K, dead_ishell, x_zero, continued);
+                    const int xf[1] = {x[f]}, x0f[1] = {x0[f]}, bf[1] = {b[f]}, sf[1] = {src ? (*src)[f] : 0};
+                    op_lin_solve<1>(xf, x0f, bf, a, c, K, dead_ishell, x_zero, src ? &sf : nullptr);
                 }
                 return;
             }
         }
-        const bool batch = NF > 1 && batch_march(K, continued);
         const T inv = T(1) / c;
         for (Slab& sl : slabs_)
             for (int f = 0; f < NF; ++f) {
                 ensure(sl, x[f]);
                 ensure(sl, x0[f]);
+                if (src) ensure(sl, (*src)[f]);
             }
-        // Decomposed grid, fused pairs: a cross-stream wait in front of every interior launch costs ~10 us of idle
-        // GPU per pair (measured: tools/evgap.hip, profiles of tools/rank_share.py). So the boundary launch grows by
-        // two planes per side and pair ("trapezoid") for trap_m_ pairs: interior launch j then covers planes
-        // [G+2+2j, ...) and reads only what interior launch j-1 wrote (planes [G+2j, ...)), back to back on the
-        // compute stream, while boundary launch j (planes [G, G+2+2j), on its own stream, after interior j-1 and halo
-        // j-1) feeds the halo exchange. Every trap_m_ pairs the interior snaps back and waits for the boundary once.
-        // Same arithmetic on every plane whichever launch computes it: results do not change.
-        // With S sweeps per launch the growth is S planes per side: if interior launch j-1 started D planes into the
-        // slab, launch j starts D + max(S_j, S_{j-1}) planes in (S_j = its sweeps). S_j: it reads only what interior
-        // launch j-1 wrote. S_{j-1}: it WRITES the buffer that was the input of launch j-1, which boundary launch j-1
-        // (another stream, possibly still running) reads up to D + S_{j-1} planes in — a four-sweep launch followed
-        // by a three-sweep one raced there until this was the maximum. Its boundary launch takes those planes.
-        int tj = 0, dprev = 0, sprev = 0;
-        int it = 0;
-        while (it < K) {
-            const bool pair = can_fuse2() && it + 2 <= K;
-            // three sweeps per pass where the S-sweep kernel is in use (never the first pass of a solve, whose iterate
-            // is caller data; a remainder of four goes as 2 + 2)
-            const bool zero_pair = x_zero && it == 0 && pair;  // the first fused pair then loads no x at all
-            const int step = sweeps_in_launch(it, K, continued, zero_pair);
-            const int depth0 = std::max(step == 2 ? pair_depth() : step, G_);  // boundary depth without growth
-            int extra = 0;
-            {
-                // does this launch continue the trapezoid block?
-                // (inject_trap_bug_: SF_TRACE_SCHEDULE's ",inject=trap" — the round-2 race, for the checker's own test)
-                const int d = dprev + (inject_trap_bug_ ? step : std::max(step, sprev));  // where its interior launch would start
-                bool cont = pair && P_ > 1 && G_ >= 2 && trap_m_ > 1 && tj > 0 && tj < trap_m_ && d >= depth0 &&
-                            nzl_ > 2 * d + 2;
-                if (cont && step >= 3 && sweeps_in_launch(it, K, continued, zero_pair, d - depth0) != step) cont = false;
-                if (cont && step == 2 && (d & 1)) cont = false;  // plane pairs: even boundary depth
-                if (!cont) tj = 0;
-                extra = cont ? d - depth0 : 0;
-                dprev = depth0 + extra;
-                sprev = step;
-            }
-            // the pass that writes the i-shell: the last one, unless nothing will read that shell (dead_ishell)
-            const bool last = it + step == K && !dead_ishell;
-            const bool first = it == 0 && !continued;
-            ++tj;
-            const char* name = step == 4 ? "jacobi4" : (step == 3 ? "jacobi3" : (step == 2 ? "jacobi2" : "jacobi1"));
+        for (const Pass& p : plan_solve(K, src != nullptr, x_zero, dead_ishell)) {
+            const bool from_src = p.first == First::SOURCE;
+            const int s = p.sweeps;  // = the reach of the pass in planes
             auto accesses = [&](Slab& sl, int a, int b, int lo, int hi, std::vector<Acc>& acc) {
                 for (int f = 0; f < NF; ++f) {
-                    if (!zero_pair) acc.push_back({sl.field[x[f]], false, a - step, b + step});
-                    acc.push_back({sl.field[x0[f]], false, a - (step - 1), b + (step - 1)});
+                    if (p.first != First::ZERO) acc.push_back({sl.field[from_src ? (*src)[f] : x[f]], false, a - s, b + s});
+                    acc.push_back({sl.field[from_src ? x[f] : x0[f]], false, a - (s - 1), b + (s - 1)});
                     acc.push_back({sl.scratch[f], true, lo, hi});
+                    if (from_src) acc.push_back({sl.field[x0[f]], true, a, b});
                 }
             };
-            for_planes(name, accesses, [&](const Launch& L) {
+            for_planes(p.name, accesses, [&](const Launch& L) {
                 sfk::JacobiArgs<T, NF> A{};
                 for (int f = 0; f < NF; ++f) {
-                    A.x[f] = L.sl.field[x[f]];
-                    A.x0[f] = L.sl.field[x0[f]];
+                    A.x[f] = L.sl.field[from_src ? (*src)[f] : x[f]];  // iterate (the source: Stam's initial guess)
+                    A.x0[f] = L.sl.field[from_src ? x[f] : x0[f]];     // right-hand side (the field before add_source)
                     A.xn[f] = L.sl.scratch[f];
+                    if (from_src) A.x0out[f] = L.sl.field[x0[f]];  // right-hand side x + dt*src for the later passes
                     A.b[f] = b[f];
                 }
                 A.a = a;
                 A.inv = inv;
-                if (first && step == 4)
-                    launch_sk_first<NF>(L, A, x_zero ? 3 : 1, batch);
-                else if (step == 4)  // three or four sweeps (the rest of the solve): the marching kernel
-                    launch_sk<NF, 4>(L, A, last, batch);
-                else if (step == 3)
-                    launch_sk<NF, 3>(L, A, last, batch);
-                else if (pair)
-                    launch_jacobi2<NF>(L, A, first, last, zero_pair);
-                else
-                    launch_jacobi<NF>(L, A, first, last);
-            }, step == 2 ? pair_depth() : step, extra);
+                if (from_src) A.dt = dt_;
+                launch_pass<NF>(L, A, p);
+            }, p.depth, p.extra);
+            // The pass stores the folded right-hand side on the planes it computes; on a decomposed grid the later
+            // passes also read it on the ghost planes next to the slab, which a small launch fills from the (current)
+            // ghost planes of x and src.
+            if (from_src) rhs_on_ghost_planes<NF>(x, x0, *src, p.depth);
             // the new iterate becomes the field; the old buffer becomes scratch
             for (Slab& sl : slabs_)
                 for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
             exchange<NF>(x);
-            it += step;
         }
     }
 
@@ -2371,7 +2393,7 @@ private:
     template <int NF>
     void rhs_on_ghost_planes(const int (&x)[NF], const int (&x0)[NF], const int (&src)[NF], int depth) {
         if (P_ == 1) return;
-        const bool two = split_enabled_ && nzl_ > 2 * std::max(depth, G_);
+        const bool two = sw_.split && nzl_ > 2 * std::max(depth, G_);
         for (Slab& sl : slabs_) {
             sfk::RhsPlanesArgs<T, NF> R;
             for (int f = 0; f < NF; ++f) {
@@ -2402,72 +2424,17 @@ private:
 
     // diffuse with add_source folded in (sources bound to resident slots): replaces
     //     add_source_bound(x, x0 <- src); swap(x0, x); lin_solve(x, x0)
-    // The first sweep pair reads the source as its iterate and the field before add_source, forms x + dt*src in
-    // registers and stores it to the x0 slot's buffer (whose old content is dead) for the later pairs. One pass
-    // over the arrays less per field. The pair stores the right-hand side on the planes it computes; on a
-    // decomposed grid the later pairs also read it on the first ghost plane of either side, which a small launch
-    // fills from the (current) ghost planes of x and src.
+    // by a solve whose first pass reads the source (op_lin_solve). One pass over the arrays less per field.
     template <int NF>
     void op_diffuse_src(const int (&x)[NF], const int (&x0)[NF], const int (&b)[NF], const int (&src)[NF], T a, T c,
                         int K, bool dead_ishell) {
-        if (!(fuse_src_ && can_fuse2() && K >= 2)) {
-            op_add_source_bound<NF>(x, x0, src);
-            for (int f = 0; f < NF; ++f) swap_slots(x0[f], x[f]);
-            op_lin_solve<NF>(x, x0, b, a, c, K, dead_ishell);
+        if (sw_.fuse_src && can_fuse2() && K >= 2) {
+            op_lin_solve<NF>(x, x0, b, a, c, K, dead_ishell, false, &src);
             return;
         }
-        if constexpr (NF > 1) {
-            if (solve_apart(K, false)) {
-                for (int f = 0; f < NF; ++f) {
-                    const int xf[1] = {x[f]}, x0f[1] = {x0[f]}, bf[1] = {b[f]}, sf[1] = {src[f]};
-                    op_diffuse_src<1>(xf, x0f, bf, sf, a, c, K, dead_ishell);
-                }
-                return;
-            }
-        }
-        const bool batch = NF > 1 && batch_march(K, false);
-        const T inv = T(1) / c;
-        for (Slab& sl : slabs_)
-            for (int f = 0; f < NF; ++f) {
-                ensure(sl, x[f]);
-                ensure(sl, x0[f]);
-                ensure(sl, src[f]);
-            }
-        // four: the same pass as four sweeps of the marching kernel (rhs formed per plane as it arrives, stored for the
-        // later launches), else a fused pair
-        const bool four = sk_first_ok(K);
-        const int sreach = four ? 4 : 2;  // sweeps of the first pass = its reach in planes
-        const int depth = four ? 4 : pair_depth();
-        auto accesses = [&](Slab& sl, int a, int b, int lo, int hi, std::vector<Acc>& acc) {
-            for (int f = 0; f < NF; ++f) {
-                acc.push_back({sl.field[src[f]], false, a - sreach, b + sreach});
-                acc.push_back({sl.field[x[f]], false, a - (sreach - 1), b + (sreach - 1)});
-                acc.push_back({sl.scratch[f], true, lo, hi});
-                acc.push_back({sl.field[x0[f]], true, a, b});
-            }
-        };
-        for_planes("jacobi_src", accesses, [&](const Launch& L) {
-            sfk::JacobiArgs<T, NF> A{};
-            for (int f = 0; f < NF; ++f) {
-                A.x[f] = L.sl.field[src[f]];    // iterate = the source (Stam's initial guess)
-                A.x0[f] = L.sl.field[x[f]];     // the field before add_source
-                A.xn[f] = L.sl.scratch[f];
-                A.x0out[f] = L.sl.field[x0[f]];  // right-hand side x + dt*src for the later passes
-                A.b[f] = b[f];
-            }
-            A.a = a;
-            A.inv = inv;
-            A.dt = dt_;
-            if (four)
-                launch_sk_first<NF>(L, A, 2, batch);
-            else
-                launch_jacobi2<NF, true>(L, A, true, K == 2 && !dead_ishell, false);
-        }, depth);
-        rhs_on_ghost_planes<NF>(x, x0, src, depth);
-        for (Slab& sl : slabs_)
-            for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
-        exchange<NF>(x);
-        op_lin_solve<NF>(x, x0, b, a, c, K - sreach, dead_ishell, false, true);
+        op_add_source_bound<NF>(x, x0, src);
+        for (int f = 0; f < NF; ++f) swap_slots(x0[f], x[f]);
+        op_lin_solve<NF>(x, x0, b, a, c, K, dead_ishell);
     }
 
     // dead_ishell: nothing reads the i-shell of the result, which is left unwritten
@@ -2509,7 +2476,7 @@ private:
             dim3 block;
             unsigned nblocks;
             const sfk::TileMap m = flat_map(L, block, nblocks);
-            if (advect_row_ >= 2 || (advect_row_ == 1 && NF >= 2)) {
+            if (sw_.advect_row >= 2 || (sw_.advect_row == 1 && NF >= 2)) {
                 // one cell per lane for the three velocity components. fp32: the i0+1 samples from the neighbour lane
                 // (256^3 245 -> 171 us, 512^3 1628 -> 1217; with own (i0, i0+1) pair loads 215 / 1537). fp64: own pair
                 // loads (256^3 376 -> 307 us; with neighbour-lane sharing 415). One field: the gather form stays
@@ -2517,7 +2484,7 @@ private:
                 // the pair form.
                 const int wpr = ceil_div(N_, 64);
                 const long waves = (long)wpr * N_ * (L.ke - L.kb);
-                if (advect_row_ == 3 || (advect_row_ == 1 && sizeof(T) == 8))
+                if (sw_.advect_row == 3 || (sw_.advect_row == 1 && sizeof(T) == 8))
                     launch_k(L, sfk::advect_row_kernel<T, NF, true>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
                 else
                     launch_k(L, sfk::advect_row_kernel<T, NF>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
@@ -2581,10 +2548,10 @@ private:
             A.flag = sl.d_flag;
             A.skip_ishell = dead_ishell ? 1 : 0;
             // the cell-to-lane mappings of op_advect, chosen the same way (SF_ADVECT_ROW as there)
-            if (advect_row_ >= 2 || (advect_row_ == 1 && NF >= 2)) {
+            if (sw_.advect_row >= 2 || (sw_.advect_row == 1 && NF >= 2)) {
                 const int wpr = ceil_div(N_, 64);
                 const long waves = (long)wpr * N_ * (L.ke - L.kb);
-                if (advect_row_ == 3 || (advect_row_ == 1 && sizeof(T) == 8))
+                if (sw_.advect_row == 3 || (sw_.advect_row == 1 && sizeof(T) == 8))
                     launch_k(L, sfk::advect_mc_row_kernel<T, NF, true>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
                 else
                     launch_k(L, sfk::advect_mc_row_kernel<T, NF>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
@@ -2624,7 +2591,7 @@ private:
         };
         // p = 0: when the first two sweeps are fused the kernel treats x as literal zeros and p is never read,
         // so the fill (one word per cell) is skipped; otherwise zero the whole field (ghosts and shells included)
-        const bool implicit_zero = can_fuse2() && K_ >= 2 && zero_skip_;
+        const bool implicit_zero = can_fuse2() && K_ >= 2 && sw_.zero_skip;
         if (!implicit_zero) join();
         for (Slab& sl : slabs_) {
             ensure(sl, p);
@@ -2775,25 +2742,21 @@ private:
 
     int N_, K_, device_;
     int L_ = 1, nranks_ = 1, rank_ = 0, P_ = 1, G_ = 1;
-    int fuse_maxvec_ = 512, ovl_mode_ = 1;  // fuse_maxvec_: widest row (vectors) the fused kernels take
+    const Switches sw_{};
+    int fuse_maxvec_ = 512;  // widest row (vectors) the fused kernels take
     int trap_m_ = 4, split_fields_ = 1, tuned_trap_ = -1, tuned_split_ = -1;
     int bound_[4] = {-1, -1, -1, -1};  // resident source slots (sf_bind_sources)
-    bool pending_join_ = false, split_enabled_ = true, graphs_ = false;
+    bool pending_join_ = false, graphs_ = false;
     std::vector<GraphEntry> graph_cache_;
     T dt_{}, diff_{}, visc_{};
     T eps_{}, beta_{}, amb_{};  // forces of SPEC §8 (0: off)
     int axis_ = 1;
     int mc_vel_ = SF_ADVECT_SEMI_LAGRANGIAN, mc_dens_ = SF_ADVECT_SEMI_LAGRANGIAN;  // advection schemes (SPEC §9)
     int num_cu_ = 256;
-    int nzl_ = 0, lead_ = 0, px_ = 0, nplanes_ = 0, nt_mode_ = 2;
-    int advect_row_ = 1;  // 0 gather form always, 1 one cell per lane for the three velocity components, 2 / 3 always
+    int nzl_ = 0, lead_ = 0, px_ = 0, nplanes_ = 0;
     bool dead_ishell_opt_ = true;   // SF_ISHELL=2 switches the dead-shell elision off (1: on, 0: every sweep writes it)
-    bool ishell_skip_ = true, zero_skip_ = true, fuse_src_ = true;
-    bool fuse2_ = true;
-    int march_k_ = 1, march_min_planes_ = 12;
-    long march_min_cells_ = 2500000, sk2_min_cells_ = 60000000;
-    int sk_s_ = 4;
-    bool sk_first_ = true;
+    bool ishell_skip_ = true;
+    long sk2_min_cells_ = 60000000;  // smallest launch a TWO-sweep marching pass takes (launch_pass)
     long plane_ = 0, field_elems_ = 0, pad_front_ = 0, pad_back_ = 0;
     std::vector<Slab> slabs_;
     FILE* trace_ = nullptr;  // SF_TRACE_SCHEDULE

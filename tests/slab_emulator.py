@@ -2,11 +2,12 @@
 the PRODUCTION exchange schedule of libsfgpu.so (fluidsolvergpu_amd/csrc/sf_solver.hpp):
 
   * G = 1 ... 4 ghost planes per side, chosen by the same rule as the Solver constructor (`Schedule.ghost_planes`);
-  * lin_solve in passes of S = 1 ... 4 fused sweeps (`Schedule.sweeps_in_launch`, the rule of the same name), each pass
+  * lin_solve in passes of S = 1 ... 4 fused sweeps (`Schedule.sweeps_in_launch`, the library's `pass_sweeps`), each pass
     = S sweep levels of which the first S-1 are RE-COMPUTED on the ghost planes next to the slab (what the marching /
     pair kernels do in registers), then ONE exchange of G planes per side;
-  * the folded `add_source` of bound sources (`op_diffuse_src`): the right-hand side x + dt*src exists on the planes the
-    first pass computes and on G-1 ghost planes per side (`rhs_on_ghost_planes`), nowhere else;
+  * the folded `add_source` of bound sources (`op_diffuse_src` = a `plan_solve` with a source first pass): the right-hand
+    side x + dt*src exists on the planes the first pass computes and on G-1 ghost planes per side
+    (`rhs_on_ghost_planes`), nowhere else;
   * exchanges after project_div (div), after every pass (the iterate), after project_sub (u, v, w together) and after
     advect — each one recorded as (sequence number, G, field slots): the list `SF_TRACE_SCHEDULE` writes for the same
     (N, P, K) on the device (tests/schedule_check.exchange_sequence), so the two can be compared entry by entry.
@@ -23,8 +24,11 @@ SLOT = {"u": 0, "v": 1, "w": 2, "u0": 3, "v0": 4, "w0": 5, "dens": 6, "dens0": 7
 
 
 class Schedule:
-    """Host-side launch-schedule rules of sf_solver.hpp, restated (constructor: ghost planes; sweeps_in_launch;
-    sk_first_ok; can_fuse2). Defaults = the library's defaults; keyword arguments = its SF_* switches."""
+    """Host-side launch-schedule rules of sf_solver.hpp, restated. C++ name -> here: constructor (ghost planes) ->
+    __init__; march_takes_slab (P > 1) / march_pass -> _interior_ok; sk_first_ok, can_fuse2 -> the same names;
+    pass_sweeps -> sweeps_in_launch; plan_solve -> passes (sweep counts only; `continued` = the passes after a folded
+    source, which plan_solve lays out in the same plan). Defaults = the library's defaults; keyword arguments = its
+    SF_* switches (struct Switches)."""
 
     def __init__(self, N, P, wsize=4, march=1, sk_s=4, sk_first=1, ishell=1, ghost=4, split=1, march_minp=12,
                  march_mincells_k=None, fuse2=1, fuse_src=1, zero_skip=1, split_fields=1):
@@ -71,7 +75,7 @@ class Schedule:
         marching = bool(pair and (it > 0 or continued) and self.march and self.ishell and self.sk_s >= 3 and left >= 3)
         if marching and self.P == 1:
             cells = self.N * self.N * self.nzl
-            marching = self.nzl >= self.minp and cells >= self.mincells  # can_sk(.., sweeps = 3)
+            marching = self.nzl >= self.minp and cells >= self.mincells  # march_takes(nzl)
         if marching and self.sk_s >= 4 and left >= 4 and left not in (5, 6) and self._interior_ok(4):
             return 4
         if marching and left != 4 and self._interior_ok(3):
@@ -205,7 +209,7 @@ class Slab:
 
     def lin_solve(self, names, bs, xs, x0s, a, c, K, zero=False, continued=False):
         """names: slot names of xs (for the exchange record). Fields are solved one after the other or together exactly
-        as op_lin_solve does (Schedule.fields_split). Returns the new xs."""
+        as op_lin_solve does (solve_apart -> Schedule.fields_split). Returns the new xs."""
         t = self.t
         if len(xs) > 1 and self.sch.fields_split():
             return [self.lin_solve([n], [b], [x], [x0], a, c, K, zero, continued)[0]
