@@ -218,6 +218,20 @@ int sf_reduce(sf_ctx* ctx, int op, int field, double* out) {
 int sf_diagnostics_get(sf_ctx* ctx, sf_diagnostics* out) {
     return guarded(ctx, [&](SolverBase& s) { s.diagnostics(out); });
 }
+int sf_set_pressure_solver(sf_ctx* ctx, int solver, double tol, int max_iters) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_pressure_solver(solver, tol, max_iters); });
+}
+int sf_project_cg(sf_ctx* ctx, int u, int v, int w, int p, int div, double tol, int max_iters) {
+    return guarded(ctx, [&](SolverBase& s) { s.project_cg(u, v, w, p, div, tol, max_iters); });
+}
+int sf_poisson_residual(sf_ctx* ctx, int p, int div, double* rel) {
+    return guarded(ctx, [&](SolverBase& s) { s.poisson_residual(p, div, rel); });
+}
+int sf_pressure_info_get(const sf_ctx* ctx, sf_pressure_info* out) {
+    if (!ctx || !ctx->impl || !out) return SF_ERR_INVALID;
+    ctx->impl->pressure_info(out);
+    return SF_OK;
+}
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });
 }

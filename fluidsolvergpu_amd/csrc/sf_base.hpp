@@ -104,6 +104,10 @@ public:
     virtual void tracers_get_owned(int* ids, void* xyz, void* dens, void* speed) = 0;
     virtual void reduce(int op, int field, double* out) = 0;
     virtual void diagnostics(sf_diagnostics* out) = 0;
+    virtual void set_pressure_solver(int solver, double tol, int max_iters) = 0;
+    virtual void project_cg(int u, int v, int w, int p, int div, double tol, int max_iters) = 0;
+    virtual void poisson_residual(int p, int div, double* rel) = 0;
+    virtual void pressure_info(sf_pressure_info* out) const = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

@@ -25,7 +25,7 @@
 //   sf_driver [--n 64] [--steps 20] [--iters 20] [--dtype f32|f64] [--every 10] [--out DIR]
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
-//             [--monitor M]
+//             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -35,6 +35,10 @@
 // from sf_diagnostics_get (docs/SPEC.md §10; %.17g, so the doubles read back exactly; every rank holds the same
 // numbers). A state with nonfinite > 0 ends the run: an error naming the step, exit status 3. Without --monitor the
 // driver issues exactly the calls it issued before the option existed.
+// --pressure selects what vel_step's two projections run (docs/SPEC.md §11): jacobi (the default, --iters sweeps) or
+// cg with a relative tolerance (default 1e-3) and an iteration limit (default 100). With --monitor a second line
+//   pressure step=<t> solver=<jacobi|cg> status=<s> iterations=<n> rel_residual=<g> iterations_total=<n>
+// follows each monitor line: the step's last projection (sf_pressure_info_get).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -71,6 +75,8 @@ struct Options {
     double vorticity = 0.0, buoyancy = 0.0, ambient = 0.0;
     int buoyancy_axis = 1;
     int advect_vel = SF_ADVECT_SEMI_LAGRANGIAN, advect_dens = SF_ADVECT_SEMI_LAGRANGIAN;
+    int pressure = SF_PRESSURE_JACOBI, cg_max_iters = 100;
+    double cg_tol = 1e-3;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
     int rank = 0, world = 1, local_rank = 0;
@@ -184,6 +190,31 @@ static Options parse(int argc, char** argv) {
             }
             if (which != "dens") o.advect_vel = SF_ADVECT_MACCORMACK;
             if (which != "vel") o.advect_dens = SF_ADVECT_MACCORMACK;
+        }
+        else if (s == "--pressure") {
+            // jacobi | cg | cg:tol | cg:tol:max_iters
+            const std::string spec = next();
+            const size_t c1 = spec.find(':'), c2 = c1 == std::string::npos ? c1 : spec.find(':', c1 + 1);
+            const std::string which = spec.substr(0, c1);
+            bool ok = which == "jacobi" ? c1 == std::string::npos : which == "cg";
+            if (ok && c1 != std::string::npos) {
+                char* end = nullptr;
+                const std::string ts = spec.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+                o.cg_tol = strtod(ts.c_str(), &end);
+                ok = !ts.empty() && *end == 0 && std::isfinite(o.cg_tol) && o.cg_tol > 0.0;
+                if (ok && c2 != std::string::npos) {
+                    const std::string ms = spec.substr(c2 + 1);
+                    const long m = strtol(ms.c_str(), &end, 10);
+                    ok = !ms.empty() && *end == 0 && m >= 0 && m <= 1000000;
+                    o.cg_max_iters = (int)m;
+                }
+            }
+            if (!ok) {
+                fprintf(stderr, "--pressure takes jacobi or cg[:tol[:max_iters]] (tol > 0, max_iters >= 0), not %s\n",
+                        spec.c_str());
+                exit(2);
+            }
+            o.pressure = which == "cg" ? SF_PRESSURE_CG : SF_PRESSURE_JACOBI;
         }
         // rehearsal of ONE rank's share on a one-GPU box: the geometry, buffers, launches and frame file of rank
         // --rank of --world, halo messages replaced by device-local copies (SF_FLAG_LOOPBACK_HALO), no communicator
@@ -333,6 +364,7 @@ static int run(const Options& o) {
     SF_CHECK_RETURN(sf_set_vorticity_confinement(g_ctx, o.vorticity));
     SF_CHECK_RETURN(sf_set_buoyancy(g_ctx, o.buoyancy, o.ambient, o.buoyancy_axis));
     SF_CHECK_RETURN(sf_set_advection(g_ctx, o.advect_vel, o.advect_dens));
+    if (o.pressure != SF_PRESSURE_JACOBI) SF_CHECK_RETURN(sf_set_pressure_solver(g_ctx, o.pressure, o.cg_tol, o.cg_max_iters));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);
@@ -413,6 +445,12 @@ static int run(const Options& o) {
             if (talk) {
                 printf("monitor step=%d mass=%.17g kinetic=%.17g max_div=%.17g cfl=%.17g nonfinite=%lld\n", t, d.mass,
                        d.kinetic, d.max_div, d.cfl, d.nonfinite);
+                sf_pressure_info pi;
+                SF_CHECK_RETURN(sf_pressure_info_get(g_ctx, &pi));
+                static const char* const status[3] = {"converged", "max_iters", "breakdown"};
+                printf("pressure step=%d solver=%s status=%s iterations=%d rel_residual=%.17g iterations_total=%lld\n", t,
+                       pi.solver == SF_PRESSURE_CG ? "cg" : "jacobi", status[pi.status], pi.iterations, pi.rel_residual,
+                       pi.iterations_total);
                 fflush(stdout);
             }
             if (d.nonfinite > 0) {

@@ -2948,4 +2948,182 @@ static __global__ void __launch_bounds__(256) fold_rows_kernel(const double* __r
     if (t == 0) planes[(long)p * nv + v] = a[0];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Conjugate-gradient projection (docs/SPEC.md §11). Every kernel has the row shape of the reductions above — one wave
+// per row (j, k), 16 bytes per lane, lane l taking the vectors l, l + 64, ... in increasing i — so the row record of an
+// inner product is the fold of the very lane accumulators §10 prescribes, and the field passes and the sums are one
+// launch. Per-cell expressions are in T as §11 brackets them; a term goes to double before it is multiplied.
+// Loads are unconditional and clamped to the row's last vector as above; lanes past the row end store nothing.
+template <class T>
+struct CgArgs {
+    const T* div;  // init: the right-hand side; residual: the right-hand side
+    T* p;          // update: p += a*d; residual: read only
+    T* r;          // init: written; update: r -= a*q; direction: read
+    T* d;          // init: written; apply: read at the seven points; direction: d = r + b*d
+    T* q;          // apply: written; update: read
+    T s;           // init: mu; update: (T)alpha; direction: (T)beta
+};
+
+// valid cells of the lane's vector: W, fewer in the ragged last vector, <= 0 past the row end
+template <int W>
+__device__ __forceinline__ int cg_valid(const Geom& g, int i0) {
+    const int nv = g.N - i0 + 1;
+    return nv > W ? W : nv;
+}
+
+// r = div - mu, d = r with set_bnd(0, d); row records of r.r
+template <class T>
+__global__ void __launch_bounds__(256) cg_init_kernel(Geom g, CgArgs<T> A, double* __restrict__ rows, int npad) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    double cs = 0.0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type dv = ldv(A.div + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            out[e] = dv[e] - A.s;
+            cs = cs + (e < nv ? (double)out[e] * (double)out[e] : 0.0);
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.r, r, i0, out, nv);
+            store_cells<T, W>(A.d, r, i0, out, nv);
+            emit_shells<T, W>(A.d, g, 0, i0, j, kl, out, nv);
+        }
+    }
+    const double rec = wave_fold(cs, FoldSum());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = rec;
+}
+
+// (A x)[i] = 6 x[i] - (((x[i-1] + x[i+1]) + (x[j-1] + x[j+1])) + (x[k-1] + x[k+1])) for the W cells of the lane's vector.
+// Five row loads (own, j -+ 1, k -+ 1); x[i-1] and x[i+W] come from the neighbouring lanes (DPP across the wave), except
+// at the two ends of the wave's stretch of the row, whose cells — the previous stretch's last cell or the shell cell
+// i = 0, the next stretch's first cell or the shell cell i = N+1 — are one wave-uniform load each. A ragged last vector
+// holds the shell cell N+1 itself.
+template <class T, int W>
+__device__ __forceinline__ void cg_stencil(const Geom& g, const T* __restrict__ x, long r, int m, int i0, int i0c,
+                                           typename VecT<T>::type& xc, T (&ax)[W]) {
+    typedef typename VecT<T>::type V;
+    const long q = r + i0c;
+    xc = ldv(x + q);
+    const V jm = ldv(x + q - g.px), jp = ldv(x + q + g.px);
+    const V km = ldv(x + q - g.plane), kp = ldv(x + q + g.plane);
+    const int first = 1 + 64 * W * m;             // first cell of this stretch
+    const int next = first + 64 * W;              // first cell of the next one
+    const int end = next < g.N + 1 ? next : g.N + 1;
+    const T lo = x[r + first - 1], hi = x[r + end];
+    const int lane = (int)threadIdx.x & 63;
+    T left = lane_up(xc[W - 1]), right = lane_dn(xc[0]);
+    if (lane == 0) left = lo;
+    if (i0 + W == end) right = hi;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+        const T l = (e == 0) ? left : xc[e - 1];
+        const T rt = (e == W - 1) ? right : xc[e + 1];
+        ax[e] = T(6) * xc[e] - (((l + rt) + (jm[e] + jp[e])) + (km[e] + kp[e]));
+    }
+}
+
+// RES == false: q = A d, row records of d.q (the kernel that decides the cost of an iteration).
+// RES == true:  e = div - A p, row records of e.e (value 0) and div.div (value 1); nothing is written to a field.
+template <class T, bool RES>
+__global__ void __launch_bounds__(256) cg_apply_dot_kernel(Geom g, CgArgs<T> A, double* __restrict__ rows, int npad) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const long r = row0(g, j, g.G + p);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    const T* __restrict__ x = RES ? A.p : A.d;
+    double c0 = 0.0, c1 = 0.0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        typename VecT<T>::type xc;
+        T ax[W];
+        cg_stencil<T, W>(g, x, r, m, i0, i0c, xc, ax);
+        const int nv = cg_valid<W>(g, i0);
+        if constexpr (RES) {
+            const typename VecT<T>::type dv = ldv(A.div + r + i0c);
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const T err = dv[e] - ax[e];
+                c0 = c0 + (e < nv ? (double)err * (double)err : 0.0);
+                c1 = c1 + (e < nv ? (double)dv[e] * (double)dv[e] : 0.0);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e) c0 = c0 + (e < nv ? (double)xc[e] * (double)ax[e] : 0.0);
+            if (nv > 0) store_cells<T, W>(A.q, r, i0, ax, nv);
+        }
+    }
+    const double rec0 = wave_fold(c0, FoldSum());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = rec0;
+    if constexpr (RES) {
+        const double rec1 = wave_fold(c1, FoldSum());
+        if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 1, p, j)] = rec1;
+    }
+}
+
+// p = p + a*d, r = r - a*q; row records of r.r
+template <class T>
+__global__ void __launch_bounds__(256) cg_update_kernel(Geom g, CgArgs<T> A, double* __restrict__ rows, int npad) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const long r = row0(g, j, g.G + p);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    double cs = 0.0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long c = r + i0c;
+        const typename VecT<T>::type pv = ldv(A.p + c), dv = ldv(A.d + c), rv = ldv(A.r + c), qv = ldv(A.q + c);
+        const int nv = cg_valid<W>(g, i0);
+        T op[W], orr[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            op[e] = pv[e] + A.s * dv[e];
+            orr[e] = rv[e] - A.s * qv[e];
+            cs = cs + (e < nv ? (double)orr[e] * (double)orr[e] : 0.0);
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.p, r, i0, op, nv);
+            store_cells<T, W>(A.r, r, i0, orr, nv);
+        }
+    }
+    const double rec = wave_fold(cs, FoldSum());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = rec;
+}
+
+// d = r + b*d with set_bnd(0, d): the shells go out with the cells they mirror, no set_bnd launch
+template <class T>
+__global__ void __launch_bounds__(256) cg_direction_kernel(Geom g, CgArgs<T> A) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type rv = ldv(A.r + r + i0c), dv = ldv(A.d + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) out[e] = rv[e] + A.s * dv[e];
+        if (nv > 0) {
+            store_cells<T, W>(A.d, r, i0, out, nv);
+            emit_shells<T, W>(A.d, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
 }  // namespace sfk

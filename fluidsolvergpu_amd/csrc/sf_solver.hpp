@@ -8,7 +8,8 @@
 //     (device-to-device copy between slabs of the same process, RCCL send/recv grouped over xGMI
 //     between processes) while the interior sweep runs. No collective reduction exists anywhere in
 //     the step, only neighbour exchange; sf_reduce / sf_diagnostics_get (SPEC §10) are calls of
-//     their own that the step never makes.
+//     their own that the step never makes. The one exception is opt-in: with the conjugate-gradient pressure solver
+//     selected (SPEC §11) the two projections of vel_step read their inner products on the host.
 //   * fields are named slots holding device pointers, so SPEC's "swap" is a pointer swap.
 //   * there is NO CPU fallback: without a gfx950 device sf_create fails with SF_ERR_NO_DEVICE.
 #pragma once
@@ -479,26 +480,10 @@ public:
     }
 
     void set_bnd(int b, int x) override {
-        join();
         check_field(x);
         check_b(b);
         SF_HIP(hipSetDevice(device_));
-        for (Slab& sl : slabs_) {
-            T* dev = ensure(sl, x);
-            const long n0 = std::max((long)N_ * nzl_, (long)N_ * N_);
-            const long n1 = std::max(N_, nzl_);
-            hipLaunchKernelGGL((sfk::set_bnd_kernel<T>), dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0,
-                               sl.cs, sl.geom, dev, b, 0);
-            hipLaunchKernelGGL((sfk::set_bnd_kernel<T>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0,
-                               sl.cs, sl.geom, dev, b, 1);
-            hipLaunchKernelGGL((sfk::set_bnd_kernel<T>), dim3(1), dim3(64), 0, sl.cs, sl.geom, dev, b, 2);
-        }
-        SF_HIP(hipGetLastError());
-        if (P_ > 1) {
-            for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
-            const int fs[1] = {x};
-            exchange<1>(fs);
-        }
+        op_set_bnd(b, x, nullptr);
     }
 
     void lin_solve(int b, int x, int x0, double a, double c, int iters) override {
@@ -688,7 +673,10 @@ public:
 
     void vel_step() override {
         SF_HIP(hipSetDevice(device_));
-        run_maybe_graphed(0, [&] { vel_step_body(); });
+        if (pressure_ == SF_PRESSURE_CG)  // the CG solve reads its sums on the host: nothing to capture
+            vel_step_body();
+        else
+            run_maybe_graphed(0, [&] { vel_step_body(); });
     }
     void dens_step() override {
         SF_HIP(hipSetDevice(device_));
@@ -725,7 +713,11 @@ public:
             swap_slots(SF_W0, SF_W);
             op_lin_solve<3>(vel, vel0, b123, a, T(1) + T(6) * a, K_, dead);
         }
-        op_project(SF_U, SF_V, SF_W, SF_U0, SF_V0, dead, dead);
+        const bool cg = pressure_ == SF_PRESSURE_CG;
+        if (cg)
+            op_project_cg(SF_U, SF_V, SF_W, SF_U0, SF_V0, cg_tol_, cg_max_iters_, dead);
+        else
+            op_project(SF_U, SF_V, SF_W, SF_U0, SF_V0, dead, dead);
         swap_slots(SF_U0, SF_U);
         swap_slots(SF_V0, SF_V);
         swap_slots(SF_W0, SF_W);
@@ -734,7 +726,10 @@ public:
             op_advect_mc<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
         else
             op_advect<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
-        op_project(SF_U, SF_V, SF_W, SF_U0, SF_V0, dead, false);
+        if (cg)
+            op_project_cg(SF_U, SF_V, SF_W, SF_U0, SF_V0, cg_tol_, cg_max_iters_, dead);
+        else
+            op_project(SF_U, SF_V, SF_W, SF_U0, SF_V0, dead, false);
     }
 
     // SPEC §3 dens_step.
@@ -1182,6 +1177,50 @@ public:
         out->cfl_z = r[9];
         out->cfl = std::max(std::max(r[7], r[8]), r[9]);
     }
+
+    // ---- conjugate-gradient projection (SPEC §11) ---------------------------------------------------------------
+    static void check_cg(double tol, int max_iters) {
+        SF_REQUIRE(std::isfinite(tol) && tol > 0.0, "pressure solver: tol must be finite and > 0");
+        SF_REQUIRE(max_iters >= 0, "pressure solver: max_iters must be >= 0");
+    }
+    void set_pressure_solver(int solver, double tol, int max_iters) override {
+        SF_REQUIRE(solver == SF_PRESSURE_JACOBI || solver == SF_PRESSURE_CG, "pressure solver must be 0 (Jacobi) or 1 (CG)");
+        check_cg(tol, max_iters);
+        pressure_ = solver;
+        cg_tol_ = tol;
+        cg_max_iters_ = max_iters;
+    }
+    void project_cg(int u, int v, int w, int p, int div, double tol, int max_iters) override {
+        const int all[5] = {u, v, w, p, div};
+        for (int a = 0; a < 5; ++a) {
+            check_field(all[a]);
+            for (int c = a + 1; c < 5; ++c) SF_REQUIRE(all[a] != all[c], "project_cg: fields must be distinct");
+        }
+        check_cg(tol, max_iters);
+        SF_HIP(hipSetDevice(device_));
+        op_project_cg(u, v, w, p, div, tol, max_iters);
+    }
+    void poisson_residual(int p, int div, double* rel) override {
+        SF_REQUIRE(rel != nullptr, "null result pointer");
+        check_field(p);
+        check_field(div);
+        SF_REQUIRE(p != div, "poisson_residual: p and div must be different fields");
+        join();
+        SF_HIP(hipSetDevice(device_));
+        records_alloc();
+        for (Slab& sl : slabs_) {
+            sfk::CgArgs<T> A{};
+            A.p = ensure(sl, p);
+            A.div = ensure(sl, div);
+            hipLaunchKernelGGL((sfk::cg_apply_dot_kernel<T, true>), dim3(row_blocks()), dim3(256), 0, sl.cs, sl.geom, A,
+                               sl.red_rows, rows_pad());
+            tr_records("poisson_residual", sl, {{A.p, false, G_ - 1, G_ + nzl_ + 1}, {A.div, false, G_, G_ + nzl_}});
+        }
+        double r[2];
+        finish_records(2, 2, 0, r);
+        *rel = r[1] == 0.0 ? 0.0 : std::sqrt(r[0] / r[1]);
+    }
+    void pressure_info(sf_pressure_info* out) const override { *out = info_; }
 
     int lin_solve_launches(int iters) const override {
         return (int)plan_solve(iters, false, false, false).size();
@@ -2565,37 +2604,31 @@ private:
         exchange<NF>(d);
     }
 
-    // mirror_u: u's i-shell was left unwritten by the solve before (b = 1: mirrored in project_div); dead_p: nothing reads
-    // p after this projection (its slot is overwritten before anyone looks), so the solve leaves p's i-shell unwritten
-    // and project_sub mirrors it. Both false for the public sf_project().
-    void op_project(int u, int v, int w, int p, int div, bool mirror_u = false, bool dead_p = false) {
-        mirror_u = mirror_u && ishell_skip_;
-        dead_p = dead_p && ishell_skip_ && K_ >= 1;
-        // (a projection whose pressure is dead is the first one of vel_step: its div slot is overwritten as well)
-        const bool dead_div = dead_p;
+    sfk::ProjectArgs<T> project_args(Slab& sl, int u, int v, int w, int p, int div, bool mirror_u, bool mirror_p,
+                                     bool skip_div_ishell) {
         const T Nf = (T)N_;
         const T h = T(1) / Nf;
-        auto args = [&](Slab& sl) {
-            sfk::ProjectArgs<T> A;
-            A.u = ensure(sl, u);
-            A.v = ensure(sl, v);
-            A.w = ensure(sl, w);
-            A.p = ensure(sl, p);
-            A.div = ensure(sl, div);
-            A.c_div = T(-0.5) * h;
-            A.c_grad = T(0.5) * Nf;
-            A.mirror_u = mirror_u ? 1 : 0;
-            A.mirror_p = dead_p ? 1 : 0;
-            A.skip_div_ishell = dead_div ? 1 : 0;
-            return A;
-        };
-        // p = 0: when the first two sweeps are fused the kernel treats x as literal zeros and p is never read,
-        // so the fill (one word per cell) is skipped; otherwise zero the whole field (ghosts and shells included)
-        const bool implicit_zero = can_fuse2() && K_ >= 2 && sw_.zero_skip;
-        if (!implicit_zero) join();
+        sfk::ProjectArgs<T> A;
+        A.u = ensure(sl, u);
+        A.v = ensure(sl, v);
+        A.w = ensure(sl, w);
+        A.p = ensure(sl, p);
+        A.div = ensure(sl, div);
+        A.c_div = T(-0.5) * h;
+        A.c_grad = T(0.5) * Nf;
+        A.mirror_u = mirror_u ? 1 : 0;
+        A.mirror_p = mirror_p ? 1 : 0;
+        A.skip_div_ishell = skip_div_ishell ? 1 : 0;
+        return A;
+    }
+
+    // First half of SPEC §3 project: p = 0 (zero_p: the whole field, ghosts and shells included; else the solve that
+    // follows treats p as literal zeros), div with set_bnd(0, div), div's ghost planes.
+    void project_first_half(int u, int v, int w, int p, int div, bool mirror_u, bool dead_div, bool zero_p) {
+        if (zero_p) join();
         for (Slab& sl : slabs_) {
             ensure(sl, p);
-            if (!implicit_zero) {
+            if (zero_p) {
                 SF_HIP(hipMemsetAsync(sl.field[p], 0, (size_t)field_elems_ * sizeof(T), sl.cs));
                 tr_whole("zero_p", sl, {}, {sl.field[p]});
             }
@@ -2610,7 +2643,8 @@ private:
             dim3 block;
             unsigned nblocks;
             const sfk::TileMap m = flat_map(L, block, nblocks);
-            launch_k(L, sfk::project_div_kernel<T>, dim3(nblocks), block, args(L.sl), m);
+            launch_k(L, sfk::project_div_kernel<T>, dim3(nblocks), block,
+                     project_args(L.sl, u, v, w, p, div, mirror_u, false, dead_div), m);
         });
         // div's ghost planes are exchanged although a single sweep reads div at cell centres only: the fused
         // sweep pair evaluates its first sweep on the first ghost plane and needs x0 = div there, and div is left
@@ -2618,8 +2652,10 @@ private:
         // p is zero, ghosts included.
         const int dv[1] = {div};
         exchange<1>(dv);
-        const int ps[1] = {p}, b0[1] = {0};
-        op_lin_solve<1>(ps, dv, b0, T(1), T(6), K_, dead_p, implicit_zero);
+    }
+
+    // Second half of SPEC §3 project: the gradient subtracted, set_bnd(1, u), (2, v), (3, w), their ghost planes.
+    void project_second_half(int u, int v, int w, int p, int div, bool mirror_p) {
         auto sub_acc = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
             acc.push_back({sl.field[p], false, a - 1, b_ + 1});
             for (int q : {u, v, w}) {
@@ -2631,10 +2667,182 @@ private:
             dim3 block;
             unsigned nblocks;
             const sfk::TileMap m = flat_map(L, block, nblocks);
-            launch_k(L, sfk::project_sub_kernel<T>, dim3(nblocks), block, args(L.sl), m);
+            launch_k(L, sfk::project_sub_kernel<T>, dim3(nblocks), block,
+                     project_args(L.sl, u, v, w, p, div, false, mirror_p, false), m);
         });
         const int uvw[3] = {u, v, w};
         exchange<3>(uvw);
+    }
+
+    void note_solve(int solver, int status, int iterations, double rel) {
+        info_.solver = solver;
+        info_.status = status;
+        info_.iterations = iterations;
+        info_.rel_residual = rel;
+        info_.solves_total += 1;
+        info_.iterations_total += iterations;
+    }
+
+    // mirror_u: u's i-shell was left unwritten by the solve before (b = 1: mirrored in project_div); dead_p: nothing reads
+    // p after this projection (its slot is overwritten before anyone looks), so the solve leaves p's i-shell unwritten
+    // and project_sub mirrors it. Both false for the public sf_project().
+    void op_project(int u, int v, int w, int p, int div, bool mirror_u = false, bool dead_p = false) {
+        mirror_u = mirror_u && ishell_skip_;
+        dead_p = dead_p && ishell_skip_ && K_ >= 1;
+        // (a projection whose pressure is dead is the first one of vel_step: its div slot is overwritten as well)
+        const bool dead_div = dead_p;
+        // p = 0: when the first two sweeps are fused the kernel treats x as literal zeros and p is never read,
+        // so the fill (one word per cell) is skipped; otherwise zero the whole field (ghosts and shells included)
+        const bool implicit_zero = can_fuse2() && K_ >= 2 && sw_.zero_skip;
+        project_first_half(u, v, w, p, div, mirror_u, dead_div, !implicit_zero);
+        const int ps[1] = {p}, dv[1] = {div}, b0[1] = {0};
+        op_lin_solve<1>(ps, dv, b0, T(1), T(6), K_, dead_p, implicit_zero);
+        project_second_half(u, v, w, p, div, dead_p);
+        note_solve(SF_PRESSURE_JACOBI, SF_CG_MAX_ITERS, K_, -1.0);
+    }
+
+    // ---- conjugate-gradient projection (SPEC §11) ---------------------------------------------------------------
+    // The work fields r, d, q are the three scratch buffers, addressed through internal slots while the operator is
+    // issued (exchange() takes slots), as `hat` is in op_advect_mc. Every row kernel runs a slab's nzl planes in one
+    // launch on its compute stream; d's ghost planes travel on the halo stream after every update of d while the host
+    // waits for the sum that follows. Two host synchronisations per iteration (finish_records).
+    static constexpr int CG_R = SF_NUM_FIELDS, CG_D = SF_NUM_FIELDS + 1, CG_Q = SF_NUM_FIELDS + 2;
+
+    unsigned row_blocks() const { return (unsigned)ceil_div((long)N_ * nzl_, 4L); }
+    double one_sum() {
+        double r[1];
+        finish_records(1, 1, 0, r);
+        return r[0];
+    }
+    sfk::CgArgs<T> cg_args(Slab& sl, int p, int div, T s) const {
+        sfk::CgArgs<T> A;
+        A.div = sl.field[div];
+        A.p = sl.field[p];
+        A.r = sl.field[CG_R];
+        A.d = sl.field[CG_D];
+        A.q = sl.field[CG_Q];
+        A.s = s;
+        return A;
+    }
+    // after a kernel that wrote d on every slab's compute stream: d's ghost planes
+    void cg_exchange_d() {
+        if (P_ == 1) return;
+        for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
+        const int ds[1] = {CG_D};
+        exchange<1>(ds);
+    }
+
+    void op_set_bnd(int b, int x, const char* trace_name) {
+        join();
+        for (Slab& sl : slabs_) {
+            T* dev = ensure(sl, x);
+            const long n0 = std::max((long)N_ * nzl_, (long)N_ * N_);
+            const long n1 = std::max(N_, nzl_);
+            hipLaunchKernelGGL((sfk::set_bnd_kernel<T>), dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0,
+                               sl.cs, sl.geom, dev, b, 0);
+            hipLaunchKernelGGL((sfk::set_bnd_kernel<T>), dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0,
+                               sl.cs, sl.geom, dev, b, 1);
+            hipLaunchKernelGGL((sfk::set_bnd_kernel<T>), dim3(1), dim3(64), 0, sl.cs, sl.geom, dev, b, 2);
+            if (trace_name) tr_whole(trace_name, sl, {dev}, {dev});
+        }
+        SF_HIP(hipGetLastError());
+        if (P_ > 1) {
+            for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
+            const int fs[1] = {x};
+            exchange<1>(fs);
+        }
+    }
+
+    void op_project_cg(int u, int v, int w, int p, int div, double tol, int max_iters, bool mirror_u = false) {
+        mirror_u = mirror_u && ishell_skip_;
+        records_alloc();
+        struct WorkSlots {
+            std::vector<Slab>& slabs;
+            explicit WorkSlots(std::vector<Slab>& s) : slabs(s) {
+                for (Slab& sl : slabs)
+                    for (int f = 0; f < 3; ++f) sl.field[CG_R + f] = sl.scratch[f];
+            }
+            ~WorkSlots() {
+                for (Slab& sl : slabs)
+                    for (int f = 0; f < 3; ++f) sl.field[CG_R + f] = nullptr;
+            }
+        } work_slots(slabs_);
+        const int kb = G_, ke = G_ + nzl_, npad = rows_pad();
+        const unsigned nblocks = row_blocks();
+
+        project_first_half(u, v, w, p, div, mirror_u, false, true);
+        join();
+        for (Slab& sl : slabs_) {
+            hipLaunchKernelGGL((sfk::reduce_rows_kernel<T, sfk::RED_SUM>), dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
+                               (const T*)sl.field[div], sl.red_rows, npad);
+            tr_records("cg_sum_div", sl, {{sl.field[div], false, kb, ke}});
+        }
+        const double n3 = (double)N_ * (double)N_ * (double)N_;
+        const T mu = (T)(one_sum() / n3);
+        for (Slab& sl : slabs_) {
+            int lo, hi;
+            wr_range(sl, kb, ke, lo, hi);
+            hipLaunchKernelGGL(sfk::cg_init_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
+                               cg_args(sl, p, div, mu), sl.red_rows, npad);
+            tr_records("cg_init", sl, {{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke},
+                                       {sl.field[CG_D], true, lo, hi}});
+        }
+        cg_exchange_d();
+        const double rho0 = one_sum();
+        double rho = rho0, last = rho0;
+        int status = SF_CG_MAX_ITERS, iters = 0;
+        if (rho0 == 0.0)
+            status = SF_CG_CONVERGED;
+        else if (!std::isfinite(rho0))
+            status = SF_CG_BREAKDOWN;
+        else
+            for (int n = 0; n < max_iters; ++n) {
+                join();  // d's ghost planes
+                for (Slab& sl : slabs_) {
+                    hipLaunchKernelGGL((sfk::cg_apply_dot_kernel<T, false>), dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
+                                       cg_args(sl, p, div, T(0)), sl.red_rows, npad);
+                    tr_records("cg_apply_dot", sl, {{sl.field[CG_D], false, kb - 1, ke + 1}, {sl.field[CG_Q], true, kb, ke}});
+                }
+                const double delta = one_sum();
+                if (!(delta > 0.0)) {
+                    status = SF_CG_BREAKDOWN;
+                    break;
+                }
+                const T aT = (T)(rho / delta);
+                for (Slab& sl : slabs_) {
+                    hipLaunchKernelGGL(sfk::cg_update_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
+                                       cg_args(sl, p, div, aT), sl.red_rows, npad);
+                    tr_records("cg_update", sl, {{sl.field[CG_D], false, kb, ke}, {sl.field[CG_Q], false, kb, ke},
+                                                 {sl.field[p], false, kb, ke}, {sl.field[p], true, kb, ke},
+                                                 {sl.field[CG_R], false, kb, ke}, {sl.field[CG_R], true, kb, ke}});
+                }
+                const double rho_new = one_sum();
+                last = rho_new;
+                iters = n + 1;
+                if (!std::isfinite(rho_new)) {
+                    status = SF_CG_BREAKDOWN;
+                    break;
+                }
+                if (rho_new <= (tol * tol) * rho0) {
+                    status = SF_CG_CONVERGED;
+                    break;
+                }
+                const T bT = (T)(rho_new / rho);
+                for (Slab& sl : slabs_) {
+                    int lo, hi;
+                    wr_range(sl, kb, ke, lo, hi);
+                    hipLaunchKernelGGL(sfk::cg_direction_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
+                                       cg_args(sl, p, div, bT));
+                    SF_HIP(hipGetLastError());
+                    tr_op("cg_direction", sl, sl.cs, {{sl.field[CG_R], false, kb, ke}, {sl.field[CG_D], false, kb, ke},
+                                                      {sl.field[CG_D], true, lo, hi}});
+                }
+                cg_exchange_d();
+                rho = rho_new;
+            }
+        op_set_bnd(0, p, "cg_set_bnd_p");
+        project_second_half(u, v, w, p, div, false);
+        note_solve(SF_PRESSURE_CG, status, iters, rho0 == 0.0 ? 0.0 : std::sqrt(last / rho0));
     }
 
     // ---- external forces (SPEC §8) ------------------------------------------------------------------------------
@@ -2752,6 +2960,9 @@ private:
     T eps_{}, beta_{}, amb_{};  // forces of SPEC §8 (0: off)
     int axis_ = 1;
     int mc_vel_ = SF_ADVECT_SEMI_LAGRANGIAN, mc_dens_ = SF_ADVECT_SEMI_LAGRANGIAN;  // advection schemes (SPEC §9)
+    int pressure_ = SF_PRESSURE_JACOBI, cg_max_iters_ = 100;  // what vel_step's projections run (SPEC §11)
+    double cg_tol_ = 1e-3;
+    sf_pressure_info info_{SF_PRESSURE_JACOBI, SF_CG_MAX_ITERS, 0, -1.0, 0, 0};  // the last projection
     int num_cu_ = 256;
     int nzl_ = 0, lead_ = 0, px_ = 0, nplanes_ = 0;
     bool dead_ishell_opt_ = true;   // SF_ISHELL=2 switches the dead-shell elision off (1: on, 0: every sweep writes it)

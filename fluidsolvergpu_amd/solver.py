@@ -27,6 +27,10 @@ SF_ADVECT_SEMI_LAGRANGIAN, SF_ADVECT_MACCORMACK = 0, 1
 SF_RED_SUM, SF_RED_SUM_SQ, SF_RED_MIN, SF_RED_MAX, SF_RED_MAX_ABS, SF_RED_COUNT_NONFINITE = range(6)
 REDUCE_OPS = {"sum": SF_RED_SUM, "sum_sq": SF_RED_SUM_SQ, "min": SF_RED_MIN, "max": SF_RED_MAX,
               "max_abs": SF_RED_MAX_ABS, "count_nonfinite": SF_RED_COUNT_NONFINITE}
+SF_PRESSURE_JACOBI, SF_PRESSURE_CG = 0, 1
+PRESSURE_SOLVERS = {"jacobi": SF_PRESSURE_JACOBI, "cg": SF_PRESSURE_CG}
+SF_CG_CONVERGED, SF_CG_MAX_ITERS, SF_CG_BREAKDOWN = 0, 1, 2
+CG_STATUS = ("converged", "max_iters", "breakdown")
 TRANSPORTS = ("none", "copy", "rccl", "rccl-self", "loopback")
 
 # every symbol include/sfgpu.h declares (tests check that the library exports all of them)
@@ -41,6 +45,7 @@ ABI_SYMBOLS = (
     "sf_set_vorticity_confinement", "sf_set_buoyancy", "sf_vorticity_magnitude", "sf_add_forces",
     "sf_set_advection", "sf_advect_maccormack",
     "sf_reduce", "sf_diagnostics_get",
+    "sf_set_pressure_solver", "sf_project_cg", "sf_poisson_residual", "sf_pressure_info_get",
 )
 
 
@@ -54,6 +59,12 @@ class SfDiagnostics(C.Structure):
     """sf_diagnostics of include/sfgpu.h (docs/SPEC.md §10)."""
     _fields_ = [(n, C.c_double) for n in ("mass", "dens_min", "dens_max", "kinetic", "max_speed", "max_div",
                                           "cfl_x", "cfl_y", "cfl_z", "cfl")] + [("nonfinite", C.c_longlong)]
+
+
+class SfPressureInfo(C.Structure):
+    """sf_pressure_info of include/sfgpu.h (docs/SPEC.md §11)."""
+    _fields_ = [("solver", C.c_int), ("status", C.c_int), ("iterations", C.c_int), ("rel_residual", C.c_double),
+                ("solves_total", C.c_longlong), ("iterations_total", C.c_longlong)]
 
 
 _ctx = C.c_void_p
@@ -90,6 +101,10 @@ lib.sf_set_advection.argtypes = [_ctx, C.c_int, C.c_int]
 lib.sf_advect_maccormack.argtypes = [_ctx] + [C.c_int] * 6
 lib.sf_reduce.argtypes = [_ctx, C.c_int, C.c_int, C.POINTER(C.c_double)]
 lib.sf_diagnostics_get.argtypes = [_ctx, C.POINTER(SfDiagnostics)]
+lib.sf_set_pressure_solver.argtypes = [_ctx, C.c_int, C.c_double, C.c_int]
+lib.sf_project_cg.argtypes = [_ctx] + [C.c_int] * 5 + [C.c_double, C.c_int]
+lib.sf_poisson_residual.argtypes = [_ctx, C.c_int, C.c_int, C.POINTER(C.c_double)]
+lib.sf_pressure_info_get.argtypes = [_ctx, C.POINTER(SfPressureInfo)]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -287,6 +302,30 @@ class FluidSolver:
         d = SfDiagnostics()
         self._ck(lib.sf_diagnostics_get(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in SfDiagnostics._fields_}
+
+    # -- conjugate-gradient projection (docs/SPEC.md §11) --------------------------------------
+    def set_pressure_solver(self, solver="jacobi", tol=1e-3, max_iters=100):
+        """What vel_step's two projections run: "jacobi" (the default: K sweeps, the §3 step exactly) or "cg" (until
+        the recurrence residual is <= tol * its initial value, at most max_iters iterations)."""
+        sid = PRESSURE_SOLVERS[solver] if isinstance(solver, str) else int(solver)
+        self._ck(lib.sf_set_pressure_solver(self._h, sid, float(tol), int(max_iters)))
+
+    def project_cg(self, u, v, w, p, div, tol=1e-3, max_iters=100):
+        """SPEC §11 project_cg; returns pressure_info() of this solve. Collective on several ranks; synchronises."""
+        self._ck(lib.sf_project_cg(self._h, _fid(u), _fid(v), _fid(w), _fid(p), _fid(div), float(tol), int(max_iters)))
+        return self.pressure_info()
+
+    def poisson_residual(self, p, div):
+        """||div - A p|| / ||div|| of what either solver left in the slots p and div (0 for a zero div)."""
+        out = C.c_double()
+        self._ck(lib.sf_poisson_residual(self._h, _fid(p), _fid(div), C.byref(out)))
+        return out.value
+
+    def pressure_info(self):
+        """The last projection of either kind: solver, status (SF_CG_*), iterations, rel_residual, and the totals."""
+        d = SfPressureInfo()
+        self._ck(lib.sf_pressure_info_get(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in SfPressureInfo._fields_}
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

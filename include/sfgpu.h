@@ -239,6 +239,38 @@ typedef struct sf_diagnostics { double mass, dens_min, dens_max, kinetic, max_sp
                                 cfl_x, cfl_y, cfl_z, cfl; long long nonfinite; } sf_diagnostics;
 int sf_diagnostics_get(sf_ctx* ctx, sf_diagnostics* out);
 
+/* Conjugate-gradient projection of docs/SPEC.md §11. K Jacobi sweeps do not solve the pressure equation on any grid of
+ * interest (the long modes of an N^3 grid need ~N^2 sweeps); unpreconditioned CG on the same operator
+ * A p = 6 p - (sum of the six neighbours), mirror shells of set_bnd(0, .), does in tens of iterations. Its inner
+ * products are §10 sums, so the result has the same bits for every decomposition and transport and equals the numpy
+ * reference tests/pressure_cg_ref.py.
+ *   sf_project_cg(u, v, w, p, div, tol, max_iters): div and p = 0 as sf_project, CG on A p = div - mean(div) until the
+ *       recurrence residual ||r|| <= tol * ||r0|| or max_iters iterations, then set_bnd(0, p) and the gradient
+ *       subtraction of sf_project. Five distinct slots; the three work fields are the context's own.
+ *   sf_set_pressure_solver(solver, tol, max_iters): what vel_step's two projections run. The default, SF_PRESSURE_JACOBI
+ *       (tol and max_iters are then checked and kept but not used), is the §3 / §8 / §9 step exactly, with the same
+ *       launches; sf_project is always the Jacobi operator. Per context and, like sf_set_coefficients, the same on
+ *       every rank. With SF_PRESSURE_CG selected SF_W0 is scratch of the solve on return from vel_step: do not rely on it
+ *       holding the pre-advect w.
+ *   sf_poisson_residual(p, div, rel): sqrt(sum e.e / sum div.div), e = div - A p in the context's precision, both sums
+ *       §10 sums; 0 when sum div.div == 0. No mean is removed: the honest comparison of what either solver left.
+ *   sf_pressure_info_get: the last projection of either kind (sf_project, sf_project_cg, or the second one of vel_step).
+ *       Jacobi: status SF_CG_MAX_ITERS, iterations = K, rel_residual = -1 (not computed). solves_total and
+ *       iterations_total count every projection of the context since sf_create.
+ * tol must be finite and > 0 and max_iters >= 0; anything else, an unknown solver, aliased slots or a NULL pointer is
+ * SF_ERR_INVALID. Status: CONVERGED (also: zero right-hand side, 0 iterations), MAX_ITERS, or BREAKDOWN when a sum is
+ * not finite or d.Ad is not > 0 (a NaN in the velocity; fp32 iterated far beyond its residual floor near 1e-4). A
+ * breakdown is a status, not an error: the call returns SF_OK, the fields hold what the iterations left, and sf_sync
+ * stays SF_OK. The calls are collective and synchronise on the host twice per iteration. */
+enum sf_pressure_solver { SF_PRESSURE_JACOBI = 0, SF_PRESSURE_CG = 1 };
+enum sf_cg_status { SF_CG_CONVERGED = 0, SF_CG_MAX_ITERS = 1, SF_CG_BREAKDOWN = 2 };
+typedef struct sf_pressure_info { int solver, status, iterations; double rel_residual;
+                                  long long solves_total, iterations_total; } sf_pressure_info;
+int sf_set_pressure_solver(sf_ctx* ctx, int solver, double tol, int max_iters);
+int sf_project_cg(sf_ctx* ctx, int u, int v, int w, int p, int div, double tol, int max_iters);
+int sf_poisson_residual(sf_ctx* ctx, int p, int div, double* rel);
+int sf_pressure_info_get(const sf_ctx* ctx, sf_pressure_info* out);
+
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);
 int sf_set_coefficients(sf_ctx* ctx, double dt, double diff, double visc);

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Time the conjugate-gradient projection of docs/SPEC.md §11 (measurement aid, not the benchmark).
+
+SPEC §5 inputs with bound sources (the benchmark's workload), K = 20, one process, one context per case. Every case runs
+under its own time limit (--limit seconds, SIGALRM: the process ends with status 124 and starts nothing more).
+
+  iteration   sf_project_cg with a tolerance nothing reaches, max_iters = M and max_iters = 0, host wall time from the
+              call to its return (the solve synchronises): (t_M - t_0) / iterations is one iteration, host
+              synchronisations included. Its compulsory traffic is 11 words per cell (apply: d in, q out; update: p, d,
+              r, q in, p, r out; direction: r, d in, d out); `ceiling_share` = the time those bytes take at the
+              sf_measure_copy_bandwidth of the same run / the measured time. Kernel times: run one case under
+              rocprofv3 --kernel-trace --stats; measured time - kernel time is the host's share.
+  step        vel_step + dens_step per step (host wall time of --steps steps between syncs) with Jacobi K = 20 and with
+              CG at each --tols, the iterations per step, and sf_poisson_residual / max_div of what the last step left.
+
+  python tools/pressure_bench.py                       # iteration: 256^3 fp32, 512^3 fp32, 512^3 fp64; step: 256^3 fp32
+  python tools/pressure_bench.py --cases 256:f32 --no-step   # e.g. under rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import json
+import os
+import signal
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DT, DIFF, VISC, K = 0.1, 1e-4, 1e-4, 20
+WORDS_PER_ITERATION = 11
+
+
+def context(N, dtype):
+    from bench import upload_inputs
+    from fluidsolvergpu_amd import solver as S
+
+    fs = S.FluidSolver(N, dtype=dtype, iters=K, dt=DT, diff=DIFF, visc=VISC)
+    upload_inputs(fs, N, DT)
+    fs.bind_sources()
+    return fs
+
+
+def iteration_case(N, dtype, iters, reps):
+    fs = context(N, dtype)
+    for _ in range(2):
+        fs.vel_step()
+        fs.dens_step()
+    fs.sync()
+    state = {n: fs.download(n) for n in ("u", "v", "w")}
+
+    def solve(max_iters):
+        for n, a in state.items():
+            fs.upload(n, a)
+        fs.sync()
+        t0 = time.perf_counter()
+        info = fs.project_cg("u", "v", "w", "u0", "v0", 1e-30, max_iters)
+        return (time.perf_counter() - t0) * 1e3, info
+
+    solve(2)
+    t0 = min(solve(0)[0] for _ in range(reps))
+    runs = [solve(iters) for _ in range(reps)]
+    tm, info = min(runs, key=lambda r: r[0])
+    gbps = fs.copy_bandwidth_gbps(1 << 30, 5)
+    fs.close()
+    per = (tm - t0) / max(info["iterations"], 1)
+    compulsory = WORDS_PER_ITERATION * float(N) ** 3 * (4 if dtype == "f32" else 8) / (gbps * 1e9) * 1e3
+    return {"case": "iteration", "grid": N, "dtype": dtype, "iterations": info["iterations"], "status": info["status"],
+            "solve_ms": round(tm, 4), "solve_0_iterations_ms": round(t0, 4), "iteration_ms": round(per, 4),
+            "copy_gbps": round(gbps, 1), "iteration_compulsory_ms": round(compulsory, 4),
+            "ceiling_share_incl_host": round(compulsory / per, 3)}
+
+
+def step_case(N, dtype, steps, tols, max_iters):
+    out = []
+    for tol in [None] + tols:
+        fs = context(N, dtype)
+        if tol is not None:
+            fs.set_pressure_solver("cg", tol, max_iters)
+        for _ in range(3):
+            fs.vel_step()
+            fs.dens_step()
+        best, its = 1e30, 0
+        for _ in range(3):
+            fs.sync()
+            i0 = fs.pressure_info()["iterations_total"]
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fs.vel_step()
+                fs.dens_step()
+            fs.sync()
+            best = min(best, (time.perf_counter() - t0) * 1e3 / steps)
+            its = (fs.pressure_info()["iterations_total"] - i0) / (2.0 * steps)
+        info = fs.pressure_info()
+        out.append({"case": "step", "grid": N, "dtype": dtype, "solver": "jacobi" if tol is None else "cg", "tol": tol,
+                    "step_ms": round(best, 4), "iterations_per_projection": round(its, 2), "last_status": info["status"],
+                    "last_rel_residual": info["rel_residual"], "poisson_residual": fs.poisson_residual("u0", "v0"),
+                    "max_div": fs.diagnostics()["max_div"]})
+        fs.close()
+    return out
+
+
+def limited(seconds, call):
+    def expired(*_):
+        print(json.dumps({"error": f"case exceeded its {seconds} s limit"}), flush=True)
+        os._exit(124)
+
+    signal.signal(signal.SIGALRM, expired)
+    signal.alarm(seconds)
+    try:
+        return call()
+    finally:
+        signal.alarm(0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="+", default=["256:f32", "512:f32", "512:f64"])
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--step-case", default="256:f32")
+    ap.add_argument("--tols", nargs="+", type=float, default=[1e-2, 1e-3])
+    ap.add_argument("--max-iters", type=int, default=200)
+    ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--limit", type=int, default=120)
+    a = ap.parse_args()
+    for c in a.cases:
+        n, t = c.split(":")
+        print(json.dumps(limited(a.limit, lambda: iteration_case(int(n), t, a.iters, a.reps))), flush=True)
+    if not a.no_step:
+        n, t = a.step_case.split(":")
+        for row in limited(3 * a.limit, lambda: step_case(int(n), t, a.steps, a.tols, a.max_iters)):
+            print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()
