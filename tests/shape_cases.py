@@ -1,9 +1,17 @@
 """The case table and the input builders shared by tests/test_shape_inputs_ref.py (CPU: the inputs discriminate) and
-tests/test_operator_shapes_gpu.py (GPU: forces, MacCormack, reductions at every shape and kernel form).
+tests/test_operator_shapes_gpu.py (GPU: forces, MacCormack, reductions at every shape and kernel form), and their
+counterparts for the conjugate-gradient projection of SPEC §11: tests/test_pressure_cg_inputs_ref.py (CPU) and
+tests/test_pressure_cg_shapes_gpu.py (GPU).
 
 Sizes: 1, 2, 3 (every interior cell is an edge and a corner), 5, 13, 31, 34 (less than a wave, ragged vectors), 64 (one
 full wave), 65 (one cell of a second wave; the plane fold pads to 128), 70, 130, 200 (two to four waves with a ragged
-last one). 260 and 324 (fp32) and 130, 200 (fp64) take the second trip of the SPEC §10 row partial (N > 64 W)."""
+last one). 260 and 324 (fp32) and 130, 200 (fp64) take the second trip of the SPEC §10 row partial (N > 64 W).
+
+CG_SHAPES adds the sizes around the end of a row's first stretch of 64 W cells, where the §11 stencil changes the cell
+it takes as a lane's neighbour: N = 64 W exactly (128 fp64, 256 fp32: lane 63 takes the shell cell, no second trip),
+64 W + 1 (129, 257: the second trip is one ragged vector that holds the shell cell itself), a full vector plus a ragged
+one in the second trip (131, 262) and a second trip of many lanes (200 fp64, 324 fp32). With the shared sizes every
+residue of N mod W occurs in both precisions."""
 import numpy as np
 
 DT = 0.1
@@ -12,6 +20,7 @@ SIZES = [1, 2, 3, 5, 13, 31, 34, 64, 65, 70, 130, 200]
 REDUCE_ONLY_F32 = [260, 324]
 SHAPES = [(N, dt) for N in SIZES for dt in DTYPES]
 REDUCE_SHAPES = SHAPES + [(N, np.float32) for N in REDUCE_ONLY_F32]
+CG_SHAPES = (SHAPES + [(N, np.float64) for N in (128, 129, 131)] + [(N, np.float32) for N in (256, 257, 262, 324)])
 DECOMPOSED = [(34, 2, "copy"), (34, 17, "rccl-self"), (65, 5, "copy"), (70, 2, "rccl-self"), (130, 2, "copy"),
               (130, 5, "rccl-self"), (200, 4, "copy")]
 
@@ -19,6 +28,31 @@ DECOMPOSED = [(34, 2, "copy"), (34, 17, "rccl-self"), (65, 5, "copy"), (70, 2, "
 def second_trip(N, dtype):
     """The SPEC §10 row partial takes m >= 1 (a lane adds more than one vector)."""
     return N > 64 * (16 // np.dtype(dtype).itemsize)
+
+
+def cg_iters(N):
+    """max_iters of the random-velocity solves: the numpy reference of a case stays at seconds (15 s for 324 fp32 at 3
+    iterations, 5 s for 200 fp64 at 4)."""
+    return 8 if N <= 130 else 4 if N <= 200 else 3
+
+
+# Seeds of the random-velocity solves: 500 + N, except where another seed makes the solve tell a mean divided in fp32,
+# (T)s / (T)N^3, from the mu of SPEC §11, (T)(s / N^3) (tests/test_pressure_cg_inputs_ref.py: one ulp of mu reaches r only
+# where it flips the rounding of div - mu in some cell).
+CG_SEEDS = {5: 508, 13: 532, 31: 535, 34: 500, 65: 584, 70: 503}
+
+
+def cg_seed(N):
+    return CG_SEEDS.get(N, 500 + N)
+
+
+# Seeds of stored_shell_pair. poisson_residual is the square root of a ratio of two sums, and a last-bit change of a sum
+# often does not reach it: at these sizes 900 + N does not show a second trip added in the wrong order, these seeds do.
+CG_SHELL_SEEDS = {131: 1034, 200: 1103, 262: 1163, 324: 1225}
+
+
+def shell_seed(N):
+    return CG_SHELL_SEEDS.get(N, 900 + N)
 
 
 def dname(dtype):
@@ -59,6 +93,19 @@ def mixed_flow_one_plane(N, dtype, seed):
 
 def normal_field(N, dtype, seed, scale=1.0):
     return (scale * np.random.RandomState(seed).standard_normal((N + 2,) * 3)).astype(dtype)
+
+
+def stored_shell_pair(N, dtype, seed):
+    """(p, div): standard normal on all (N+2)^3 entries and no set_bnd, so that every shell cell differs from the cell
+    it would mirror: a stencil that reads a neighbour "as stored" (SPEC §11) from the wrong cell reads another value."""
+    rng = np.random.RandomState(seed)
+    return tuple(rng.standard_normal((N + 2,) * 3).astype(dtype) for _ in range(2))
+
+
+def cg_velocity(N, dtype, seed):
+    """(u, v, w) for project_cg: 0.05-normal on all entries, shells as drawn."""
+    rng = np.random.RandomState(seed)
+    return [(0.05 * rng.standard_normal((N + 2,) * 3)).astype(dtype) for _ in range(3)]
 
 
 def decades_field(N, dtype, seed):

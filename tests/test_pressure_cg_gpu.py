@@ -9,6 +9,7 @@ import pytest
 
 import diagnostics_ref as D
 import pressure_cg_ref as R
+from shape_cases import cg_velocity as random_velocity
 from test_maccormack_gpu import OPERATOR_CASES, assert_same, make, random_fields, upload_all
 
 pytestmark = pytest.mark.gpu
@@ -26,13 +27,15 @@ def S():
     return solver
 
 
-def check_solve(fs, u, v, w, tol, max_iters, what):
-    """Uploads u, v, w, runs sf_project_cg into (u0, v0) and compares everything with the reference. Returns it."""
+def check_solve(fs, u, v, w, tol, max_iters, what, want=None):
+    """Uploads u, v, w, runs sf_project_cg into (u0, v0) and compares everything with the reference (`want`, if the
+    caller has computed R.project_cg of these arguments already). Returns it."""
     for n, a in (("u", u), ("v", v), ("w", w)):
         fs.upload(n, a)
     info = fs.project_cg("u", "v", "w", "u0", "v0", tol, max_iters)
     fs.sync()
-    want = R.project_cg(u, v, w, tol, max_iters)
+    if want is None:
+        want = R.project_cg(u, v, w, tol, max_iters)
     print(f"{what}: got {info} want status {want['status']} iterations {want['iterations']} rel {want['rel_residual']!r}")
     assert info["solver"] == S().SF_PRESSURE_CG
     assert (info["status"], info["iterations"]) == (want["status"], want["iterations"]), what
@@ -42,11 +45,6 @@ def check_solve(fs, u, v, w, tol, max_iters, what):
     got = fs.poisson_residual("u0", "v0")
     assert D.bits(got) == D.bits(R.poisson_residual(want["p"], want["div"])), what
     return want
-
-
-def random_velocity(N, dtype, seed):
-    rng = np.random.RandomState(seed)
-    return [(0.05 * rng.standard_normal((N + 2,) * 3)).astype(dtype) for _ in range(3)]
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
@@ -71,7 +69,9 @@ def test_project_cg_matches_the_reference(N, P, transport, dtype):
                          ids=lambda x: str(x) if isinstance(x, int) else x.__name__)
 def test_small_ragged_and_two_trip_rows(N, dtype):
     """N = 1, 2, 3 (every cell a wall cell), 130 (ragged vectors; the second trip of an fp64 row) and 260 fp32 (the
-    second trip of an fp32 row), at max_iters = 8."""
+    second trip of an fp32 row), at max_iters = 8. At 130 fp64 and 260 fp32 the second trip is lane 0's single vector:
+    neither the order of a second trip's additions nor lane_up / lane_dn inside the second stretch can show there.
+    tests/test_pressure_cg_shapes_gpu.py runs the sizes that do (N = 64 W, 64 W + 1, 131 / 262, 200 / 324)."""
     with make(N, dtype) as fs:
         check_solve(fs, *random_velocity(N, dtype, 600 + N), 1e-3, 8, f"N={N}")
 
@@ -133,11 +133,25 @@ def composed_step(fs, forces, mc, tol, max_iters):
 @pytest.mark.parametrize("P", [1, 4])
 @pytest.mark.parametrize("forces_mc", [False, True], ids=["plain", "forces-maccormack"])
 def test_vel_step_with_cg_is_the_composed_step(forces_mc, P, dtype):
+    vel_step_against_the_composed_step(forces_mc, P, dtype, 6)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("P", [1, 4])
+@pytest.mark.parametrize("forces_mc", [False, True], ids=["plain", "forces-maccormack"])
+def test_vel_step_with_cg_is_the_composed_step_after_a_marching_diffuse(forces_mc, P, dtype, monkeypatch):
+    """K = 9 under SF_MARCH_MINCELLS_K=0: the diffusion of vel_step runs the marching kernel, whose first pass leaves
+    the i-shell of the velocity unwritten, and project_cg mirrors u's itself; the single operators write every shell."""
+    monkeypatch.setenv("SF_MARCH_MINCELLS_K", "0")
+    vel_step_against_the_composed_step(forces_mc, P, dtype, 9)
+
+
+def vel_step_against_the_composed_step(forces_mc, P, dtype, K):
     N, tol, max_iters, steps = 32, 1e-2, 10, 2
     f = random_fields(N, dtype, 31 + P)
     out = []
     for composed in (False, True):
-        with make(N, dtype, K=6, P=P) as fs:
+        with make(N, dtype, K=K, P=P) as fs:
             upload_all(fs, f)
             if forces_mc:
                 fs.set_vorticity_confinement(0.3)
