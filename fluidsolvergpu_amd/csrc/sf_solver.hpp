@@ -22,12 +22,14 @@ template <class T>
 class Solver final : public SolverBase {
     static constexpr int W = sfk::VecT<T>::W;
     static constexpr int NSCRATCH = 3;
-    // internal slot for |curl u| of the forces (SPEC §8) while they are issued: it aliases scratch[0], which no solve
-    // holds at that point, and is null otherwise (exchange() addresses fields by slot)
-    static constexpr int MAG_SLOT = SF_NUM_FIELDS;
-    // internal slots for `hat`, the first-order result inside advect_mc (SPEC §9): HAT_SLOT + f aliases scratch[f] for
-    // the duration of op_advect_mc (no solve and no force pass runs inside it) and is null otherwise
-    static constexpr int HAT_SLOT = SF_NUM_FIELDS;
+    // Internal slots: field[WORK_SLOT + f] aliases scratch[f] while an operator whose work field must be addressed by
+    // slot is issued (exchange() and op_advect take slots). Invariant: an internal slot is non-null only while a
+    // ScratchAlias guard lives; guards do not nest; and nothing that swaps scratch pointers with slots (op_lin_solve)
+    // runs under a guard. ~Solver frees the named slots only, so a stale alias could not be freed twice.
+    static constexpr int WORK_SLOT = SF_NUM_FIELDS;
+    static constexpr int MAG_SLOT = WORK_SLOT;  // |curl u| of the forces (SPEC §8)
+    static constexpr int HAT_SLOT = WORK_SLOT;  // + f: `hat`, the first-order result inside advect_mc (SPEC §9)
+    static constexpr int CG_R = WORK_SLOT, CG_D = WORK_SLOT + 1, CG_Q = WORK_SLOT + 2;  // CG's r, d, q (SPEC §11)
 
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
@@ -56,6 +58,23 @@ class Solver final : public SolverBase {
         // [value][plane][rows_pad()] and plane records [plane][value]
         double* red_rows = nullptr;
         double* red_planes = nullptr;
+    };
+
+    // The first n internal slots of every slab alias its scratch buffers while this lives (invariant at WORK_SLOT). The
+    // alias is taken afresh by every operator, because the solves in between swap scratch pointers with slots.
+    struct ScratchAlias {
+        std::vector<Slab>& slabs;
+        const int n;
+        ScratchAlias(std::vector<Slab>& s, int n_) : slabs(s), n(n_) {
+            for (Slab& sl : slabs)
+                for (int f = 0; f < n; ++f) SF_REQUIRE(!sl.field[WORK_SLOT + f], "internal: scratch alias already set");
+            for (Slab& sl : slabs)
+                for (int f = 0; f < n; ++f) sl.field[WORK_SLOT + f] = sl.scratch[f];
+        }
+        ~ScratchAlias() {
+            for (Slab& sl : slabs)
+                for (int f = 0; f < n; ++f) sl.field[WORK_SLOT + f] = nullptr;
+        }
     };
 
     // One launch of an operator as for_planes issues it: planes [kb, ke) of slab sl on stream st (sl.cs or sl.bs).
@@ -336,7 +355,7 @@ public:
         if (trace_) std::fclose(trace_);
         if (comm_) ncclCommDestroy(comm_);
         for (Slab& sl : slabs_) {
-            for (T*& f : sl.field) free_field(f);
+            for (int f = 0; f < SF_NUM_FIELDS; ++f) free_field(sl.field[f]);  // not the internal slots: aliases
             for (T*& f : sl.scratch) free_field(f);
             if (sl.d_flag) (void)hipFree(sl.d_flag);
             if (sl.red_rows) (void)hipFree(sl.red_rows);
@@ -365,30 +384,14 @@ public:
         join();
         check_field(field);
         SF_REQUIRE(host != nullptr, "null host pointer");
-        SF_HIP(hipSetDevice(device_));
-        const size_t S = (size_t)N_ + 2;
-        for (Slab& sl : slabs_) {
-            T* dev = ensure(sl, field);
-            // every stored plane that exists globally (ghosts included) comes from the global array
-            const int gb = std::max(sl.geom.kg0, 0), ge = std::min(sl.geom.kg0 + nplanes_, N_ + 2);
-            const T* src = static_cast<const T*>(host) + (size_t)gb * S * S;
-            SF_HIP(hipMemcpy2DAsync(dev + (size_t)(gb - sl.geom.kg0) * plane_ + (lead_ - 1), (size_t)px_ * sizeof(T), src,
-                                    S * sizeof(T), S * sizeof(T), S * (size_t)(ge - gb), hipMemcpyHostToDevice, sl.cs));
-        }
-        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        (void)upload_range(field, 0, N_ + 2, static_cast<const T*>(host));  // the global array: every stored plane
     }
 
     void download(int field, void* host) override {
         join();
         check_field(field);
         SF_REQUIRE(host != nullptr, "null host pointer");
-        for (Slab& sl : slabs_) {
-            const int kb = sl.geom.kg0 + G_ - (sl.geom.wall_lo ? 1 : 0);
-            const int ke = sl.geom.kg0 + G_ + nzl_ + (sl.geom.wall_hi ? 1 : 0);
-            const size_t S = (size_t)N_ + 2;
-            copy_planes_out(sl, field, kb, ke, static_cast<T*>(host) + (size_t)kb * S * S);
-        }
-        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        (void)download_range(field, 0, N_ + 2, static_cast<T*>(host));  // the global array: every owned plane
     }
 
     void download_planes(int field, int kb, int ke, void* host) override {
@@ -396,19 +399,7 @@ public:
         check_field(field);
         SF_REQUIRE(host != nullptr, "null host pointer");
         SF_REQUIRE(kb < ke, "empty plane range");
-        const size_t S = (size_t)N_ + 2;
-        bool any = false;
-        for (Slab& sl : slabs_) {
-            // planes of [kb,ke) this slab is the owner of (interior; shell planes on wall slabs)
-            const int ob = sl.geom.kg0 + G_ - (sl.geom.wall_lo ? 1 : 0);
-            const int oe = sl.geom.kg0 + G_ + nzl_ + (sl.geom.wall_hi ? 1 : 0);
-            const int b = std::max(kb, ob), e = std::min(ke, oe);
-            if (b >= e) continue;
-            any = true;
-            copy_planes_out(sl, field, b, e, static_cast<T*>(host) + (size_t)(b - kb) * S * S);
-        }
-        SF_REQUIRE(any, "plane range not stored by this context");
-        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        SF_REQUIRE(download_range(field, kb, ke, static_cast<T*>(host)), "plane range not stored by this context");
     }
 
     void upload_planes(int field, int kb, int ke, const void* host) override {
@@ -416,22 +407,7 @@ public:
         check_field(field);
         SF_REQUIRE(host != nullptr, "null host pointer");
         SF_REQUIRE(kb < ke, "empty plane range");
-        SF_HIP(hipSetDevice(device_));
-        const size_t S = (size_t)N_ + 2;
-        bool any = false;
-        for (Slab& sl : slabs_) {
-            T* dev = ensure(sl, field);
-            const int b = std::max(std::max(kb, sl.geom.kg0), 0);
-            const int e = std::min(std::min(ke, sl.geom.kg0 + nplanes_), N_ + 2);
-            if (b >= e) continue;
-            any = true;
-            const T* src = static_cast<const T*>(host) + (size_t)(b - kb) * S * S;
-            SF_HIP(hipMemcpy2DAsync(dev + (size_t)(b - sl.geom.kg0) * plane_ + (lead_ - 1), (size_t)px_ * sizeof(T),
-                                    src, S * sizeof(T), S * sizeof(T), S * (size_t)(e - b), hipMemcpyHostToDevice,
-                                    sl.cs));
-        }
-        SF_REQUIRE(any, "plane range not stored by this context");
-        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        SF_REQUIRE(upload_range(field, kb, ke, static_cast<const T*>(host)), "plane range not stored by this context");
     }
 
     void stored_planes(int* kb, int* ke) const override {
@@ -539,11 +515,7 @@ public:
     }
 
     void project(int u, int v, int w, int p, int div) override {
-        const int all[5] = {u, v, w, p, div};
-        for (int a = 0; a < 5; ++a) {
-            check_field(all[a]);
-            for (int c = a + 1; c < 5; ++c) SF_REQUIRE(all[a] != all[c], "project: fields must be distinct");
-        }
+        check_distinct("project: fields must be distinct", {u, v, w, p, div});
         SF_HIP(hipSetDevice(device_));
         op_project(u, v, w, p, div);
     }
@@ -558,11 +530,7 @@ public:
 
     // SPEC §8 add_forces, the sources updated in place
     void add_forces(int u, int v, int w, int dens, int su, int sv, int sw) override {
-        const int all[7] = {u, v, w, dens, su, sv, sw};
-        for (int a = 0; a < 7; ++a) {
-            check_field(all[a]);
-            for (int c = a + 1; c < 7; ++c) SF_REQUIRE(all[a] != all[c], "add_forces: slots must be distinct");
-        }
+        check_distinct("add_forces: slots must be distinct", {u, v, w, dens, su, sv, sw});
         SF_HIP(hipSetDevice(device_));
         const int s[3] = {su, sv, sw};
         op_add_forces(u, v, w, dens, s, s);
@@ -582,11 +550,9 @@ public:
 
     void bind_sources(int su, int sv, int sw, int sd) override {
         const int b[4] = {su, sv, sw, sd};
-        const int own[4] = {SF_U0, SF_V0, SF_W0, SF_DENS0};
         for (int q = 0; q < 4; ++q) {
             SF_REQUIRE(b[q] >= -1 && b[q] < SF_NUM_FIELDS, "bind_sources: slot out of range");
             SF_REQUIRE(b[q] < 0 || b[q] >= SF_USER0, "bind_sources: sources must live in SF_USER0..3");
-            (void)own;
         }
         for (int q = 0; q < 4; ++q) bound_[q] = b[q];
     }
@@ -879,10 +845,7 @@ public:
     void snapshot_read(int index, void* host) override {
         SF_REQUIRE(host != nullptr, "null host pointer");
         // the planes this context is the owner of (shell planes on the end slabs), at their place in the GLOBAL array
-        const int kb = slabs_.front().geom.kg0 + G_ - (slabs_.front().geom.wall_lo ? 1 : 0);
-        const int ke = slabs_.back().geom.kg0 + G_ + nzl_ + (slabs_.back().geom.wall_hi ? 1 : 0);
-        const size_t S = (size_t)N_ + 2;
-        snapshot_read_planes(index, kb, ke, static_cast<T*>(host) + (size_t)kb * S * S);
+        snapshot_read_planes(index, 0, N_ + 2, host);
     }
 
     // Planes [kb, ke) of snapshot `index` into a host array that holds exactly those planes (dense (N+2)^2 each).
@@ -895,15 +858,12 @@ public:
         bool any = false;
         for (Slab& sl : slabs_) {
             SF_HIP(hipStreamWaitEvent(sl.os, sl.snap_done, 0));
-            const int ob = sl.geom.kg0 + G_ - (sl.geom.wall_lo ? 1 : 0);
-            const int oe = sl.geom.kg0 + G_ + nzl_ + (sl.geom.wall_hi ? 1 : 0);
+            int ob, oe;
+            owned_range(sl, ob, oe);
             const int b = std::max(kb, ob), e = std::min(ke, oe);
             if (b >= e) continue;
             any = true;
-            SF_HIP(hipMemcpy2DAsync(static_cast<T*>(host) + (size_t)(b - kb) * S * S, S * sizeof(T),
-                                    sl.snap[index] + (size_t)(b - sl.geom.kg0) * plane_ + (lead_ - 1),
-                                    (size_t)px_ * sizeof(T), S * sizeof(T), S * (size_t)(e - b), hipMemcpyDeviceToHost,
-                                    sl.os));
+            copy_planes_out(sl, sl.snap[index], sl.os, b, e, static_cast<T*>(host) + (size_t)(b - kb) * S * S);
         }
         SF_REQUIRE(any, "plane range not stored by this context");
         for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.os));
@@ -1119,20 +1079,17 @@ public:
         join();
         SF_HIP(hipSetDevice(device_));
         records_alloc();
-        const int npad = rows_pad();
-        const unsigned nblocks = (unsigned)ceil_div((long)N_ * nzl_, 4L);
-        for (Slab& sl : slabs_) {
-            const T* x = ensure(sl, field);
-            auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom, x, sl.red_rows, npad); };
-            switch (op) {
-                case SF_RED_SUM: go(sfk::reduce_rows_kernel<T, sfk::RED_SUM>); break;
-                case SF_RED_SUM_SQ: go(sfk::reduce_rows_kernel<T, sfk::RED_SUM_SQ>); break;
-                case SF_RED_MIN: go(sfk::reduce_rows_kernel<T, sfk::RED_MIN>); break;
-                case SF_RED_MAX: go(sfk::reduce_rows_kernel<T, sfk::RED_MAX>); break;
-                case SF_RED_MAX_ABS: go(sfk::reduce_rows_kernel<T, sfk::RED_MAX_ABS>); break;
-                default: go(sfk::reduce_rows_kernel<T, sfk::RED_COUNT_NONFINITE>); break;
-            }
-            tr_records("reduce_rows", sl, {{x, false, G_, G_ + nzl_}});
+        auto go = [&](auto kernel) {
+            launch_rows("reduce_rows", kernel, [&](Slab& sl) { return (const T*)ensure(sl, field); },
+                        [&](Slab& sl) { return std::vector<Acc>{{sl.field[field], false, G_, G_ + nzl_}}; });
+        };
+        switch (op) {
+            case SF_RED_SUM: go(sfk::reduce_rows_kernel<T, sfk::RED_SUM>); break;
+            case SF_RED_SUM_SQ: go(sfk::reduce_rows_kernel<T, sfk::RED_SUM_SQ>); break;
+            case SF_RED_MIN: go(sfk::reduce_rows_kernel<T, sfk::RED_MIN>); break;
+            case SF_RED_MAX: go(sfk::reduce_rows_kernel<T, sfk::RED_MAX>); break;
+            case SF_RED_MAX_ABS: go(sfk::reduce_rows_kernel<T, sfk::RED_MAX_ABS>); break;
+            default: go(sfk::reduce_rows_kernel<T, sfk::RED_COUNT_NONFINITE>); break;
         }
         const bool sum = op == SF_RED_SUM || op == SF_RED_SUM_SQ || op == SF_RED_COUNT_NONFINITE;
         const int nsum = sum ? 1 : 0, nmin = op == SF_RED_MIN ? 1 : 0;
@@ -1146,9 +1103,7 @@ public:
         join();
         SF_HIP(hipSetDevice(device_));
         records_alloc();
-        const int npad = rows_pad();
-        const unsigned nblocks = (unsigned)ceil_div((long)N_ * nzl_, 4L);
-        for (Slab& sl : slabs_) {
+        launch_rows("diag_rows", sfk::diag_rows_kernel<T>, [&](Slab& sl) {
             sfk::DiagArgs<T> A;
             A.u = sl.field[SF_U];
             A.v = sl.field[SF_V];
@@ -1156,10 +1111,11 @@ public:
             A.dens = sl.field[SF_DENS];
             A.c_div = T(-0.5) * (T(1) / (T)N_);
             A.dt0 = dt_ * (T)N_;
-            hipLaunchKernelGGL(sfk::diag_rows_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom, A, sl.red_rows, npad);
-            tr_records("diag_rows", sl, {{A.u, false, G_, G_ + nzl_}, {A.v, false, G_, G_ + nzl_},
-                                         {A.w, false, G_ - 1, G_ + nzl_ + 1}, {A.dens, false, G_, G_ + nzl_}});
-        }
+            return A;
+        }, [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[SF_U], false, G_, G_ + nzl_}, {sl.field[SF_V], false, G_, G_ + nzl_},
+                                    {sl.field[SF_W], false, G_ - 1, G_ + nzl_ + 1}, {sl.field[SF_DENS], false, G_, G_ + nzl_}};
+        });
         // record order of sfk::diag_rows_kernel: 0 mass, 1 kinetic sum, 2 nonfinite (sums), 3 dens_min (minimum),
         // 4 dens_max, 5 max speed^2, 6 max_div, 7..9 cfl_x, y, z (maxima)
         double r[sfk::DIAG_NV];
@@ -1191,11 +1147,7 @@ public:
         cg_max_iters_ = max_iters;
     }
     void project_cg(int u, int v, int w, int p, int div, double tol, int max_iters) override {
-        const int all[5] = {u, v, w, p, div};
-        for (int a = 0; a < 5; ++a) {
-            check_field(all[a]);
-            for (int c = a + 1; c < 5; ++c) SF_REQUIRE(all[a] != all[c], "project_cg: fields must be distinct");
-        }
+        check_distinct("project_cg: fields must be distinct", {u, v, w, p, div});
         check_cg(tol, max_iters);
         SF_HIP(hipSetDevice(device_));
         op_project_cg(u, v, w, p, div, tol, max_iters);
@@ -1208,14 +1160,14 @@ public:
         join();
         SF_HIP(hipSetDevice(device_));
         records_alloc();
-        for (Slab& sl : slabs_) {
+        launch_rows("poisson_residual", sfk::cg_apply_dot_kernel<T, true>, [&](Slab& sl) {
             sfk::CgArgs<T> A{};
             A.p = ensure(sl, p);
             A.div = ensure(sl, div);
-            hipLaunchKernelGGL((sfk::cg_apply_dot_kernel<T, true>), dim3(row_blocks()), dim3(256), 0, sl.cs, sl.geom, A,
-                               sl.red_rows, rows_pad());
-            tr_records("poisson_residual", sl, {{A.p, false, G_ - 1, G_ + nzl_ + 1}, {A.div, false, G_, G_ + nzl_}});
-        }
+            return A;
+        }, [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[p], false, G_ - 1, G_ + nzl_ + 1}, {sl.field[div], false, G_, G_ + nzl_}};
+        });
         double r[2];
         finish_records(2, 2, 0, r);
         *rel = r[1] == 0.0 ? 0.0 : std::sqrt(r[0] / r[1]);
@@ -1245,6 +1197,13 @@ private:
     // ---- helpers --------------------------------------------------------------------------
     static void check_field(int f) { SF_REQUIRE(f >= 0 && f < SF_NUM_FIELDS, "field id out of range"); }
     static void check_b(int b) { SF_REQUIRE(b >= 0 && b <= 3, "boundary mode b must be 0..3"); }
+    // every field valid (checked in order, each before it is compared) and no two the same: `what` is the message
+    static void check_distinct(const char* what, std::initializer_list<int> fields) {
+        for (const int* a = fields.begin(); a != fields.end(); ++a) {
+            check_field(*a);
+            for (const int* c = a + 1; c != fields.end(); ++c) SF_REQUIRE(*a != *c, what);
+        }
+    }
 
     // ---- decomposed tracers (SPEC §6.1) ------------------------------------------------------------------------
     // How the records of the neighbour below (d = 0) / above (d = 1) of local slab s reach it: no neighbour, read in
@@ -1460,15 +1419,52 @@ private:
         return (unsigned)std::max(1L, std::min(blocks, cap));
     }
 
-    void copy_planes_out(Slab& sl, int field, int kb, int ke, T* dst) {
-        SF_HIP(hipSetDevice(device_));
-        T* dev = ensure(sl, field);
+    // the planes of the global array that slab sl is the owner of: its interior, and the shell plane on a wall slab
+    void owned_range(const Slab& sl, int& kb, int& ke) const {
+        kb = sl.geom.kg0 + G_ - (sl.geom.wall_lo ? 1 : 0);
+        ke = sl.geom.kg0 + G_ + nzl_ + (sl.geom.wall_hi ? 1 : 0);
+    }
+    // global planes [kb, ke) of buffer src of slab sl into dense (N+2)^2 planes at dst, on stream st
+    void copy_planes_out(const Slab& sl, const T* src, hipStream_t st, int kb, int ke, T* dst) const {
         const size_t S = (size_t)N_ + 2;
         const int klb = kb - sl.geom.kg0;
         SF_REQUIRE(klb >= 0 && ke - sl.geom.kg0 <= nplanes_, "plane range outside slab");
-        SF_HIP(hipMemcpy2DAsync(dst, S * sizeof(T), dev + (size_t)klb * plane_ + (lead_ - 1),
-                                (size_t)px_ * sizeof(T), S * sizeof(T), S * (size_t)(ke - kb),
-                                hipMemcpyDeviceToHost, sl.cs));
+        SF_HIP(hipMemcpy2DAsync(dst, S * sizeof(T), src + (size_t)klb * plane_ + (lead_ - 1), (size_t)px_ * sizeof(T),
+                                S * sizeof(T), S * (size_t)(ke - kb), hipMemcpyDeviceToHost, st));
+    }
+    // Planes [kb, ke) of a field from / to a host array that holds exactly those planes: every slab takes the ones it
+    // stores (upload: ghost planes included) / is the owner of (download). False: no slab has any of them.
+    bool upload_range(int field, int kb, int ke, const T* host) {
+        SF_HIP(hipSetDevice(device_));
+        const size_t S = (size_t)N_ + 2;
+        bool any = false;
+        for (Slab& sl : slabs_) {
+            T* dev = ensure(sl, field);
+            const int b = std::max(std::max(kb, sl.geom.kg0), 0);
+            const int e = std::min(std::min(ke, sl.geom.kg0 + nplanes_), N_ + 2);
+            if (b >= e) continue;
+            any = true;
+            SF_HIP(hipMemcpy2DAsync(dev + (size_t)(b - sl.geom.kg0) * plane_ + (lead_ - 1), (size_t)px_ * sizeof(T),
+                                    host + (size_t)(b - kb) * S * S, S * sizeof(T), S * sizeof(T), S * (size_t)(e - b),
+                                    hipMemcpyHostToDevice, sl.cs));
+        }
+        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        return any;
+    }
+    bool download_range(int field, int kb, int ke, T* host) {
+        SF_HIP(hipSetDevice(device_));
+        const size_t S = (size_t)N_ + 2;
+        bool any = false;
+        for (Slab& sl : slabs_) {
+            int ob, oe;
+            owned_range(sl, ob, oe);
+            const int b = std::max(kb, ob), e = std::min(ke, oe);
+            if (b >= e) continue;
+            any = true;
+            copy_planes_out(sl, ensure(sl, field), sl.cs, b, e, host + (size_t)(b - kb) * S * S);
+        }
+        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        return any;
     }
 
     // 1-D banded grid of launch L for the one-vector-per-thread kernels: fills block, returns the map and block count.
@@ -1602,12 +1598,23 @@ private:
         if (comm_) SF_HIP(hipMalloc(&red_gather_, nv * N_ * sizeof(double)));
         SF_HIP(hipHostMalloc(&red_host_, nv * N_ * sizeof(double), hipHostMallocDefault));
     }
-    // trace of a row kernel on the slab's compute stream: its field reads, and the row records it writes
-    void tr_records(const char* name, const Slab& sl, std::vector<Acc> acc) {
-        SF_HIP(hipGetLastError());
-        if (!trace_) return;
-        acc.push_back({sl.red_rows, true, 0, nplanes_});
-        tr_op(name, sl, sl.cs, acc);
+    unsigned row_blocks() const { return (unsigned)ceil_div((long)N_ * nzl_, 4L); }
+    // One row kernel (one wave per row, the nzl planes of a slab in one launch: SPEC §10, §11) on every slab's compute
+    // stream, with its trace. args(sl): the kernel's argument after the geometry; acc(sl): its field accesses. RECORDS:
+    // the kernel also takes, and writes, the slab's row records.
+    template <bool RECORDS = true, class K, class ArgsF, class AccF>
+    void launch_rows(const char* name, K kernel, ArgsF args, AccF acc) {
+        for (Slab& sl : slabs_) {
+            if constexpr (RECORDS)
+                hipLaunchKernelGGL(kernel, dim3(row_blocks()), dim3(256), 0, sl.cs, sl.geom, args(sl), sl.red_rows, rows_pad());
+            else
+                hipLaunchKernelGGL(kernel, dim3(row_blocks()), dim3(256), 0, sl.cs, sl.geom, args(sl));
+            SF_HIP(hipGetLastError());
+            if (!trace_) continue;
+            std::vector<Acc> a = acc(sl);
+            if (RECORDS) a.push_back({sl.red_rows, true, 0, nplanes_});
+            tr_op(name, sl, sl.cs, a);
+        }
     }
     // Row records -> plane records -> host -> (all ranks' records) -> the fold over global k. Values below nsum are
     // sums, the next nmin minima, the rest maxima. Leaves every compute stream idle.
@@ -1657,9 +1664,7 @@ private:
         for (int s = 0; s < L_; ++s) {
             Slab& sl = slabs_[s];
             st_wait(sl, sl.cs, sl, &Slab::boundary_done);
-            st_wait(sl, sl.cs, sl, &Slab::halo_done);
-            if (s > 0) st_wait(sl, sl.cs, slabs_[s - 1], &Slab::halo_done);
-            if (s < L_ - 1) st_wait(sl, sl.cs, slabs_[s + 1], &Slab::halo_done);
+            wait_neighbourhood(s, sl.cs, &Slab::halo_done);
         }
         pending_join_ = false;
     }
@@ -1760,72 +1765,80 @@ private:
         std::fprintf(trace_, "]}\n");
     }
 
+    // G_ planes per direction and field: the first / last G_ interior planes go to the neighbour's ghost planes.
+    // Offsets in elements from the start of a field.
+    struct HaloPlanes {
+        size_t count, send_lo, send_hi, recv_lo, recv_hi;
+    };
+    HaloPlanes halo_planes() const {
+        return {(size_t)G_ * plane_, (size_t)G_ * plane_, (size_t)nzl_ * plane_, 0, (size_t)(G_ + nzl_) * plane_};
+    }
+    // stream st of local slab s waits for event e of that slab and of its neighbours in this process
+    void wait_neighbourhood(int s, hipStream_t st, hipEvent_t Slab::*e) {
+        Slab& sl = slabs_[s];
+        st_wait(sl, st, sl, e);
+        if (s > 0) st_wait(sl, st, slabs_[s - 1], e);
+        if (s < L_ - 1) st_wait(sl, st, slabs_[s + 1], e);
+    }
+    // Consumers of an exchange: the next boundary launch reads my ghosts, and neighbours that pulled from my planes
+    // must be done before I overwrite them two sweeps later. The compute stream only waits when it runs a
+    // whole-field operator (join()).
+    void consumers_wait_halo() {
+        for (int s = 0; s < L_; ++s) wait_neighbourhood(s, slabs_[s].bs, &Slab::halo_done);
+        pending_join_ = true;
+    }
+    // One copy kernel on sl's halo stream for all fields and both sides: sl's low ghost planes from slab `lo`, its high
+    // ghost planes from slab `hi` (null: that side is not copied). A neighbour gives the planes next to sl; sl itself
+    // (the loopback stand-in) the planes it would send that way.
+    template <int NF>
+    void halo_copy(Slab& sl, const int (&fields)[NF], const Slab* lo, const Slab* hi) {
+        const HaloPlanes h = halo_planes();
+        sfk::HaloCopyArgs H;
+        H.nseg = 0;
+        H.n16 = (long)(h.count * sizeof(T) / 16);
+        for (int f = 0; f < NF; ++f) {
+            T* mine = sl.field[fields[f]];
+            if (lo) {
+                H.src[H.nseg] = reinterpret_cast<const float4*>(lo->field[fields[f]] + (lo == &sl ? h.send_lo : h.send_hi));
+                H.dst[H.nseg++] = reinterpret_cast<float4*>(mine + h.recv_lo);
+            }
+            if (hi) {
+                H.src[H.nseg] = reinterpret_cast<const float4*>(hi->field[fields[f]] + (hi == &sl ? h.send_hi : h.send_lo));
+                H.dst[H.nseg++] = reinterpret_cast<float4*>(mine + h.recv_hi);
+            }
+        }
+        const unsigned gx = (unsigned)std::max(1L, std::min((H.n16 + 255) / 256, 512L));
+        hipLaunchKernelGGL(sfk::halo_copy_kernel, dim3(gx, H.nseg), dim3(256), 0, sl.hs, H);
+        SF_HIP(hipGetLastError());
+    }
+
     // Halo exchange of NF fields: first / last interior plane -> neighbour's ghost plane.
     // Must follow for_planes (uses boundary_done). Compute streams wait on the result.
     template <int NF>
     void exchange(const int (&fields)[NF]) {
         if (P_ == 1) return;
-        // G_ planes per direction: the first / last G_ interior planes go to the neighbour's ghost planes
-        const size_t gcount = (size_t)G_ * plane_;
-        const size_t bytes = gcount * sizeof(T);
-        const size_t send_lo = (size_t)G_ * plane_, send_hi = (size_t)nzl_ * plane_;
-        const size_t recv_lo = 0, recv_hi = (size_t)(G_ + nzl_) * plane_;
         tr_xchg<NF>(fields);
         ++xchg_seq_;
         if (rccl_self_) {
-            exchange_rccl_self<NF>(fields, gcount, send_lo, send_hi, recv_lo, recv_hi);
+            exchange_rccl_self<NF>(fields);
             return;
         }
+        const HaloPlanes h = halo_planes();
         for (int s = 0; s < L_; ++s) {
             Slab& sl = slabs_[s];
-            st_wait(sl, sl.hs, sl, &Slab::boundary_done);
-            const bool has_lo = sl.gid > 0, has_hi = sl.gid < P_ - 1;
-            const bool lo_local = has_lo && s > 0, hi_local = has_hi && s < L_ - 1;
-            if (lo_local) st_wait(sl, sl.hs, slabs_[s - 1], &Slab::boundary_done);
-            if (hi_local) st_wait(sl, sl.hs, slabs_[s + 1], &Slab::boundary_done);
-            // pull from neighbours that live in this process: one copy kernel for all fields and both sides
-            if (lo_local || hi_local) {
-                sfk::HaloCopyArgs H;
-                H.nseg = 0;
-                H.n16 = (long)(bytes / 16);
-                for (int f = 0; f < NF; ++f) {
-                    T* mine = sl.field[fields[f]];
-                    if (lo_local) {
-                        H.src[H.nseg] = reinterpret_cast<const float4*>(slabs_[s - 1].field[fields[f]] + send_hi);
-                        H.dst[H.nseg++] = reinterpret_cast<float4*>(mine + recv_lo);
-                    }
-                    if (hi_local) {
-                        H.src[H.nseg] = reinterpret_cast<const float4*>(slabs_[s + 1].field[fields[f]] + send_lo);
-                        H.dst[H.nseg++] = reinterpret_cast<float4*>(mine + recv_hi);
-                    }
-                }
-                const unsigned gx = (unsigned)std::max(1L, std::min((H.n16 + 255) / 256, 512L));
-                hipLaunchKernelGGL(sfk::halo_copy_kernel, dim3(gx, H.nseg), dim3(256), 0, sl.hs, H);
-                SF_HIP(hipGetLastError());
-                tr_halo<NF>("halo_pull", sl, sl.hs, fields, lo_local ? &slabs_[s - 1] : nullptr,
-                            hi_local ? &slabs_[s + 1] : nullptr, false, false);
+            wait_neighbourhood(s, sl.hs, &Slab::boundary_done);
+            // pull from neighbours that live in this process
+            Slab* lo = s > 0 ? &slabs_[s - 1] : nullptr;
+            Slab* hi = s < L_ - 1 ? &slabs_[s + 1] : nullptr;
+            if (lo || hi) {
+                halo_copy<NF>(sl, fields, lo, hi);
+                tr_halo<NF>("halo_pull", sl, sl.hs, fields, lo, hi, false, false);
             }
             // neighbours in other processes: grouped send/recv over RCCL (xGMI point-to-point)
-            const bool lo_remote = has_lo && !lo_local, hi_remote = has_hi && !hi_local;
+            const bool lo_remote = sl.gid > 0 && !lo, hi_remote = sl.gid < P_ - 1 && !hi;
             if ((lo_remote || hi_remote) && loopback_) {
                 // SF_FLAG_LOOPBACK_HALO: same bytes, same stream, same dependencies, but from this slab's own planes
-                sfk::HaloCopyArgs H;
-                H.nseg = 0;
-                H.n16 = (long)(bytes / 16);
-                for (int f = 0; f < NF; ++f) {
-                    T* mine = sl.field[fields[f]];
-                    if (lo_remote) {
-                        H.src[H.nseg] = reinterpret_cast<const float4*>(mine + send_lo);
-                        H.dst[H.nseg++] = reinterpret_cast<float4*>(mine + recv_lo);
-                    }
-                    if (hi_remote) {
-                        H.src[H.nseg] = reinterpret_cast<const float4*>(mine + send_hi);
-                        H.dst[H.nseg++] = reinterpret_cast<float4*>(mine + recv_hi);
-                    }
-                }
-                const unsigned gx = (unsigned)std::max(1L, std::min((H.n16 + 255) / 256, 512L));
-                hipLaunchKernelGGL(sfk::halo_copy_kernel, dim3(gx, H.nseg), dim3(256), 0, sl.hs, H);
-                SF_HIP(hipGetLastError());
+                halo_copy<NF>(sl, fields, lo_remote ? &sl : nullptr, hi_remote ? &sl : nullptr);
                 tr_halo<NF>("halo_loopback", sl, sl.hs, fields, nullptr, nullptr, lo_remote, hi_remote);
             } else if (lo_remote || hi_remote) {
                 const ncclDataType_t dt = sizeof(T) == 4 ? ncclFloat : ncclDouble;
@@ -1833,12 +1846,12 @@ private:
                 for (int f = 0; f < NF; ++f) {
                     T* mine = sl.field[fields[f]];
                     if (lo_remote) {
-                        SF_NCCL(ncclSend(mine + send_lo, gcount, dt, rank_ - 1, comm_, sl.hs));
-                        SF_NCCL(ncclRecv(mine + recv_lo, gcount, dt, rank_ - 1, comm_, sl.hs));
+                        SF_NCCL(ncclSend(mine + h.send_lo, h.count, dt, rank_ - 1, comm_, sl.hs));
+                        SF_NCCL(ncclRecv(mine + h.recv_lo, h.count, dt, rank_ - 1, comm_, sl.hs));
                     }
                     if (hi_remote) {
-                        SF_NCCL(ncclSend(mine + send_hi, gcount, dt, rank_ + 1, comm_, sl.hs));
-                        SF_NCCL(ncclRecv(mine + recv_hi, gcount, dt, rank_ + 1, comm_, sl.hs));
+                        SF_NCCL(ncclSend(mine + h.send_hi, h.count, dt, rank_ + 1, comm_, sl.hs));
+                        SF_NCCL(ncclRecv(mine + h.recv_hi, h.count, dt, rank_ + 1, comm_, sl.hs));
                     }
                 }
                 SF_NCCL(ncclGroupEnd());
@@ -1847,16 +1860,7 @@ private:
             }
             ev_record(sl, &Slab::halo_done, sl.hs);
         }
-        // consumers: the next boundary launch reads my ghosts, and neighbours that pulled from my planes must be
-        // done before I overwrite them two sweeps later. The compute stream only waits when it runs a
-        // whole-field operator (join()).
-        for (int s = 0; s < L_; ++s) {
-            Slab& sl = slabs_[s];
-            st_wait(sl, sl.bs, sl, &Slab::halo_done);
-            if (s > 0) st_wait(sl, sl.bs, slabs_[s - 1], &Slab::halo_done);
-            if (s < L_ - 1) st_wait(sl, sl.bs, slabs_[s + 1], &Slab::halo_done);
-        }
-        pending_join_ = true;
+        consumers_wait_halo();
     }
 
     // SF_FLAG_RCCL_SELF: the ghost planes of the L logical slabs travel through a real RCCL communicator (one rank,
@@ -1867,15 +1871,10 @@ private:
     // the neighbour's ghost planes); one group spans all slabs because a send to self needs its receive in the same
     // group.
     template <int NF>
-    void exchange_rccl_self(const int (&fields)[NF], size_t gcount, size_t send_lo, size_t send_hi, size_t recv_lo,
-                            size_t recv_hi) {
+    void exchange_rccl_self(const int (&fields)[NF]) {
         const ncclDataType_t dt = sizeof(T) == 4 ? ncclFloat : ncclDouble;
-        for (int s = 0; s < L_; ++s) {
-            Slab& sl = slabs_[s];
-            st_wait(sl, sl.hs, sl, &Slab::boundary_done);
-            if (s > 0) st_wait(sl, sl.hs, slabs_[s - 1], &Slab::boundary_done);
-            if (s < L_ - 1) st_wait(sl, sl.hs, slabs_[s + 1], &Slab::boundary_done);
-        }
+        const HaloPlanes h = halo_planes();
+        for (int s = 0; s < L_; ++s) wait_neighbourhood(s, slabs_[s].hs, &Slab::boundary_done);
         SF_NCCL(ncclGroupStart());
         for (int s = 0; s + 1 < L_; ++s) {
             Slab& lo = slabs_[s];
@@ -1884,11 +1883,11 @@ private:
                 T* a = lo.field[fields[f]];
                 T* b = hi.field[fields[f]];
                 // upward: last interior planes of slab s -> low ghost planes of slab s+1
-                SF_NCCL(ncclSend(a + send_hi, gcount, dt, 0, comm_, lo.hs));
-                SF_NCCL(ncclRecv(b + recv_lo, gcount, dt, 0, comm_, hi.hs));
+                SF_NCCL(ncclSend(a + h.send_hi, h.count, dt, 0, comm_, lo.hs));
+                SF_NCCL(ncclRecv(b + h.recv_lo, h.count, dt, 0, comm_, hi.hs));
                 // downward: first interior planes of slab s+1 -> high ghost planes of slab s
-                SF_NCCL(ncclSend(b + send_lo, gcount, dt, 0, comm_, hi.hs));
-                SF_NCCL(ncclRecv(a + recv_hi, gcount, dt, 0, comm_, lo.hs));
+                SF_NCCL(ncclSend(b + h.send_lo, h.count, dt, 0, comm_, hi.hs));
+                SF_NCCL(ncclRecv(a + h.recv_hi, h.count, dt, 0, comm_, lo.hs));
             }
         }
         SF_NCCL(ncclGroupEnd());
@@ -1897,13 +1896,14 @@ private:
             tr_halo<NF>("halo_rccl_self", slabs_[s], slabs_[s].hs, fields, s > 0 ? &slabs_[s - 1] : nullptr,
                         s < L_ - 1 ? &slabs_[s + 1] : nullptr, false, false);
         for (int s = 0; s < L_; ++s) ev_record(slabs_[s], &Slab::halo_done, slabs_[s].hs);
-        for (int s = 0; s < L_; ++s) {
-            Slab& sl = slabs_[s];
-            st_wait(sl, sl.bs, sl, &Slab::halo_done);
-            if (s > 0) st_wait(sl, sl.bs, slabs_[s - 1], &Slab::halo_done);
-            if (s < L_ - 1) st_wait(sl, sl.bs, slabs_[s + 1], &Slab::halo_done);
-        }
-        pending_join_ = true;
+        consumers_wait_halo();
+    }
+    // after whole-field kernels wrote field x on every slab's compute stream: its ghost planes
+    void publish_from_cs(int x) {
+        if (P_ == 1) return;
+        for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
+        const int fs[1] = {x};
+        exchange<1>(fs);
     }
 
     template <int NF>
@@ -2476,18 +2476,60 @@ private:
         op_lin_solve<NF>(x, x0, b, a, c, K, dead_ishell);
     }
 
+    // The cell-to-lane mapping of the advect kernels (SF_ADVECT_ROW = 0 the gather form always, 2 / 3 always the
+    // sharing / the pair form). Default: one cell per lane for the three velocity components. fp32: the i0+1 samples
+    // from the neighbour lane (256^3 245 -> 171 us, 512^3 1628 -> 1217; with own (i0, i0+1) pair loads 215 / 1537).
+    // fp64: own pair loads (256^3 376 -> 307 us; with neighbour-lane sharing 415). One field: the gather form stays
+    // (fp32 79 vs 88 / 113, fp64 130 vs 150 / 129).
+    enum class AdvectForm { GATHER, ROW, ROW_PAIRS };
+    AdvectForm advect_form(int nf) const {
+        if (!(sw_.advect_row >= 2 || (sw_.advect_row == 1 && nf >= 2))) return AdvectForm::GATHER;
+        return (sw_.advect_row == 3 || (sw_.advect_row == 1 && sizeof(T) == 8)) ? AdvectForm::ROW_PAIRS : AdvectForm::ROW;
+    }
+    // the members AdvectArgs and AdvectMcArgs have in common
+    template <class Args, int NF>
+    void fill_advect_args(Args& A, const Slab& sl, const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u,
+                          int v, int w, bool dead_ishell) const {
+        for (int f = 0; f < NF; ++f) {
+            A.d[f] = sl.field[d[f]];
+            A.d0[f] = sl.field[d0[f]];
+            A.b[f] = b[f];
+        }
+        A.u = sl.field[u];
+        A.v = sl.field[v];
+        A.w = sl.field[w];
+        A.dt0 = dt_ * (T)N_;
+        A.flag = sl.d_flag;
+        A.skip_ishell = dead_ishell ? 1 : 0;
+    }
+    // launch of the kernel of advect_form(nf) among the three given
+    template <class Args, class KG, class KR, class KP>
+    void launch_advect(const Launch& L, int nf, const Args& A, KG gather, KR row, KP row_pairs) {
+        const AdvectForm form = advect_form(nf);
+        if (form == AdvectForm::GATHER) {
+            dim3 block;
+            unsigned nblocks;
+            const sfk::TileMap m = flat_map(L, block, nblocks);
+            launch_k(L, gather, dim3(nblocks), block, A, m);
+            return;
+        }
+        const int wpr = ceil_div(N_, 64);
+        const dim3 nblocks((unsigned)ceil_div((long)wpr * N_ * (L.ke - L.kb), 4L));
+        if (form == AdvectForm::ROW_PAIRS)
+            launch_k(L, row_pairs, nblocks, 256u, A, wpr);
+        else
+            launch_k(L, row, nblocks, 256u, A, wpr);
+    }
+
     // dead_ishell: nothing reads the i-shell of the result, which is left unwritten
     template <int NF>
     void op_advect(const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u, int v, int w, bool dead_ishell) {
-        const T dt0 = dt_ * (T)N_;
         for (Slab& sl : slabs_) {
             for (int f = 0; f < NF; ++f) {
                 ensure(sl, d[f]);
                 ensure(sl, d0[f]);
             }
-            ensure(sl, u);
-            ensure(sl, v);
-            ensure(sl, w);
+            for (int f : {u, v, w}) ensure(sl, f);
         }
         auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
             for (int f = 0; f < NF; ++f) {
@@ -2499,36 +2541,10 @@ private:
             acc.push_back({sl.field[w], false, a, b_});
         };
         for_planes("advect", accesses, [&](const Launch& L) {
-            Slab& sl = L.sl;
             sfk::AdvectArgs<T, NF> A;
-            for (int f = 0; f < NF; ++f) {
-                A.d[f] = sl.field[d[f]];
-                A.d0[f] = sl.field[d0[f]];
-                A.b[f] = b[f];
-            }
-            A.u = sl.field[u];
-            A.v = sl.field[v];
-            A.w = sl.field[w];
-            A.dt0 = dt0;
-            A.flag = sl.d_flag;
-            A.skip_ishell = dead_ishell ? 1 : 0;
-            dim3 block;
-            unsigned nblocks;
-            const sfk::TileMap m = flat_map(L, block, nblocks);
-            if (sw_.advect_row >= 2 || (sw_.advect_row == 1 && NF >= 2)) {
-                // one cell per lane for the three velocity components. fp32: the i0+1 samples from the neighbour lane
-                // (256^3 245 -> 171 us, 512^3 1628 -> 1217; with own (i0, i0+1) pair loads 215 / 1537). fp64: own pair
-                // loads (256^3 376 -> 307 us; with neighbour-lane sharing 415). One field: the gather form stays
-                // (fp32 79 vs 88 / 113, fp64 130 vs 150 / 129). SF_ADVECT_ROW = 0 never, 2 / 3 always the sharing /
-                // the pair form.
-                const int wpr = ceil_div(N_, 64);
-                const long waves = (long)wpr * N_ * (L.ke - L.kb);
-                if (sw_.advect_row == 3 || (sw_.advect_row == 1 && sizeof(T) == 8))
-                    launch_k(L, sfk::advect_row_kernel<T, NF, true>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
-                else
-                    launch_k(L, sfk::advect_row_kernel<T, NF>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
-            } else
-                launch_k(L, sfk::advect_kernel<T, NF>, dim3(nblocks), block, A, m);
+            fill_advect_args(A, L.sl, d, d0, b, u, v, w, dead_ishell);
+            launch_advect(L, NF, A, sfk::advect_kernel<T, NF>, sfk::advect_row_kernel<T, NF>,
+                          sfk::advect_row_kernel<T, NF, true>);
         }, 1, 0, /*interior_reads_ghosts=*/true);  // a long back-trace may reach a ghost plane from any plane
         exchange<NF>(d);
     }
@@ -2538,7 +2554,6 @@ private:
     template <int NF>
     void op_advect_mc(const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u, int v, int w, bool dead_ishell) {
         static_assert(NF <= NSCRATCH, "not enough scratch buffers");
-        const T dt0 = dt_ * (T)N_;
         for (Slab& sl : slabs_) {
             for (int f = 0; f < NF; ++f) {
                 ensure(sl, d[f]);
@@ -2546,20 +2561,8 @@ private:
             }
             for (int f : {u, v, w}) ensure(sl, f);
         }
-        // hat lives in the scratch buffers, addressed through the HAT slots while this operator is issued (op_advect and
-        // exchange take slots). The solves swap scratch pointers with slots, so the alias is taken afresh on every call
-        // and dropped on every way out.
-        struct HatSlots {
-            std::vector<Slab>& slabs;
-            explicit HatSlots(std::vector<Slab>& s) : slabs(s) {
-                for (Slab& sl : slabs)
-                    for (int f = 0; f < NF; ++f) sl.field[HAT_SLOT + f] = sl.scratch[f];
-            }
-            ~HatSlots() {
-                for (Slab& sl : slabs)
-                    for (int f = 0; f < NF; ++f) sl.field[HAT_SLOT + f] = nullptr;
-            }
-        } hat_slots(slabs_);
+        // hat lives in the scratch buffers, addressed through the HAT slots while this operator is issued
+        ScratchAlias hat_slots(slabs_, NF);
         int hat[NF];
         for (int f = 0; f < NF; ++f) hat[f] = HAT_SLOT + f;
         op_advect<NF>(hat, d0, b, u, v, w, false);
@@ -2572,34 +2575,11 @@ private:
             for (int q : {u, v, w}) acc.push_back({sl.field[q], false, a, b_});
         };
         for_planes("advect_mc", accesses, [&](const Launch& L) {
-            Slab& sl = L.sl;
             sfk::AdvectMcArgs<T, NF> A;
-            for (int f = 0; f < NF; ++f) {
-                A.d[f] = sl.field[d[f]];
-                A.d0[f] = sl.field[d0[f]];
-                A.hat[f] = sl.field[hat[f]];
-                A.b[f] = b[f];
-            }
-            A.u = sl.field[u];
-            A.v = sl.field[v];
-            A.w = sl.field[w];
-            A.dt0 = dt0;
-            A.flag = sl.d_flag;
-            A.skip_ishell = dead_ishell ? 1 : 0;
-            // the cell-to-lane mappings of op_advect, chosen the same way (SF_ADVECT_ROW as there)
-            if (sw_.advect_row >= 2 || (sw_.advect_row == 1 && NF >= 2)) {
-                const int wpr = ceil_div(N_, 64);
-                const long waves = (long)wpr * N_ * (L.ke - L.kb);
-                if (sw_.advect_row == 3 || (sw_.advect_row == 1 && sizeof(T) == 8))
-                    launch_k(L, sfk::advect_mc_row_kernel<T, NF, true>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
-                else
-                    launch_k(L, sfk::advect_mc_row_kernel<T, NF>, dim3((unsigned)ceil_div(waves, 4L)), 256u, A, wpr);
-            } else {
-                dim3 block;
-                unsigned nblocks;
-                const sfk::TileMap m = flat_map(L, block, nblocks);
-                launch_k(L, sfk::advect_mc_kernel<T, NF>, dim3(nblocks), block, A, m);
-            }
+            fill_advect_args(A, L.sl, d, d0, b, u, v, w, dead_ishell);
+            for (int f = 0; f < NF; ++f) A.hat[f] = L.sl.field[hat[f]];
+            launch_advect(L, NF, A, sfk::advect_mc_kernel<T, NF>, sfk::advect_mc_row_kernel<T, NF>,
+                          sfk::advect_mc_row_kernel<T, NF, true>);
         }, 1, 0, /*interior_reads_ghosts=*/true);  // either trace may reach a ghost plane from any plane
         exchange<NF>(d);
     }
@@ -2706,9 +2686,6 @@ private:
     // issued (exchange() takes slots), as `hat` is in op_advect_mc. Every row kernel runs a slab's nzl planes in one
     // launch on its compute stream; d's ghost planes travel on the halo stream after every update of d while the host
     // waits for the sum that follows. Two host synchronisations per iteration (finish_records).
-    static constexpr int CG_R = SF_NUM_FIELDS, CG_D = SF_NUM_FIELDS + 1, CG_Q = SF_NUM_FIELDS + 2;
-
-    unsigned row_blocks() const { return (unsigned)ceil_div((long)N_ * nzl_, 4L); }
     double one_sum() {
         double r[1];
         finish_records(1, 1, 0, r);
@@ -2724,14 +2701,6 @@ private:
         A.s = s;
         return A;
     }
-    // after a kernel that wrote d on every slab's compute stream: d's ghost planes
-    void cg_exchange_d() {
-        if (P_ == 1) return;
-        for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
-        const int ds[1] = {CG_D};
-        exchange<1>(ds);
-    }
-
     void op_set_bnd(int b, int x, const char* trace_name) {
         join();
         for (Slab& sl : slabs_) {
@@ -2746,48 +2715,32 @@ private:
             if (trace_name) tr_whole(trace_name, sl, {dev}, {dev});
         }
         SF_HIP(hipGetLastError());
-        if (P_ > 1) {
-            for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
-            const int fs[1] = {x};
-            exchange<1>(fs);
-        }
+        publish_from_cs(x);
     }
 
     void op_project_cg(int u, int v, int w, int p, int div, double tol, int max_iters, bool mirror_u = false) {
         mirror_u = mirror_u && ishell_skip_;
         records_alloc();
-        struct WorkSlots {
-            std::vector<Slab>& slabs;
-            explicit WorkSlots(std::vector<Slab>& s) : slabs(s) {
-                for (Slab& sl : slabs)
-                    for (int f = 0; f < 3; ++f) sl.field[CG_R + f] = sl.scratch[f];
-            }
-            ~WorkSlots() {
-                for (Slab& sl : slabs)
-                    for (int f = 0; f < 3; ++f) sl.field[CG_R + f] = nullptr;
-            }
-        } work_slots(slabs_);
-        const int kb = G_, ke = G_ + nzl_, npad = rows_pad();
-        const unsigned nblocks = row_blocks();
+        ScratchAlias work_slots(slabs_, 3);
+        const int kb = G_, ke = G_ + nzl_;
+        // d as a kernel writes it: the shell plane of a wall slab included
+        auto d_written = [&](Slab& sl) {
+            int lo, hi;
+            wr_range(sl, kb, ke, lo, hi);
+            return Acc{sl.field[CG_D], true, lo, hi};
+        };
 
         project_first_half(u, v, w, p, div, mirror_u, false, true);
         join();
-        for (Slab& sl : slabs_) {
-            hipLaunchKernelGGL((sfk::reduce_rows_kernel<T, sfk::RED_SUM>), dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
-                               (const T*)sl.field[div], sl.red_rows, npad);
-            tr_records("cg_sum_div", sl, {{sl.field[div], false, kb, ke}});
-        }
+        launch_rows("cg_sum_div", sfk::reduce_rows_kernel<T, sfk::RED_SUM>,
+                    [&](Slab& sl) { return (const T*)sl.field[div]; },
+                    [&](Slab& sl) { return std::vector<Acc>{{sl.field[div], false, kb, ke}}; });
         const double n3 = (double)N_ * (double)N_ * (double)N_;
         const T mu = (T)(one_sum() / n3);
-        for (Slab& sl : slabs_) {
-            int lo, hi;
-            wr_range(sl, kb, ke, lo, hi);
-            hipLaunchKernelGGL(sfk::cg_init_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
-                               cg_args(sl, p, div, mu), sl.red_rows, npad);
-            tr_records("cg_init", sl, {{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke},
-                                       {sl.field[CG_D], true, lo, hi}});
-        }
-        cg_exchange_d();
+        launch_rows("cg_init", sfk::cg_init_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, mu); }, [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke}, d_written(sl)};
+        });
+        publish_from_cs(CG_D);
         const double rho0 = one_sum();
         double rho = rho0, last = rho0;
         int status = SF_CG_MAX_ITERS, iters = 0;
@@ -2798,24 +2751,22 @@ private:
         else
             for (int n = 0; n < max_iters; ++n) {
                 join();  // d's ghost planes
-                for (Slab& sl : slabs_) {
-                    hipLaunchKernelGGL((sfk::cg_apply_dot_kernel<T, false>), dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
-                                       cg_args(sl, p, div, T(0)), sl.red_rows, npad);
-                    tr_records("cg_apply_dot", sl, {{sl.field[CG_D], false, kb - 1, ke + 1}, {sl.field[CG_Q], true, kb, ke}});
-                }
+                launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false>,
+                            [&](Slab& sl) { return cg_args(sl, p, div, T(0)); }, [&](Slab& sl) {
+                                return std::vector<Acc>{{sl.field[CG_D], false, kb - 1, ke + 1}, {sl.field[CG_Q], true, kb, ke}};
+                            });
                 const double delta = one_sum();
                 if (!(delta > 0.0)) {
                     status = SF_CG_BREAKDOWN;
                     break;
                 }
                 const T aT = (T)(rho / delta);
-                for (Slab& sl : slabs_) {
-                    hipLaunchKernelGGL(sfk::cg_update_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
-                                       cg_args(sl, p, div, aT), sl.red_rows, npad);
-                    tr_records("cg_update", sl, {{sl.field[CG_D], false, kb, ke}, {sl.field[CG_Q], false, kb, ke},
-                                                 {sl.field[p], false, kb, ke}, {sl.field[p], true, kb, ke},
-                                                 {sl.field[CG_R], false, kb, ke}, {sl.field[CG_R], true, kb, ke}});
-                }
+                launch_rows("cg_update", sfk::cg_update_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, aT); },
+                            [&](Slab& sl) {
+                                return std::vector<Acc>{{sl.field[CG_D], false, kb, ke}, {sl.field[CG_Q], false, kb, ke},
+                                                        {sl.field[p], false, kb, ke},    {sl.field[p], true, kb, ke},
+                                                        {sl.field[CG_R], false, kb, ke}, {sl.field[CG_R], true, kb, ke}};
+                            });
                 const double rho_new = one_sum();
                 last = rho_new;
                 iters = n + 1;
@@ -2828,16 +2779,13 @@ private:
                     break;
                 }
                 const T bT = (T)(rho_new / rho);
-                for (Slab& sl : slabs_) {
-                    int lo, hi;
-                    wr_range(sl, kb, ke, lo, hi);
-                    hipLaunchKernelGGL(sfk::cg_direction_kernel<T>, dim3(nblocks), dim3(256), 0, sl.cs, sl.geom,
-                                       cg_args(sl, p, div, bT));
-                    SF_HIP(hipGetLastError());
-                    tr_op("cg_direction", sl, sl.cs, {{sl.field[CG_R], false, kb, ke}, {sl.field[CG_D], false, kb, ke},
-                                                      {sl.field[CG_D], true, lo, hi}});
-                }
-                cg_exchange_d();
+                // the one row kernel that writes no row records
+                launch_rows<false>("cg_direction", sfk::cg_direction_kernel<T>,
+                                   [&](Slab& sl) { return cg_args(sl, p, div, bT); }, [&](Slab& sl) {
+                                       return std::vector<Acc>{{sl.field[CG_R], false, kb, ke}, {sl.field[CG_D], false, kb, ke},
+                                                               d_written(sl)};
+                                   });
+                publish_from_cs(CG_D);
                 rho = rho_new;
             }
         op_set_bnd(0, p, "cg_set_bnd_p");
@@ -2891,7 +2839,7 @@ private:
     }
 
     // add_forces(u, v, w, dens, src -> dst): dst_a = src_a + f_a on interior cells, src's shells copied where dst is
-    // another slot (bound sources), then the ghost planes of dst. |curl u| lives in scratch[0] meanwhile.
+    // another slot (bound sources), then the ghost planes of dst. |curl u| lives in scratch[0] meanwhile (MAG_SLOT).
     void op_add_forces(int u, int v, int w, int dens, const int (&src)[3], const int (&dst)[3]) {
         const bool vort = eps_ != T(0), buoy = beta_ != T(0);
         if (!vort && !buoy) return;
@@ -2903,10 +2851,8 @@ private:
                 ensure(sl, dst[a]);
             }
         }
-        if (vort) {
-            for (Slab& sl : slabs_) sl.field[MAG_SLOT] = sl.scratch[0];
-            op_vorticity(u, v, w, MAG_SLOT);
-        }
+        ScratchAlias mag_slot(slabs_, vort ? 1 : 0);
+        if (vort) op_vorticity(u, v, w, MAG_SLOT);
         auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
             if (vort) {
                 acc.push_back({sl.field[u], false, a - 1, b_ + 1});
@@ -2944,8 +2890,6 @@ private:
         // the sources' ghost planes: the fused first sweep of diffuse evaluates on the first ghost plane and reads x0
         // and the initial iterate there (see op_project)
         exchange<3>(dst);
-        if (vort)
-            for (Slab& sl : slabs_) sl.field[MAG_SLOT] = nullptr;
     }
 
     int N_, K_, device_;
