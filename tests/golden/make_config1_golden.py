@@ -12,12 +12,13 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import numpy as np  # noqa: E402
 import ref_writer  # noqa: E402
-import test_config1_plumbing as T  # noqa: E402
+import ref_support as T  # noqa: E402
+from fluidsolvergpu_amd import vtk as sfvtk  # noqa: E402
 
 f, dens, vel = T.run_config1()
 out = {"dens_sum": float(dens.sum()), "dens_max": float(dens.max()), "dens_argmax": int(np.argmax(dens)),
        "writer": "reference (oracle/_ref)" if ref_writer.available() else "sfvtk"}
-w = ref_writer.Writer() if ref_writer.available() else T.sfvtk
+w = ref_writer.Writer() if ref_writer.available() else sfvtk
 d = tempfile.mkdtemp()
 for ub, key in ((1, "binary"), (0, "ascii")):
     p = os.path.join(d, key + ".vtk")

@@ -8,14 +8,7 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_functions(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(?:int|void|const char\s*\*)\s+(\w+)\s*\(", text)))
+from abi_header import ROOT, declared_functions
 
 
 def test_sfgpu_exports_every_declared_symbol():
@@ -83,7 +76,8 @@ def test_driver_rejects_rank_override_without_loopback():
 
 def test_switch_table_matches_the_library_and_the_switch_tests():
     """INTEGRATION.md §5 documents exactly the SF_* switches libsfgpu.so reads (at most twenty), and each of them is
-    exercised by a GPU test (tests/test_switches_gpu.py, or the test the table / that file names)."""
+    exercised by a GPU test (tests/test_switches_gpu.py, or the test the table / that file names; the fixtures that set a
+    switch are in tests/gpu_support.py)."""
     src = ""
     for f in ("sf_solver.hpp", "sf_base.hpp", "sf_api.hip", "sf_kernels.hpp"):
         src += open(os.path.join(ROOT, "fluidsolvergpu_amd", "csrc", f)).read()
@@ -94,7 +88,7 @@ def test_switch_table_matches_the_library_and_the_switch_tests():
     assert read == documented, (sorted(read - documented), sorted(documented - read))
     assert len(documented) <= 20
     tests = ""
-    for f in ("test_switches_gpu.py", "test_parity_gpu.py", "test_schedule_check.py", "conftest.py"):
+    for f in ("test_switches_gpu.py", "test_parity_gpu.py", "test_schedule_check.py", "conftest.py", "gpu_support.py"):
         tests += open(os.path.join(ROOT, "tests", f)).read()
     missing = [s for s in documented if s not in tests]
     assert not missing, missing

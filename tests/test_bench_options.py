@@ -9,11 +9,8 @@ import sys
 import numpy as np
 import pytest
 
-from test_dist_gloo import free_port
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench  # noqa: E402
+import bench
+from gpu_support import ROOT, free_port
 
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype")
 FULL_ONLY = ("step_times_ms", "hbm_copy_gbps_same_run", "single_gpu", "speedup", "roofline", "roofline_cache_resident",

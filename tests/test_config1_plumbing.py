@@ -9,28 +9,11 @@ import os
 
 import numpy as np
 
-import oracle_lib as O
 import ref_writer
 from fluidsolvergpu_amd import vtk as sfvtk
+from ref_support import frame_args, run_config1
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-N, K, DT, DIFF, VISC = 32, 10, 0.1, 1e-4, 1e-4
-
-
-def run_config1():
-    z = lambda: np.zeros((N + 2,) * 3, np.float32)
-    f = {n: z() for n in ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")}
-    c = N // 2
-    f["dens0"][c, c, c] = 100.0
-    f["v0"][c, c, c] = 5.0
-    O.step(N, f, np.float32(DT), np.float32(DIFF), np.float32(VISC), K)
-    dens = np.ascontiguousarray(f["dens"][1:-1, 1:-1, 1:-1]).ravel()
-    vel = np.stack([f["u"][1:-1, 1:-1, 1:-1], f["v"][1:-1, 1:-1, 1:-1], f["w"][1:-1, 1:-1, 1:-1]], -1).ravel()
-    return f, dens, vel
-
-
-def frame_args(path, ub, dens, vel):
-    return (path, ub, [N + 1] * 3, 2, [1, 3], [0, 0], ["density", "velocity"], [dens, vel])
 
 
 def test_config1_frame_matches_golden(tmp_path):

@@ -3,25 +3,21 @@ the enum and the struct agree between include/sfgpu.h and the ctypes mirror, and
 touches the device. No GPU needed."""
 import ctypes as C
 import os
-import re
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_header import ROOT, declared_functions, enum_values, header_text, struct_members
+
 SYMBOLS = ("sf_reduce", "sf_diagnostics_get")
 OPS = {"SF_RED_SUM": 0, "SF_RED_SUM_SQ": 1, "SF_RED_MIN": 2, "SF_RED_MAX": 3, "SF_RED_MAX_ABS": 4,
        "SF_RED_COUNT_NONFINITE": 5}
 DOUBLES = ["mass", "dens_min", "dens_max", "kinetic", "max_speed", "max_div", "cfl_x", "cfl_y", "cfl_z", "cfl"]
 
 
-def header():
-    return open(os.path.join(ROOT, "include", "sfgpu.h")).read()
-
-
 def test_symbols_declared_exported_and_wrapped():
     from fluidsolvergpu_amd import solver
 
     for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header()), f"sfgpu.h does not declare {name}"
+        assert name in declared_functions("sfgpu.h"), f"sfgpu.h does not declare {name}"
         assert name in solver.ABI_SYMBOLS
         assert hasattr(solver.lib, name), f"libsfgpu.so does not export {name}"
     for method in ("reduce", "diagnostics"):
@@ -31,9 +27,7 @@ def test_symbols_declared_exported_and_wrapped():
 def test_enum_values():
     from fluidsolvergpu_amd import solver
 
-    m = re.search(r"enum\s+sf_reduce_op\s*\{([^}]*)\}", header())
-    assert m, "sfgpu.h does not declare enum sf_reduce_op"
-    assert {k: int(v) for k, v in re.findall(r"(SF_RED_\w+)\s*=\s*(\d+)", m.group(1))} == OPS
+    assert {k: int(v) for k, v in enum_values(header_text(), "sf_reduce_op").items()} == OPS
     for name, value in OPS.items():
         assert getattr(solver, name) == value
     assert sorted(solver.REDUCE_OPS.values()) == list(range(6))
@@ -42,15 +36,7 @@ def test_enum_values():
 def test_struct_layout_matches_the_header():
     from fluidsolvergpu_amd import solver
 
-    m = re.search(r"typedef\s+struct\s+sf_diagnostics\s*\{([^}]*)\}\s*sf_diagnostics\s*;", header())
-    assert m, "sfgpu.h does not declare struct sf_diagnostics"
-    members = []
-    for decl in m.group(1).split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        ctype = "long long" if decl.startswith("long long ") else decl.split(" ")[0]
-        members += [(n.strip(), ctype) for n in decl[len(ctype):].split(",")]
+    members = struct_members(header_text(), "sf_diagnostics")
     assert members == [(n, "double") for n in DOUBLES] + [("nonfinite", "long long")]
     want = {"double": C.c_double, "long long": C.c_longlong}
     assert [(n, t) for n, t in solver.SfDiagnostics._fields_] == [(n, want[t]) for n, t in members]

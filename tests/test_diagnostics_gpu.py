@@ -10,52 +10,10 @@ import pytest
 
 import diagnostics_ref as D
 import oracle_lib as O
-from test_maccormack_gpu import OPERATOR_CASES
+from gpu_support import (DT, DTYPES, OPERATOR_CASES, OPERATOR_IDS, ROOT, STATE, S, assert_same_bits, check_diag,
+                         check_reduce, make)
 
 pytestmark = pytest.mark.gpu
-
-DT, DIFF, VISC = 0.1, 1e-4, 1e-4
-DTYPES = [np.float32, np.float64]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STATE = ("u", "v", "w", "dens")
-CASE_IDS = [f"N{n}-P{p}-{t}" for n, p, t in OPERATOR_CASES]
-
-
-def S():
-    from fluidsolvergpu_amd import solver
-
-    return solver
-
-
-def make(N, dtype, K=4, P=1, transport="copy"):
-    kw = {}
-    if P > 1:
-        kw["nslabs_local"] = P
-        if transport == "rccl-self":
-            kw["flags"] = S().SF_FLAG_RCCL_SELF
-    return S().FluidSolver(N, dtype="f32" if dtype == np.float32 else "f64", iters=K, dt=DT, diff=DIFF, visc=VISC, **kw)
-
-
-def same_field(got, want, what):
-    uint = np.uint32 if got.dtype == np.float32 else np.uint64
-    assert np.array_equal(got.view(uint), want.view(uint)), f"{what}: fields differ"
-
-
-def check_reduce(fs, slot, x, what):
-    for op in D.OPS:
-        got, want = fs.reduce(op, slot), D.reduce(op, x)
-        print(f"{what} {op}: got {got!r} want {want!r}")
-        assert D.bits(got) == D.bits(want), f"{what}: {op}: got {got!r} want {want!r}"
-
-
-def check_diag(fs, f, what):
-    got, want = fs.diagnostics(), D.diagnostics(f["u"], f["v"], f["w"], f["dens"], DT)
-    print(f"{what}: {got}")
-    assert set(got) == set(want)
-    for name in want:
-        assert D.bits(got[name]) == D.bits(want[name]), f"{what}: {name}: got {got[name]!r} want {want[name]!r}"
-    assert isinstance(got["nonfinite"], int)
-    return got
 
 
 def random_state(N, dtype, seed):
@@ -66,7 +24,7 @@ def random_state(N, dtype, seed):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
-@pytest.mark.parametrize("N,P,transport", OPERATOR_CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("N,P,transport", OPERATOR_CASES, ids=OPERATOR_IDS)
 def test_every_op_and_the_struct_match_the_reference(N, P, transport, dtype):
     rng = np.random.RandomState(300 + N + P)
     x = (rng.standard_normal((N + 2,) * 3) * 10.0 ** rng.randint(-2, 3, (N + 2,) * 3)).astype(dtype)
@@ -79,9 +37,9 @@ def test_every_op_and_the_struct_match_the_reference(N, P, transport, dtype):
         check_reduce(fs, "user1", x, f"N={N} P={P} {transport}")
         check_reduce(fs, "user2", np.zeros_like(x), "unallocated slot")  # allocated on first use: zeros
         check_diag(fs, f, f"N={N} P={P} {transport}")
-        same_field(fs.download("user1"), x, "user1 after the calls")
+        assert_same_bits(fs.download("user1"), x, "user1 after the calls")
         for n in STATE:
-            same_field(fs.download(n), f[n], f"{n} after the calls")
+            assert_same_bits(fs.download(n), f[n], f"{n} after the calls")
         if transport == "rccl-self":  # one collective per call went through the communicator
             assert fs.transport_info()["rccl_groups"] - g0 == 2 * len(D.OPS) + 1
         else:
@@ -187,7 +145,7 @@ def test_calls_do_not_change_a_later_step(P, transport):
             fs.sync()
             out.append({n: fs.download(n) for n in S().FIELD_NAMES})
     for n in S().FIELD_NAMES:
-        same_field(out[1][n], out[0][n], f"{n} with and without diagnostics calls")
+        assert_same_bits(out[1][n], out[0][n], f"{n} with and without diagnostics calls")
 
 
 def read_frame(path, N):

@@ -6,10 +6,9 @@ import numpy as np
 import pytest
 
 import diagnostics_ref as D
+from shape_cases import DT, DTYPES
 
-DTYPES = [np.float32, np.float64]
 SIZES = [1, 2, 5, 17, 64, 70]  # tails, non-multiples of W, non-powers of two, more than one vector per lane (70: fp64)
-DT = 0.1
 
 
 def divisors(N):

@@ -1,21 +1,14 @@
 """N > 1 host path on CPU: world_size 2 (and 4) over gloo, launched exactly like bench.py is
 (`python -m torch.distributed.run`, rendezvous on 127.0.0.1)."""
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
+from gpu_support import free_port
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 @pytest.mark.parametrize("world,N,K,dtype", [(2, 8, 3, "f32"), (2, 6, 2, "f64"), (4, 8, 2, "f32")])

@@ -2,19 +2,18 @@
 driver takes the four new options before it touches the device. No GPU needed."""
 import ctypes as C
 import os
-import re
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_header import ROOT, declared_functions
+
 FORCE_SYMBOLS = ("sf_set_vorticity_confinement", "sf_set_buoyancy", "sf_vorticity_magnitude", "sf_add_forces")
 
 
 def test_force_symbols_declared_exported_and_wrapped():
     from fluidsolvergpu_amd import solver
 
-    header = open(os.path.join(ROOT, "include", "sfgpu.h")).read()
     for name in FORCE_SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), f"sfgpu.h does not declare {name}"
+        assert name in declared_functions("sfgpu.h"), f"sfgpu.h does not declare {name}"
         assert name in solver.ABI_SYMBOLS
         assert hasattr(solver.lib, name), f"libsfgpu.so does not export {name}"
     for method in ("set_vorticity_confinement", "set_buoyancy", "vorticity_magnitude", "add_forces"):

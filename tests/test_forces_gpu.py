@@ -9,67 +9,15 @@ import pytest
 
 import forces_ref as F
 import oracle_lib as O
+from gpu_support import (DIFF, DT, DTYPES, NAMES, OPERATOR_CASES, OPERATOR_IDS, ROOT, USER, VISC, S, assert_same_bits,
+                         bench_state, check_all, make, random_fields, set_forces, upload_all)
 
 pytestmark = pytest.mark.gpu
 
-DT, DIFF, VISC = 0.1, 1e-4, 1e-4
-NAMES = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
-USER = {"u0": "user0", "v0": "user1", "w0": "user2", "dens0": "user3"}
-DTYPES = [np.float32, np.float64]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def S():
-    from fluidsolvergpu_amd import solver
-
-    return solver
-
-
-def make(N, dtype, K=4, P=1, transport="copy", **kw):
-    if P > 1:
-        kw["nslabs_local"] = P
-        if transport == "rccl-self":
-            kw["flags"] = S().SF_FLAG_RCCL_SELF
-    return S().FluidSolver(N, dtype="f32" if dtype == np.float32 else "f64", iters=K, dt=DT, diff=DIFF, visc=VISC,
-                           **kw)
-
-
-def assert_same(got, want, what):
-    """Exact equality of the bits (the sign of a zero and NaN payloads included)."""
-    uint = np.uint32 if got.dtype == np.float32 else np.uint64
-    bad = np.argwhere(got.view(uint) != want.view(uint))
-    if len(bad):
-        raise AssertionError(f"{what}: {len(bad)} entries differ, first at {bad[0]}: got {got[tuple(bad[0])]!r} "
-                             f"want {want[tuple(bad[0])]!r}")
-
-
-def random_fields(N, dtype, seed, vel=0.05):
-    """Random state whose back-traces stay within one plane (|dt*N*w| < 1) for the decomposed contexts."""
-    rng = np.random.RandomState(seed)
-    f = {n: (0.2 * rng.standard_normal((N + 2,) * 3)).astype(dtype) for n in NAMES}
-    for n in ("u", "v", "w"):
-        f[n] = (vel * rng.standard_normal((N + 2,) * 3)).astype(dtype)
-    return f
-
-
-def upload_all(fs, f):
-    for n, a in f.items():
-        fs.upload(n, a)
-
-
-def check_all(fs, want, what, names=NAMES):
-    fs.sync()
-    for n in names:
-        assert_same(fs.download(n), want[n], f"{what}: {n}")
-
 
 # ---- the two passes singly -------------------------------------------------------------------------------------
-OPERATOR_CASES = [(17, 1, "copy"), (40, 1, "copy"), (40, 2, "copy"), (40, 4, "rccl-self"), (40, 5, "copy"),
-                  (64, 1, "copy"), (64, 2, "rccl-self"), (64, 4, "copy")]
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
-@pytest.mark.parametrize("N,P,transport", OPERATOR_CASES, ids=[f"N{n}-P{p}-{t}" for n, p, t in OPERATOR_CASES])
+@pytest.mark.parametrize("N,P,transport", OPERATOR_CASES, ids=OPERATOR_IDS)
 def test_operators_match_reference(N, P, transport, dtype):
     f = random_fields(N, dtype, 11 + N + P, vel=1.0)
     eps, beta, amb, axis = 0.35, 1.7, 0.1, 2
@@ -92,11 +40,6 @@ def test_operators_match_reference(N, P, transport, dtype):
 # ---- full steps --------------------------------------------------------------------------------------------------
 FORCES = {"vort": dict(eps=0.3), "buoy": dict(beta=2.0, ambient=0.05, axis=1), "both": dict(eps=0.3, beta=-1.5,
                                                                                                ambient=0.0, axis=2)}
-
-
-def set_forces(fs, eps=0.0, beta=0.0, ambient=0.0, axis=1):
-    fs.set_vorticity_confinement(eps)
-    fs.set_buoyancy(beta, ambient, axis)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
@@ -123,7 +66,7 @@ def test_steps_match_reference(mode, bound, P, dtype):
             check_all(fs, want, f"{mode} {'bound' if bound else 'unbound'} P={P} step {s}")
         if bound:
             for n, slot in USER.items():
-                assert_same(fs.download(slot), src[n], f"bound slot {slot} after the steps")
+                assert_same_bits(fs.download(slot), src[n], f"bound slot {slot} after the steps")
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
@@ -149,8 +92,6 @@ def test_forces_off_again_is_the_plain_step(dtype):
 def test_marching_path_256_with_forces():
     """256^3 fp32 K = 20 (the size classes above ~136^3 run the marching Jacobi kernel), SPEC §5 inputs with bound
     sources plus both forces: one step against the oracle."""
-    from test_full_size_gpu import bench_state
-
     N, K, dtype = 256, 20, np.float32
     forces = dict(eps=0.25, beta=0.8, ambient=0.5, axis=1)
     f, src = bench_state(N, dtype)
@@ -210,11 +151,11 @@ def test_closed_forms_through_the_abi(dtype, P):
             fs.add_forces("u", "v", "w", "dens", "u0", "v0", "w0")
             fs.sync()
             mag = fs.download("user0")
-            assert_same(mag, F.vorticity(u, v, w), f"{name}: |omega|")
+            assert_same_bits(mag, F.vorticity(u, v, w), f"{name}: |omega|")
             su, sv, sw = zero.copy(), zero.copy(), zero.copy()
             F.add_forces(u, v, w, zero, su, sv, sw, eps=eps)
             for n, ref in (("u0", su), ("v0", sv), ("w0", sw)):
-                assert_same(fs.download(n), ref, f"{name}: {n}")
+                assert_same_bits(fs.download(n), ref, f"{name}: {n}")
             if name == "shear":
                 assert np.array_equal(mag[1:-1, 1:-1, 1:-1], np.broadcast_to(2 * N * np.arange(1, N + 1), (N, N, N)))
                 assert not fs.download("u0").any() and not fs.download("w0").any()

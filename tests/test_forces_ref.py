@@ -4,8 +4,8 @@ import numpy as np
 import pytest
 
 import forces_ref as F
+from shape_cases import DTYPES
 
-DTYPES = [np.float32, np.float64]
 SIZES = [1, 2, 5, 17, 40]
 
 
@@ -15,7 +15,7 @@ def grid(N, dtype, fn):
     return np.asarray(fn(i, j, k), dtype=np.float64).astype(dtype) + np.zeros((N + 2,) * 3, dtype)
 
 
-def rand_fields(N, dtype, seed):
+def force_inputs(N, dtype, seed):
     rng = np.random.RandomState(seed)
     return [rng.standard_normal((N + 2,) * 3).astype(dtype) for _ in range(7)]
 
@@ -26,7 +26,7 @@ def test_uniform_velocity_gives_no_force(N, dtype):
     u = grid(N, dtype, lambda i, j, k: 0.75 + 0 * i)
     v = grid(N, dtype, lambda i, j, k: -1.5 + 0 * i)
     w = grid(N, dtype, lambda i, j, k: 3.0 + 0 * i)
-    _, _, _, dens, su, sv, sw = rand_fields(N, dtype, 1)
+    _, _, _, dens, su, sv, sw = force_inputs(N, dtype, 1)
     want = [a.copy() for a in (su, sv, sw)]
     F.add_forces(u, v, w, dens, su, sv, sw, eps=0.7)
     for got, ref in zip((su, sv, sw), want):
@@ -47,7 +47,7 @@ def test_rigid_rotation_gives_uniform_magnitude_and_no_force(N, dtype):
     for face in (mag[0, 1:-1, 1:-1], mag[-1, 1:-1, 1:-1], mag[1:-1, 0, 1:-1], mag[1:-1, -1, 1:-1],
                  mag[1:-1, 1:-1, 0], mag[1:-1, 1:-1, -1]):
         assert (face == dtype(2 * N)).all()
-    _, _, _, dens, su, sv, sw = rand_fields(N, dtype, 2)
+    _, _, _, dens, su, sv, sw = force_inputs(N, dtype, 2)
     want = [a.copy() for a in (su, sv, sw)]
     F.add_forces(u, v, w, dens, su, sv, sw, eps=0.4)
     for got, ref in zip((su, sv, sw), want):
@@ -86,7 +86,7 @@ def test_shear_profile_closed_form(N, dtype):
 def test_buoyancy_on_uniform_density_is_one_rounding(N, dtype, axis):
     beta, C, amb = 0.37, 3.5, 0.5  # C - amb is exact: beta * 3 rounds once
     dens = grid(N, dtype, lambda i, j, k: C + 0 * i)
-    u, v, w, _, su, sv, sw = rand_fields(N, dtype, 3)
+    u, v, w, _, su, sv, sw = force_inputs(N, dtype, 3)
     for a in (su, sv, sw):
         a[1:-1, 1:-1, 1:-1] = 0
     zeroed = [a.copy() for a in (su, sv, sw)]
@@ -103,7 +103,7 @@ def test_buoyancy_on_uniform_density_is_one_rounding(N, dtype, axis):
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
 def test_zero_coefficients_evaluate_nothing(dtype):
     N = 5
-    u, v, w, dens, su, sv, sw = rand_fields(N, dtype, 4)
+    u, v, w, dens, su, sv, sw = force_inputs(N, dtype, 4)
     sv[2, 2, 2] = -0.0
     u[1, 1, 1] = np.nan
     want = [a.copy() for a in (su, sv, sw)]
@@ -150,7 +150,7 @@ def scalar_force(u, v, w, dens, s, k, j, i, eps, beta, amb, axis):
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
 def test_vectorised_reference_equals_scalar_evaluation(dtype):
     N, eps, beta, amb, axis = 17, 0.45, -1.3, 0.2, 2
-    u, v, w, dens, su, sv, sw = rand_fields(N, dtype, 5)
+    u, v, w, dens, su, sv, sw = force_inputs(N, dtype, 5)
     src = [a.copy() for a in (su, sv, sw)]
     F.add_forces(u, v, w, dens, su, sv, sw, eps=eps, beta=beta, ambient=amb, axis=axis)
     rng = np.random.RandomState(6)

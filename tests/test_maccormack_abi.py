@@ -1,27 +1,23 @@
 """CPU side of MacCormack advection (docs/SPEC.md §9): the two entry points are declared, exported and wrapped, and the
 driver takes --maccormack before it touches the device. No GPU needed."""
 import os
-import re
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_header import ROOT, declared_functions, enum_values, header_text
+
 SYMBOLS = ("sf_set_advection", "sf_advect_maccormack")
 
 
 def test_symbols_declared_exported_and_wrapped():
     from fluidsolvergpu_amd import solver
 
-    header = open(os.path.join(ROOT, "include", "sfgpu.h")).read()
     for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), f"sfgpu.h does not declare {name}"
+        assert name in declared_functions("sfgpu.h"), f"sfgpu.h does not declare {name}"
         assert name in solver.ABI_SYMBOLS
         assert hasattr(solver.lib, name), f"libsfgpu.so does not export {name}"
     for method in ("set_advection", "advect_maccormack"):
         assert callable(getattr(solver.FluidSolver, method))
-    m = re.search(r"enum\s+sf_advection\s*\{([^}]*)\}", header)
-    assert m, "sfgpu.h does not declare enum sf_advection"
-    values = dict(re.findall(r"(SF_ADVECT_\w+)\s*=\s*(\d+)", m.group(1)))
-    assert values == {"SF_ADVECT_SEMI_LAGRANGIAN": "0", "SF_ADVECT_MACCORMACK": "1"}
+    assert enum_values(header_text(), "sf_advection") == {"SF_ADVECT_SEMI_LAGRANGIAN": "0", "SF_ADVECT_MACCORMACK": "1"}
     assert (solver.SF_ADVECT_SEMI_LAGRANGIAN, solver.SF_ADVECT_MACCORMACK) == (0, 1)
 
 

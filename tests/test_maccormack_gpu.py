@@ -9,70 +9,18 @@ import pytest
 
 import maccormack_ref as M
 import oracle_lib as O
+from gpu_support import (DIFF, DT, DTYPES, NAMES, OPERATOR_CASES, OPERATOR_IDS, ROOT, USER, VISC, S, assert_same_bits,
+                         bench_state, check_all, make, random_fields, upload_all)
 
 pytestmark = pytest.mark.gpu
 
-DT, DIFF, VISC = 0.1, 1e-4, 1e-4
-NAMES = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
-USER = {"u0": "user0", "v0": "user1", "w0": "user2", "dens0": "user3"}
-DTYPES = [np.float32, np.float64]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SL, MC = M.SEMI_LAGRANGIAN, M.MACCORMACK
 SCHEMES = {"vel": (MC, SL), "dens": (SL, MC), "both": (MC, MC)}
 
 
-def S():
-    from fluidsolvergpu_amd import solver
-
-    return solver
-
-
-def make(N, dtype, K=4, P=1, transport="copy", **kw):
-    if P > 1:
-        kw["nslabs_local"] = P
-        if transport == "rccl-self":
-            kw["flags"] = S().SF_FLAG_RCCL_SELF
-    return S().FluidSolver(N, dtype="f32" if dtype == np.float32 else "f64", iters=K, dt=DT, diff=DIFF, visc=VISC,
-                           **kw)
-
-
-def assert_same(got, want, what):
-    """Exact equality of the bits (the sign of a zero and NaN payloads included)."""
-    uint = np.uint32 if got.dtype == np.float32 else np.uint64
-    bad = np.argwhere(got.view(uint) != want.view(uint))
-    if len(bad):
-        raise AssertionError(f"{what}: {len(bad)} entries differ, first at {bad[0]}: got {got[tuple(bad[0])]!r} "
-                             f"want {want[tuple(bad[0])]!r}")
-
-
-def random_fields(N, dtype, seed, vel=0.05):
-    """Random state whose traces stay within one plane (|dt*N*w| < 1) for the decomposed contexts."""
-    rng = np.random.RandomState(seed)
-    f = {n: (0.2 * rng.standard_normal((N + 2,) * 3)).astype(dtype) for n in NAMES}
-    for n in ("u", "v", "w"):
-        f[n] = (vel * rng.standard_normal((N + 2,) * 3)).astype(dtype)
-    return f
-
-
-def upload_all(fs, f):
-    for n, a in f.items():
-        fs.upload(n, a)
-
-
-def check_all(fs, want, what, names=NAMES):
-    fs.sync()
-    for n in names:
-        assert_same(fs.download(n), want[n], f"{what}: {n}")
-
-
 # ---- the operator singly -----------------------------------------------------------------------------------------
-# (the case table of test_forces_gpu.py)
-OPERATOR_CASES = [(17, 1, "copy"), (40, 1, "copy"), (40, 2, "copy"), (40, 4, "rccl-self"), (40, 5, "copy"),
-                  (64, 1, "copy"), (64, 2, "rccl-self"), (64, 4, "copy")]
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
-@pytest.mark.parametrize("N,P,transport", OPERATOR_CASES, ids=[f"N{n}-P{p}-{t}" for n, p, t in OPERATOR_CASES])
+@pytest.mark.parametrize("N,P,transport", OPERATOR_CASES, ids=OPERATOR_IDS)
 def test_operator_matches_reference(N, P, transport, dtype):
     """b = 0..3 on random fields; u and v trace over several cells, |dt*N*w| < 1 (one ghost plane)."""
     rng = np.random.RandomState(100 + N + P)
@@ -88,9 +36,9 @@ def test_operator_matches_reference(N, P, transport, dtype):
             fs.advect_maccormack(b, "dens", "dens0", "u", "v", "w")
             fs.sync()
             want = M.advect_mc(b, np.zeros_like(d0), d0, u, v, w, DT)
-            assert_same(fs.download("dens"), want, f"N={N} P={P} {transport} b={b}")
+            assert_same_bits(fs.download("dens"), want, f"N={N} P={P} {transport} b={b}")
         for n, a in (("dens0", d0), ("u", u), ("v", v), ("w", w)):
-            assert_same(fs.download(n), a, f"input {n} after the operator")
+            assert_same_bits(fs.download(n), a, f"input {n} after the operator")
         if transport == "rccl-self":
             assert fs.transport_info()["rccl_groups"] > 0
 
@@ -113,7 +61,7 @@ def test_operator_takes_every_branch(N, sigma, dtype):
         for b in range(4):
             fs.advect_maccormack(b, "user1", "user0", "u0", "v0", "w0")
             fs.sync()
-            assert_same(fs.download("user1"), M.advect_mc(b, np.zeros_like(d0), d0, u, v, w, DT), f"b={b}")
+            assert_same_bits(fs.download("user1"), M.advect_mc(b, np.zeros_like(d0), d0, u, v, w, DT), f"b={b}")
 
 
 # ---- full steps --------------------------------------------------------------------------------------------------
@@ -148,7 +96,7 @@ def test_steps_match_reference(mode, P, bound, dtype):
         run_steps(fs, want, K, steps, f"{mode} P={P}", src if bound else None, SCHEMES[mode])
         if bound:
             for n, slot in USER.items():
-                assert_same(fs.download(slot), src[n], f"bound slot {slot} after the steps")
+                assert_same_bits(fs.download(slot), src[n], f"bound slot {slot} after the steps")
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
@@ -176,8 +124,6 @@ _REF_256 = {}
 
 def reference_256(dtype):
     """One step of the SPEC §5 inputs at 256^3, K = 20, both schemes on (computed once per precision)."""
-    from test_full_size_gpu import bench_state
-
     key = np.dtype(dtype).name
     if key not in _REF_256:
         N = 256
@@ -229,7 +175,7 @@ def test_graph_replay_tracks_the_schemes(monkeypatch):
                 fs.sync()
             M.step(want, DT, DIFF, VISC, K, velocity=schemes[0], density=schemes[1])
             for n in NAMES:
-                assert_same(graphed.download(n), plain.download(n), f"SF_GRAPH=1 step {s} {schemes}: {n} vs plain")
+                assert_same_bits(graphed.download(n), plain.download(n), f"SF_GRAPH=1 step {s} {schemes}: {n} vs plain")
             check_all(graphed, want, f"SF_GRAPH=1 step {s} {schemes}")
 
 

@@ -6,8 +6,8 @@ import pytest
 
 import maccormack_ref as M
 import oracle_lib as O
+from gpu_support import DTYPES, NAMES
 
-DTYPES = [np.float32, np.float64]
 I = M.I
 
 
@@ -183,7 +183,6 @@ def test_translating_bump_keeps_its_shape(dtype):
 
 
 # ---- step() ------------------------------------------------------------------------------------------------------
-NAMES = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
 
 
 def fields(N, dtype, seed):

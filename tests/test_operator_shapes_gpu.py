@@ -5,81 +5,23 @@ MacCormack kernels, traces of several cells that vary along a row, and the speci
 zeros, ties) the SPEC's select forms exist for. tests/test_shape_inputs_ref.py shows on the CPU that these inputs tell
 a subtly wrong kernel from a right one.
 
-Every comparison is exact bit equality against the numpy references (maccormack_ref, forces_ref, diagnostics_ref).
-Where an input holds NaN: the same entries NaN, every other entry the same bits (NaN payloads are not compared).
+Every comparison is exact bit equality (gpu_support.assert_same_bits) against the numpy references (maccormack_ref,
+forces_ref, diagnostics_ref). Where an input holds NaN (nan_ok): the same entries NaN, every other entry the same bits.
 References are computed once per (N, precision) and reused across the forms."""
 import numpy as np
 import pytest
 
-import diagnostics_ref as D
 import forces_ref as F
 import maccormack_ref as M
 import oracle_lib as O
 import shape_cases as C
+from gpu_support import (DIFF, DT, NAMES, STATE, USER, VISC, Cache, advect_form, assert_same_bits, check_diag,  # noqa: F401
+                         check_reduce, make, set_forces)  # (advect_form: a fixture, parametrised indirectly below)
 
 pytestmark = pytest.mark.gpu
 
-DT, DIFF, VISC = C.DT, 1e-4, 1e-4
-NAMES = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
-USER = {"u0": "user0", "v0": "user1", "w0": "user2", "dens0": "user3"}
-STATE = ("u", "v", "w", "dens")
 SL, MC = M.SEMI_LAGRANGIAN, M.MACCORMACK
 FORMS = ["default", "gather", "row", "pairs"]
-
-
-def S():
-    from fluidsolvergpu_amd import solver
-
-    return solver
-
-
-def make(N, dtype, K=4, P=1, transport="copy"):
-    kw = {}
-    if P > 1:
-        kw["nslabs_local"] = P
-        if transport == "rccl-self":
-            kw["flags"] = S().SF_FLAG_RCCL_SELF
-    return S().FluidSolver(N, dtype=C.dname(dtype), iters=K, dt=DT, diff=DIFF, visc=VISC, **kw)
-
-
-def assert_same(got, want, what, nan_ok=False):
-    """Exact equality of the bits, the sign of a zero included. nan_ok: NaN in the same entries, payloads not compared."""
-    uint = np.uint32 if got.dtype == np.float32 else np.uint64
-    differ = got.view(uint) != want.view(uint)
-    if nan_ok:
-        differ &= ~(np.isnan(got) & np.isnan(want))
-    bad = np.argwhere(differ)
-    if len(bad):
-        raise AssertionError(f"{what}: {len(bad)} entries differ, first at [k,j,i]={bad[0]}: got "
-                             f"{got[tuple(bad[0])]!r} want {want[tuple(bad[0])]!r}")
-
-
-@pytest.fixture
-def advect_form(request, monkeypatch):
-    """The cell-to-lane form of advect and of the MacCormack second pass (SF_ADVECT_ROW, read when a context is created):
-    unset = the default (one cell per lane for the three velocity components — neighbour-lane samples in fp32, own pair
-    loads in fp64 — and the gather form for one field), 0 = always the gather form, 2 = always neighbour-lane samples,
-    3 = always own pair loads. So every form sees every size and both precisions, for one field and for three."""
-    form = request.param
-    if form != "default":
-        monkeypatch.setenv("SF_ADVECT_ROW", {"gather": "0", "row": "2", "pairs": "3"}[form])
-    else:
-        monkeypatch.delenv("SF_ADVECT_ROW", raising=False)
-    return form
-
-
-class Cache:
-    """References keyed by case, a few kept (the cases of one key run one after another)."""
-
-    def __init__(self, keep=2):
-        self.keep, self.items = keep, {}
-
-    def get(self, key, build):
-        if key not in self.items:
-            while len(self.items) >= self.keep:
-                self.items.pop(next(iter(self.items)))
-            self.items[key] = build()
-        return self.items[key]
 
 
 # ---- §9: the operator in every form ------------------------------------------------------------------------------
@@ -104,16 +46,16 @@ def run_operator(fs, d0, u, v, w, want, what, nan_ok=False):
         fs.upload("dens", np.full(d0.shape, 7.0, d0.dtype))
         fs.advect_maccormack(b, "dens", "dens0", "u", "v", "w")
         fs.sync()
-        assert_same(fs.download("dens"), want[b], f"{what} b={b}", nan_ok)
+        assert_same_bits(fs.download("dens"), want[b], f"{what} b={b}", nan_ok)
     for n, a in (("dens0", d0), ("u", u), ("v", v), ("w", w)):
-        assert_same(fs.download(n), a, f"{what}: input {n} after the operator", nan_ok)
+        assert_same_bits(fs.download(n), a, f"{what}: input {n} after the operator", nan_ok)
 
 
-OPERATOR_CASES = [(N, t, form) for N, t in C.SHAPES for form in FORMS]
+MC_OPERATOR_CASES = [(N, t, form) for N, t in C.SHAPES for form in FORMS]
 
 
-@pytest.mark.parametrize("N,dtype,advect_form", OPERATOR_CASES, indirect=["advect_form"],
-                         ids=[f"N{N}-{C.dname(t)}-{f}" for N, t, f in OPERATOR_CASES])
+@pytest.mark.parametrize("N,dtype,advect_form", MC_OPERATOR_CASES, indirect=["advect_form"],
+                         ids=[f"N{N}-{C.dname(t)}-{f}" for N, t, f in MC_OPERATOR_CASES])
 def test_maccormack_operator(N, dtype, advect_form):
     """sf_advect_maccormack, b = 0..3, on mixed_flow (traces of up to 2.5 cells, a share of neighbouring cells landing
     in neighbouring cells and a share not, all three outcomes of §9) at P = 1."""
@@ -200,7 +142,7 @@ def test_vel_step_maccormack_long_traces(N, dtype, forces, advect_form):
             fs.dens_step()
             fs.sync()
             for n in NAMES:
-                assert_same(fs.download(n), after[s][n], f"N={N} {advect_form} step {s}: {n}")
+                assert_same_bits(fs.download(n), after[s][n], f"N={N} {advect_form} step {s}: {n}")
 
 
 # ---- §9: special values ------------------------------------------------------------------------------------------
@@ -242,11 +184,6 @@ FORCE_MODES = {"vort": dict(eps=0.35), "buoy": dict(beta=1.7, ambient=0.1, axis=
                "both": dict(eps=0.35, beta=1.7, ambient=0.1, axis=2)}
 
 
-def set_forces(fs, eps=0.0, beta=0.0, ambient=0.0, axis=1):
-    fs.set_vorticity_confinement(eps)
-    fs.set_buoyancy(beta, ambient, axis)
-
-
 def run_force_operators(fs, f, what, nan_ok=False, modes=FORCE_MODES):
     N = f["u"].shape[0] - 2
     for n, a in f.items():
@@ -254,7 +191,7 @@ def run_force_operators(fs, f, what, nan_ok=False, modes=FORCE_MODES):
     fs.upload("user0", np.full((N + 2,) * 3, 7.0, f["u"].dtype))
     fs.vorticity_magnitude("u", "v", "w", "user0")
     fs.sync()
-    assert_same(fs.download("user0"), F.vorticity(f["u"], f["v"], f["w"]), f"{what}: |omega|", nan_ok)
+    assert_same_bits(fs.download("user0"), F.vorticity(f["u"], f["v"], f["w"]), f"{what}: |omega|", nan_ok)
     for mode, coef in modes.items():
         want = {n: a.copy() for n, a in f.items()}
         with np.errstate(all="ignore"):
@@ -265,7 +202,7 @@ def run_force_operators(fs, f, what, nan_ok=False, modes=FORCE_MODES):
         fs.add_forces("u", "v", "w", "dens", "u0", "v0", "w0")
         fs.sync()
         for n in NAMES:
-            assert_same(fs.download(n), want[n], f"{what} {mode}: {n}", nan_ok)
+            assert_same_bits(fs.download(n), want[n], f"{what} {mode}: {n}", nan_ok)
 
 
 @pytest.mark.parametrize("N,dtype", C.SHAPES, ids=[f"N{N}-{C.dname(t)}" for N, t in C.SHAPES])
@@ -292,9 +229,9 @@ def test_forces(N, dtype):
             fs.dens_step()
             fs.sync()
             for n in NAMES:
-                assert_same(fs.download(n), want[n], f"N={N} bound {mode}: {n}")
+                assert_same_bits(fs.download(n), want[n], f"N={N} bound {mode}: {n}")
             for n, slot in USER.items():
-                assert_same(fs.download(slot), src[n], f"N={N} bound {mode}: slot {slot}")
+                assert_same_bits(fs.download(slot), src[n], f"N={N} bound {mode}: slot {slot}")
 
 
 @pytest.mark.parametrize("dtype", C.DTYPES, ids=["f32", "f64"])
@@ -320,7 +257,7 @@ def test_zero_coefficients_evaluate_nothing(N, dtype):
         fs.add_forces("u", "v", "w", "dens", "u0", "v0", "w0")
         fs.sync()
         for n in ("u0", "w0"):  # the NaN velocity reached nothing, the -0 sources kept their sign
-            assert_same(fs.download(n), f[n], f"N={N} eps=0: {n}")
+            assert_same_bits(fs.download(n), f[n], f"N={N} eps=0: {n}")
         assert np.isnan(fs.download("v0")).sum() == 1  # dens[1, N, 1] through the buoyancy, nothing else
 
 
@@ -347,11 +284,11 @@ def test_force_closed_forms_on_the_smallest_grids(N, dtype):
             fs.sync()
             mag = fs.download("user0")
             got = [fs.download(n) for n in ("u0", "v0", "w0")]
-            assert_same(mag, F.vorticity(u, v, w), f"{name}: |omega|")
+            assert_same_bits(mag, F.vorticity(u, v, w), f"{name}: |omega|")
             ref = [zero.copy(), zero.copy(), zero.copy()]
             F.add_forces(u, v, w, zero, *ref, eps=eps)
             for a, r, n in zip(got, ref, "uvw"):
-                assert_same(a, r, f"{name}: source of {n}")
+                assert_same_bits(a, r, f"{name}: source of {n}")
             if name == "rotation":
                 assert (mag[inner] == 2 * N).all()
                 assert not any(a.any() for a in got)
@@ -366,21 +303,6 @@ def test_force_closed_forms_on_the_smallest_grids(N, dtype):
 
 
 # ---- §10 ---------------------------------------------------------------------------------------------------------
-def check_reduce(fs, slot, x, what):
-    for op in D.OPS:
-        got, want = fs.reduce(op, slot), D.reduce(op, x)
-        print(f"{what} {op}: got {got!r} want {want!r}")
-        assert D.bits(got) == D.bits(want), f"{what}: {op}: got {got!r} want {want!r}"
-
-
-def check_diag(fs, f, what):
-    got, want = fs.diagnostics(), D.diagnostics(f["u"], f["v"], f["w"], f["dens"], DT)
-    print(f"{what}: {got}")
-    assert set(got) == set(want)
-    for name in want:
-        assert D.bits(got[name]) == D.bits(want[name]), f"{what}: {name}: got {got[name]!r} want {want[name]!r}"
-
-
 def reduction_inputs(N, dtype):
     """(x, state), plain and through special_values: magnitudes over five decades; the state's velocities scaled to a
     CFL of a few cells."""
@@ -399,9 +321,9 @@ def run_reductions(fs, N, dtype, what):
             fs.upload(n, f[n])
         check_reduce(fs, "user1", x, f"{what} {kind}")
         check_diag(fs, f, f"{what} {kind}")
-        assert_same(fs.download("user1"), x, f"{what} {kind}: user1 after the calls", nan_ok=True)
+        assert_same_bits(fs.download("user1"), x, f"{what} {kind}: user1 after the calls", nan_ok=True)
         for n in STATE:
-            assert_same(fs.download(n), f[n], f"{what} {kind}: {n} after the calls", nan_ok=True)
+            assert_same_bits(fs.download(n), f[n], f"{what} {kind}: {n} after the calls", nan_ok=True)
 
 
 @pytest.mark.parametrize("N,dtype", C.REDUCE_SHAPES, ids=[f"N{N}-{C.dname(t)}" for N, t in C.REDUCE_SHAPES])

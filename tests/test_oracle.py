@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from shape_cases import DT
 
-DT = 0.1
 
 
 # ---------------------------------------------------------------------------------- numpy restatement

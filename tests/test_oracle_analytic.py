@@ -27,19 +27,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-
-LD = np.longdouble
-DTYPES = [np.float32, np.float64]
-
-
-def modes(N, m):
-    i = np.arange(N + 2, dtype=LD)
-    th = LD(np.pi) * LD(m) * (i - LD(0.5)) / LD(N)
-    return np.cos(th), np.sin(th)
-
-
-def product(fk, fj, fi):
-    return fk[:, None, None] * fj[None, :, None] * fi[None, None, :]
+from ref_support import LD, modes, product, tol
+from shape_cases import DTYPES
 
 
 def jacobi_amplitude(A, B, a, c, lam, K):
@@ -47,10 +36,6 @@ def jacobi_amplitude(A, B, a, c, lam, K):
     for _ in range(K):
         A = (B + a * lam * A) / c
     return A
-
-
-def tol(dtype, K, scale):
-    return 16.0 * (K + 2) * float(np.finfo(dtype).eps) * float(scale)
 
 
 CASES = [(8, (1, 0, 0), 3), (8, (2, 3, 1), 5), (16, (0, 0, 0), 4), (16, (5, 2, 7), 6), (24, (3, 3, 3), 20), (12, (11, 1, 4), 7)]

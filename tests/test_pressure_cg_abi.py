@@ -1,28 +1,25 @@
 """CPU side of the conjugate-gradient projection (docs/SPEC.md §11): the four entry points are declared, exported and
 wrapped, and the driver takes --pressure before it touches the device. No GPU needed."""
 import os
-import re
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from abi_header import ROOT, declared_functions, enum_values, header_text, struct_field_names
+
 SYMBOLS = ("sf_set_pressure_solver", "sf_project_cg", "sf_poisson_residual", "sf_pressure_info_get")
 
 
 def test_symbols_declared_exported_and_wrapped():
     from fluidsolvergpu_amd import solver
 
-    header = open(os.path.join(ROOT, "include", "sfgpu.h")).read()
     for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, header), f"sfgpu.h does not declare {name}"
+        assert name in declared_functions("sfgpu.h"), f"sfgpu.h does not declare {name}"
         assert name in solver.ABI_SYMBOLS
         assert hasattr(solver.lib, name), f"libsfgpu.so does not export {name}"
     for method in ("set_pressure_solver", "project_cg", "poisson_residual", "pressure_info"):
         assert callable(getattr(solver.FluidSolver, method))
     for enum, want in (("sf_pressure_solver", {"SF_PRESSURE_JACOBI": "0", "SF_PRESSURE_CG": "1"}),
                        ("sf_cg_status", {"SF_CG_CONVERGED": "0", "SF_CG_MAX_ITERS": "1", "SF_CG_BREAKDOWN": "2"})):
-        m = re.search(r"enum\s+%s\s*\{([^}]*)\}" % enum, header)
-        assert m, f"sfgpu.h does not declare enum {enum}"
-        assert dict(re.findall(r"(SF_\w+)\s*=\s*(\d+)", m.group(1))) == want
+        assert enum_values(header_text(), enum) == want
     assert (solver.SF_PRESSURE_JACOBI, solver.SF_PRESSURE_CG) == (0, 1)
     assert (solver.SF_CG_CONVERGED, solver.SF_CG_MAX_ITERS, solver.SF_CG_BREAKDOWN) == (0, 1, 2)
 
@@ -32,11 +29,7 @@ def test_info_struct_matches_the_header():
 
     from fluidsolvergpu_amd import solver
 
-    header = open(os.path.join(ROOT, "include", "sfgpu.h")).read()
-    m = re.search(r"typedef struct sf_pressure_info \{([^}]*)\}", header)
-    assert m
-    names = re.findall(r"(\w+)\s*[,;]", m.group(1))
-    assert names == [n for n, _ in solver.SfPressureInfo._fields_]
+    assert struct_field_names(header_text(), "sf_pressure_info") == [n for n, _ in solver.SfPressureInfo._fields_]
     kinds = dict(solver.SfPressureInfo._fields_)
     assert kinds["rel_residual"] is C.c_double and kinds["iterations_total"] is C.c_longlong and kinds["solver"] is C.c_int
 

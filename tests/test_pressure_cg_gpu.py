@@ -9,45 +9,17 @@ import pytest
 
 import diagnostics_ref as D
 import pressure_cg_ref as R
+from gpu_support import (DTYPE_IDS, DTYPES, OPERATOR_CASES, VISC, S, assert_same_bits, check_solve, make, random_fields,
+                         upload_all)
 from shape_cases import cg_velocity as random_velocity
-from test_maccormack_gpu import OPERATOR_CASES, assert_same, make, random_fields, upload_all
 
 pytestmark = pytest.mark.gpu
 
-DT, DIFF, VISC = 0.1, 1e-4, 1e-4
-DTYPES = [np.float32, np.float64]
-IDS = ["f32", "f64"]
 CASES = sorted(OPERATOR_CASES + [(32, 1, "copy"), (32, 4, "copy")])
 CASE_IDS = [f"N{n}-P{p}-{t}" for n, p, t in CASES]
 
 
-def S():
-    from fluidsolvergpu_amd import solver
-
-    return solver
-
-
-def check_solve(fs, u, v, w, tol, max_iters, what, want=None):
-    """Uploads u, v, w, runs sf_project_cg into (u0, v0) and compares everything with the reference (`want`, if the
-    caller has computed R.project_cg of these arguments already). Returns it."""
-    for n, a in (("u", u), ("v", v), ("w", w)):
-        fs.upload(n, a)
-    info = fs.project_cg("u", "v", "w", "u0", "v0", tol, max_iters)
-    fs.sync()
-    if want is None:
-        want = R.project_cg(u, v, w, tol, max_iters)
-    print(f"{what}: got {info} want status {want['status']} iterations {want['iterations']} rel {want['rel_residual']!r}")
-    assert info["solver"] == S().SF_PRESSURE_CG
-    assert (info["status"], info["iterations"]) == (want["status"], want["iterations"]), what
-    assert D.bits(info["rel_residual"]) == D.bits(want["rel_residual"]), what
-    for slot, name in (("u", "u"), ("v", "v"), ("w", "w"), ("u0", "p"), ("v0", "div")):
-        assert_same(fs.download(slot), want[name], f"{what}: {name}")
-    got = fs.poisson_residual("u0", "v0")
-    assert D.bits(got) == D.bits(R.poisson_residual(want["p"], want["div"])), what
-    return want
-
-
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("N,P,transport", CASES, ids=CASE_IDS)
 def test_project_cg_matches_the_reference(N, P, transport, dtype):
     """A random velocity (shells as uploaded: the operator reads neighbours as stored) stopped by max_iters, and the
@@ -100,7 +72,7 @@ def test_residual_after_both_solvers_and_the_motivation(P, transport):
         fs.project("u", "v", "w", "u0", "v0")
         res_j = fs.poisson_residual("u0", "v0")
         jac = R.project_jacobi(u, v, w, 20)
-        assert_same(fs.download("u0"), jac["p"], "jacobi p")
+        assert_same_bits(fs.download("u0"), jac["p"], "jacobi p")
         assert D.bits(res_j) == D.bits(R.poisson_residual(jac["p"], jac["div"]))
         info = fs.pressure_info()
         assert (info["solver"], info["status"], info["iterations"]) == (S().SF_PRESSURE_JACOBI, S().SF_CG_MAX_ITERS, 20)
@@ -129,14 +101,14 @@ def composed_step(fs, forces, mc, tol, max_iters):
     return first, second
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("P", [1, 4])
 @pytest.mark.parametrize("forces_mc", [False, True], ids=["plain", "forces-maccormack"])
 def test_vel_step_with_cg_is_the_composed_step(forces_mc, P, dtype):
     vel_step_against_the_composed_step(forces_mc, P, dtype, 6)
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("P", [1, 4])
 @pytest.mark.parametrize("forces_mc", [False, True], ids=["plain", "forces-maccormack"])
 def test_vel_step_with_cg_is_the_composed_step_after_a_marching_diffuse(forces_mc, P, dtype, monkeypatch):
@@ -172,7 +144,7 @@ def vel_step_against_the_composed_step(forces_mc, P, dtype, K):
             assert total["solves_total"] == 2 * steps
             out.append(({n: fs.download(n) for n in ("u", "v", "w")}, infos, total["iterations_total"]))
     for n in ("u", "v", "w"):
-        assert_same(out[0][0][n], out[1][0][n], f"{n}: vel_step with CG against the composed step")
+        assert_same_bits(out[0][0][n], out[1][0][n], f"{n}: vel_step with CG against the composed step")
     assert out[0][2] == out[1][2]
     for a, b in zip(out[0][1], out[1][1]):  # sf_pressure_info_get reports the second projection of the step
         assert (a["solver"], a["status"], a["iterations"]) == (b["solver"], b["status"], b["iterations"])
@@ -199,10 +171,10 @@ def test_set_back_to_jacobi_is_the_untouched_context(P):
             info = fs.pressure_info()
             assert (info["solver"], info["iterations"], info["solves_total"]) == (S().SF_PRESSURE_JACOBI, 6, 4)
     for n in S().FIELD_NAMES:
-        assert_same(out[1][n], out[0][n], f"{n}: Jacobi selected again against the default context")
+        assert_same_bits(out[1][n], out[0][n], f"{n}: Jacobi selected again against the default context")
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("P", [1, 2])
 def test_nan_and_no_iterations_are_statuses_not_errors(P, dtype):
     N = 24
@@ -210,7 +182,7 @@ def test_nan_and_no_iterations_are_statuses_not_errors(P, dtype):
     with make(N, dtype, P=P) as fs:
         want = check_solve(fs, u, v, w, 1e-3, 0, "max_iters = 0")
         assert (want["status"], want["iterations"]) == (R.MAX_ITERS, 0)
-        assert_same(fs.download("u"), u, "u after no iteration")  # p = 0: u - c_grad*(0 - 0)
+        assert_same_bits(fs.download("u"), u, "u after no iteration")  # p = 0: u - c_grad*(0 - 0)
         bad = u.copy()
         bad[N // 2, 3, 5] = np.nan
         for n, a in (("u", bad), ("v", v), ("w", w)):

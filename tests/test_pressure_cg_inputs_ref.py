@@ -35,7 +35,7 @@ import pytest
 import diagnostics_ref as D
 import pressure_cg_ref as R
 import shape_cases as C
-from test_shape_inputs_ref import row_partials_one_trip, same_bits
+from ref_support import row_partials_one_trip, same_bits
 
 I, P, M = R.I, R.P, R.M
 F64 = np.float64

@@ -6,10 +6,8 @@ import pytest
 
 import diagnostics_ref as D
 import pressure_cg_ref as R
-from test_oracle_analytic import LD, modes, product, tol
-
-DTYPES = [np.float32, np.float64]
-IDS = ["f32", "f64"]
+from gpu_support import DTYPE_IDS, DTYPES
+from ref_support import LD, modes, product, tol
 
 
 def same(a, b):
@@ -32,7 +30,7 @@ def few_shell(N):
     return (shell[:, None, None] + shell[None, :, None] + shell[None, None, :]) <= 1
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("N,m", [(8, (1, 1, 1)), (16, (2, 5, 3)), (12, (4, 0, 7))])
 def test_a_single_mode_is_solved_in_one_iteration(N, m, dtype):
     """div = D M is an eigenvector of A with eigenvalue 6 - lambda: the first search direction is the answer."""
@@ -54,7 +52,7 @@ def test_a_single_mode_is_solved_in_one_iteration(N, m, dtype):
     assert R.poisson_residual(out["p"], out["div"]) <= 64 * float(np.finfo(dtype).eps)
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 def test_two_modes_take_two_iterations(dtype):
     N = 16
     (u1, v1, w1), _, _ = mode_pair(N, (2, 5, 3), (0.6, -0.4, 0.9), np.float64)
@@ -65,7 +63,7 @@ def test_two_modes_take_two_iterations(dtype):
     assert R.project_cg(u, v, w, 1e-3, 1)["status"] == R.MAX_ITERS
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 def test_zero_velocity_is_left_alone(dtype):
     N = 9
     z = np.zeros((N + 2,) * 3, dtype)
@@ -78,7 +76,7 @@ def test_zero_velocity_is_left_alone(dtype):
     assert R.poisson_residual(out["p"], out["div"]) == 0.0
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 def test_no_iterations_allowed(dtype):
     u, v, w = R.smooth_velocity(12, dtype)
     out = R.project_cg(u, v, w, 1e-3, 0)
@@ -88,7 +86,7 @@ def test_no_iterations_allowed(dtype):
         assert np.array_equal(out[n], f)
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 def test_a_nan_in_the_velocity_is_a_breakdown(dtype):
     u, v, w = R.smooth_velocity(12, dtype)
     u[5, 6, 7] = np.nan
@@ -97,7 +95,7 @@ def test_a_nan_in_the_velocity_is_a_breakdown(dtype):
     assert np.isnan(out["rel_residual"])
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("N", [8, 20])
 def test_emulated_slabs_give_the_same_bits(N, dtype):
     rng = np.random.RandomState(N)

@@ -21,8 +21,7 @@ import pytest
 import diagnostics_ref as D
 import pressure_cg_ref as R
 import shape_cases as C
-from test_maccormack_gpu import assert_same, make, random_fields, upload_all
-from test_pressure_cg_gpu import S, check_solve
+from gpu_support import S, assert_same_bits, check_solve, make, random_fields, upload_all
 
 pytestmark = pytest.mark.gpu
 
@@ -55,8 +54,8 @@ def test_residual_reads_the_shells_as_stored(N, dtype, P, transport):
             want = R.poisson_residual(a, b)
             print(f"N={N} P={P}: got {got!r} want {want!r}")
             assert D.bits(got) == D.bits(want)
-            assert_same(fs.download("u0"), a, "p after the residual")
-            assert_same(fs.download("v0"), b, "div after the residual")
+            assert_same_bits(fs.download("u0"), a, "p after the residual")
+            assert_same_bits(fs.download("v0"), b, "div after the residual")
 
 
 # ---- (b) -----------------------------------------------------------------------------------------------------------
@@ -109,9 +108,9 @@ def test_zero_velocity_with_a_negative_zero(N, P, transport, dtype):
     with make(N, dtype, P=P, transport=transport) as fs:
         want = check_solve(fs, u, v, w, TOL, 20, f"zero N={N} P={P}")
         assert (want["status"], want["iterations"], D.bits(want["rel_residual"])) == (R.CONVERGED, 0, D.bits(0.0))
-        assert_same(fs.download("u0"), np.zeros_like(u), "p")
+        assert_same_bits(fs.download("u0"), np.zeros_like(u), "p")
         for n, f in (("u", u), ("v", v), ("w", w)):
-            assert_same(fs.download(n), f, f"{n} unchanged")
+            assert_same_bits(fs.download(n), f, f"{n} unchanged")
 
 
 @pytest.mark.parametrize("dtype", C.DTYPES, ids=C.dname)
@@ -204,7 +203,7 @@ def test_vel_step_with_cg_under_switches(K, bound, P, env, monkeypatch):
     got_fields, got_infos = vel_steps_with_cg(K, bound, P)
     assert got_infos == want_infos, env
     for n in VEL_NAMES:
-        assert_same(got_fields[n], want_fields[n], f"{env} K={K} bound={bound} P={P}: {n}")
+        assert_same_bits(got_fields[n], want_fields[n], f"{env} K={K} bound={bound} P={P}: {n}")
 
 
 def test_graphs_replay_around_an_uncaptured_cg_step(monkeypatch):
@@ -234,4 +233,4 @@ def test_graphs_replay_around_an_uncaptured_cg_step(monkeypatch):
     assert out[0][1] == out[1][1]
     assert [i[0] for i in out[0][1]] == [S().SF_PRESSURE_JACOBI, S().SF_PRESSURE_CG, S().SF_PRESSURE_JACOBI]
     for n in S().FIELD_NAMES:
-        assert_same(out[1][0][n], out[0][0][n], f"{n}: SF_GRAPH=1 against no graphs")
+        assert_same_bits(out[1][0][n], out[0][0][n], f"{n}: SF_GRAPH=1 against no graphs")

@@ -14,17 +14,11 @@ import forces_ref as F
 import maccormack_ref as M
 import oracle_lib as O
 import shape_cases as C
+from ref_support import row_partials_one_trip, same_bits
+from shape_cases import DT
 
-DT = C.DT
 I = (slice(1, -1),) * 3
 IDS = [f"N{N}-{C.dname(t)}" for N, t in C.SHAPES]
-
-
-def same_bits(a, b):
-    """Same positions NaN, every other entry the same bits (the comparison of the GPU tests)."""
-    uint = np.uint32 if a.dtype == np.float32 else np.uint64
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(uint)[~na], b.view(uint)[~nb]))
 
 
 # ---- the flow takes every branch ---------------------------------------------------------------------------------
@@ -186,22 +180,7 @@ def test_nan_and_inf_velocities_are_legal_inputs():
 
 
 # ---- §10 ---------------------------------------------------------------------------------------------------------
-def row_partials_one_trip(terms, W, drop=False):
-    """Mutation 6: the lane stride of the first trip only; cells beyond 64 W are added to lane 0 one after another
-    (drop: not added at all — the loop over m runs once)."""
-    nk, N, _ = terms.shape
-    first = min(N, D.LANES * W)
-    t = np.zeros((nk, N, D.LANES * W), np.float64)
-    t[:, :, :first] = terms[:, :, :first]
-    t = t.reshape(nk, N, D.LANES, W)
-    c = np.zeros((nk, N, D.LANES), np.float64)
-    for e in range(W):
-        c = c + t[:, :, :, e]
-    for i in range(first, N if not drop else first):
-        c[:, :, 0] = c[:, :, 0] + terms[:, :, i]
-    return D.halve(c)
-
-
+# (mutation 6, the row partial of one trip: ref_support.row_partials_one_trip)
 def plane_partials_sequential(terms, W):
     """Mutation 7: the N row partials of a plane added one after another instead of folded by halving. (Padding to 2n
     instead of n cannot be told apart: the extra entries are +0.0 and no partial is ever -0.)"""

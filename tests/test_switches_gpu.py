@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_parity_gpu import DT, DIFF, VISC, NAMES, assert_same, make, rand_fields, small_velocity
+from gpu_support import DIFF, DT, NAMES, VISC, assert_equal_values, make, rand_fields, slab_kw, small_velocity
 
 pytestmark = pytest.mark.gpu
 
@@ -32,17 +32,14 @@ SWITCHES = [
     {"SF_AUTOTUNE": "0"},           # rccl-self contexts keep the default schedule instead of measuring one
     {"SF_MARCH": "0", "SF_TRAP": "3", "SF_HALO_STREAM": "2", "SF_SPLIT_FIELDS": "0"},
 ]
-# (SF_GRAPH: test_parity_gpu.py::test_graph_replay_matches; SF_MARCH_MINCELLS_K: the march_mode fixture there and below;
+# (SF_GRAPH: test_parity_gpu.py::test_graph_replay_matches; SF_MARCH_MINCELLS_K: the march_mode fixture of tests/gpu_support.py and below;
 # SF_TRACE_SCHEDULE: tests/test_schedule_trace.py)
 
 
 def run_case(N, P, K, steps, transport="copy", dtype=np.float32):
     f = small_velocity(rand_fields(N, dtype, 300 + N + P), N, dtype)
     src = {n: f[n].copy() for n in ("u0", "v0", "w0", "dens0")}
-    kw = {"nslabs_local": P}
-    if transport == "rccl-self" and P >= 2:
-        kw["flags"] = 2
-    with make(N, dtype, K=K, **kw) as fs:
+    with make(N, dtype, K=K, **slab_kw(transport, P)) as fs:
         for n in NAMES:
             fs.upload(n, f[n])
         for slot, n in (("user0", "u0"), ("user1", "v0"), ("user2", "w0"), ("user3", "dens0")):
@@ -71,7 +68,7 @@ def test_switch_settings_against_the_oracle(env, monkeypatch):
                                       (96, 3, 20, 1, "copy"), (96, 2, 4, 1, "copy"), (96, 2, 6, 2, "rccl-self")):
         got, want = run_case(N, P, K, steps, transport)
         for n in got:
-            assert_same(got[n], want[n], f"{env} N={N} P={P} K={K} {transport}: {n}")
+            assert_equal_values(got[n], want[n], f"{env} N={N} P={P} K={K} {transport}: {n}")
 
 
 @pytest.mark.parametrize("sweeps", ["2", "3"])
@@ -83,4 +80,4 @@ def test_two_and_three_sweep_marching_fp64(sweeps, monkeypatch):
     for N, P, K, steps, transport in ((64, 1, 7, 2, "copy"), (96, 3, 20, 1, "copy"), (72, 1, 9, 1, "copy")):
         got, want = run_case(N, P, K, steps, transport, dtype=np.float64)
         for n in got:
-            assert_same(got[n], want[n], f"SK_S={sweeps} f64 N={N} P={P} K={K}: {n}")
+            assert_equal_values(got[n], want[n], f"SK_S={sweeps} f64 N={N} P={P} K={K}: {n}")

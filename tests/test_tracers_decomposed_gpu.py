@@ -1,6 +1,6 @@
 """Tracers on slab-decomposed contexts (docs/SPEC.md §6.1): ownership by the sampled plane, migration to the
-neighbouring slab through the ghost-plane transports, and output in id order. Every comparison is exact bit equality,
-against the CPU oracle and against the undecomposed context."""
+neighbouring slab through the ghost-plane transports, and output in id order. Every comparison is exact equality of the
+values (gpu_support.assert_equal_values), against the CPU oracle and against the undecomposed context."""
 import os
 import subprocess
 
@@ -8,35 +8,9 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_support import DT, DTYPES, NAMES, ROOT, S, assert_equal_values, make
 
 pytestmark = pytest.mark.gpu
-
-DT, DIFF, VISC = 0.1, 1e-4, 1e-4
-NAMES = ("u", "v", "w", "u0", "v0", "w0", "dens", "dens0")
-DTYPES = [np.float32, np.float64]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def S():
-    from fluidsolvergpu_amd import solver
-
-    return solver
-
-
-def make(N, dtype, K=4, P=1, transport="copy", **kw):
-    if P > 1:
-        kw["nslabs_local"] = P
-        if transport == "rccl-self":
-            kw["flags"] = S().SF_FLAG_RCCL_SELF
-    return S().FluidSolver(N, dtype="f32" if dtype == np.float32 else "f64", iters=K, dt=DT, diff=DIFF, visc=VISC,
-                           **kw)
-
-
-def assert_same(got, want, what):
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        raise AssertionError(f"{what}: {len(bad)} entries differ, first at {bad[0]}: got {got[tuple(bad[0])]!r} "
-                             f"want {want[tuple(bad[0])]!r}")
 
 
 def owner(z, N, nzl):
@@ -95,8 +69,8 @@ def test_tracers_parity_with_oracle_and_one_slab(P, transport, dtype):
                 assert fs.transport_info()["rccl_groups"] - g0 == calls
             assert fs.tracers_owned() == len(pos)
     for q, (what, w) in enumerate((("positions", want), ("density", want_d), ("speed", want_s))):
-        assert_same(out[P][q], w, f"P={P} {transport}: {what} vs oracle")
-        assert_same(out[P][q], out[1][q], f"P={P} {transport}: {what} vs one slab")
+        assert_equal_values(out[P][q], w, f"P={P} {transport}: {what} vs oracle")
+        assert_equal_values(out[P][q], out[1][q], f"P={P} {transport}: {what} vs one slab")
 
 
 def test_set_then_get_returns_raw_positions():
@@ -131,7 +105,7 @@ def test_tracers_with_full_steps(transport):
             out[p] = fs.tracers_get()
             fs.sync()
     for q, what in enumerate(("positions", "density", "speed")):
-        assert_same(out[P][q], out[1][q], f"{transport}: {what} after {rounds} full steps")
+        assert_equal_values(out[P][q], out[1][q], f"{transport}: {what} after {rounds} full steps")
 
 
 def test_get_owned_on_four_slabs():
@@ -148,9 +122,9 @@ def test_get_owned_on_four_slabs():
         kb, ke = fs.owned_planes()
     assert (kb, ke) == (1, N + 1)
     np.testing.assert_array_equal(ids, np.arange(len(pos)))
-    assert_same(oxyz, xyz, "owned positions")
-    assert_same(odens, dens, "owned density")
-    assert_same(ospeed, speed, "owned speed")
+    assert_equal_values(oxyz, xyz, "owned positions")
+    assert_equal_values(odens, dens, "owned density")
+    assert_equal_values(ospeed, speed, "owned speed")
 
 
 def test_get_owned_per_slab_of_a_rank_share():
@@ -213,9 +187,9 @@ def test_capacity_overflow_is_reported_and_recoverable():
     want = pos.copy()
     O.tracers_advect(want, f["u"], f["v"], f["w"], np.float32(DT))
     want_d, want_s = O.tracers_sample(want, f["dens"], f["u"], f["v"], f["w"])
-    assert_same(got[0], want, "positions after re-set")
-    assert_same(got[1], want_d, "density after re-set")
-    assert_same(got[2], want_s, "speed after re-set")
+    assert_equal_values(got[0], want, "positions after re-set")
+    assert_equal_values(got[1], want_d, "density after re-set")
+    assert_equal_values(got[2], want_s, "speed after re-set")
 
 
 def test_tracer_skipping_a_slab_is_reported():
