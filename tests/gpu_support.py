@@ -1,5 +1,5 @@
 """What the GPU suites (tests/test_*_gpu.py) share: the constants of the step, the case table of the single operators,
-the context factory, the two comparisons, the input builders, the checks against the numpy references and the fixtures
+the context factory, the comparison, the input builders, the checks against the numpy references and the fixtures
 that select a kernel form. A test module imports what it needs from here and from the reference modules, never from
 another test module. Importing this module needs no GPU and no libsfgpu.so."""
 import socket
@@ -60,12 +60,12 @@ def check_transport(fs, transport, P):
         assert info["transport"] == "copy" and info["rccl_groups"] == 0, info
 
 
-# ---- the two comparisons -----------------------------------------------------------------------------------------
-def _raise_on(differ, got, want, what, extra=""):
+# ---- the comparison ----------------------------------------------------------------------------------------------
+def _raise_on(differ, got, want, what):
     bad = np.argwhere(differ)
     if len(bad):
         at = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} entries differ{extra}, first at [k,j,i]={bad[0]}: got {got[at]!r} "
+        raise AssertionError(f"{what}: {len(bad)} entries differ, first at [k,j,i]={bad[0]}: got {got[at]!r} "
                              f"want {want[at]!r}")
 
 
@@ -78,15 +78,6 @@ def assert_same_bits(got, want, what, nan_ok=False):
     if nan_ok:
         differ &= ~(np.isnan(got) & np.isnan(want))
     _raise_on(differ, got, want, what)
-
-
-def assert_equal_values(got, want, what):
-    """Equality of the values (np.array_equal). It does not see the sign of a zero: -0.0 equals +0.0 here. A NaN equals
-    nothing, itself included. The rule of the parity and tracer files; where the bits matter use assert_same_bits."""
-    if not np.array_equal(got, want):
-        with np.errstate(invalid="ignore"):
-            err = np.max(np.abs(got.astype(np.float64) - want.astype(np.float64)))
-        _raise_on(got != want, got, want, what, f", Linf={err:g}")
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------

@@ -178,3 +178,129 @@ def zero_coefficient_inputs(N, dtype):
         f[n][1:-1, 1:-1, 1:-1:2] = -0.0
     f["v"][1, 1, 1] = f["u"][N, N, N] = f["dens"][1, N, 1] = np.nan
     return f
+
+
+# ---- inputs of the SPEC §3 operators and tracers held to bits (tests/stable_cases.py) ------------------------------
+def wall_sites(N, rng):
+    """Interior cells (k, j, i) that special_values meets only by luck: one on each of the six faces of the interior
+    (i, j or k = 1 or N), one edge cell, one corner cell and, where N allows, cells 64 and 65 of a row: the last lane of
+    a wave and the first of the next."""
+    r = lambda: 1 + rng.randint(N)
+    sites = [(r(), r(), 1), (r(), r(), N), (r(), 1, r()), (r(), N, r()), (1, r(), r()), (N, r(), r()),
+             (N, 1, r()), (N, N, 1)]
+    if N >= 65:
+        k, j = r(), r()
+        sites += [(k, j, 64), (k, j, 65)]
+    return sites
+
+
+def wall_specials(x, rng, nonfinite=True):
+    """A copy of x with the values of SPECIALS planted at wall_sites: -0 and +0 on a cell of every site (a draw of
+    sites each), and with nonfinite NaN, +inf and -inf too. From N = 64 on each non-finite value takes a draw of sites
+    of its own; below, the three take turns over one draw, so that a small grid holds eight non-finite cells and a
+    compared field does not drown in NaN."""
+    x = x.copy()
+    T = x.dtype.type
+    N = x.shape[0] - 2
+    for val in SPECIALS[3:]:
+        for c in wall_sites(N, rng):
+            x[c] = T(val)
+    if nonfinite and N >= 64:
+        for val in SPECIALS[:3]:
+            for c in wall_sites(N, rng):
+                x[c] = T(val)
+    elif nonfinite:
+        for q, c in enumerate(wall_sites(N, rng)):
+            x[c] = T(SPECIALS[q % 3])
+    return x
+
+
+def zero_region(f, K, rng):
+    """Copies of the fields of the dict f with two boxes of zeros, the same boxes in every field: one from the low i, j
+    and k walls (shell included) 2K + 3 cells inward, clipped to N, of +0 and -0 with random signs; one of the same
+    depth against the high walls, clipped to N / 2 so that it leaves the first standing, uniformly -0. Cells more than K from a box's inner faces stay zero through K sweeps,
+    so their sign is what the SPEC's expression gives for zero operands."""
+    out = {}
+    for n, x in f.items():
+        x = x.copy()
+        T = x.dtype.type
+        N = x.shape[0] - 2
+        side = min(N, 2 * K + 3)
+        lo = (slice(0, side + 1),) * 3
+        x[lo] = np.where(rng.random_sample(x[lo].shape) < 0.5, T(-0.0), T(0.0))
+        if N >= 2:
+            x[(slice(N + 1 - min(side, N // 2), N + 2),) * 3] = T(-0.0)
+        out[n] = x
+    return out
+
+
+def subnormal_field(N, dtype, seed, huge=False, scale=1.0):
+    """Normal data (of standard deviation `scale`) in which about one cell in eight is a subnormal of either sign (one in sixty-four the
+    smallest one) and, with huge (set_bnd and add_source only: a sum of six of them overflows a sweep), one cell in
+    sixty-four lies within a factor two of the largest finite value, so that an edge's A + B overflows."""
+    rng = np.random.RandomState(seed)
+    T = np.dtype(dtype).type
+    fi = np.finfo(dtype)
+    x = (scale * rng.standard_normal((N + 2,) * 3)).astype(dtype)
+    sign = np.where(rng.random_sample(x.shape) < 0.5, T(-1), T(1))
+    pick = rng.random_sample(x.shape)
+    sub = (rng.random_sample(x.shape) * float(fi.tiny)).astype(dtype)  # below the smallest normal
+    x = np.where(pick < 1.0 / 8.0, sign * sub, x)
+    x = np.where(pick < 1.0 / 64.0, sign * T(fi.smallest_subnormal), x)
+    if huge:
+        big = (T(fi.max) * (0.5 + 0.5 * rng.random_sample(x.shape))).astype(dtype)
+        x = np.where(pick > 1.0 - 1.0 / 64.0, sign * big, x)
+    return x.astype(dtype)
+
+
+LANDING_DT = 0.125
+
+
+def exact_landing(N, dtype, seed, dt=LANDING_DT):
+    """(d0, u, v, w) for advect with dt: velocities m / dt0 with m an integer in -3 .. 3 or, on one cell in eight, the
+    half-integer that carries the cell onto lo = 0.5 or hi = N + 0.5. With dt = 0.125 and N a power of two dt0 is a
+    power of two, every velocity exact, and the traces land exactly on cell centres (s1 = t1 = r1 = 0, also with
+    i0 = N and clamped at lo) and on the two bounds. d0 is standard normal with a block of -0, and three cells (2, 2, c)
+    whose trace is made to land on their own centre with d0 = -0 there and +inf, a negative and a positive value at the
+    i0 + 1 sample, which the SPEC multiplies by s1 = 0: NaN, and +0 from -0 + (+0)."""
+    rng = np.random.RandomState(seed)
+    T = np.dtype(dtype).type
+    dt0 = T(dt) * T(N)
+    idx = np.arange(N + 2, dtype=np.float64)
+    vel = []
+    for ax in range(3):
+        m = rng.randint(-3, 4, (N + 2,) * 3).astype(np.float64)
+        shape = [1, 1, 1]
+        shape[2 - ax] = N + 2
+        pos = idx.reshape(shape)
+        pick = rng.random_sample(m.shape)
+        m = np.where(pick < 1.0 / 16.0, pos - 0.5, m)
+        m = np.where(pick > 1.0 - 1.0 / 16.0, pos - (N + 0.5), m)
+        vel.append(m)
+    d0 = rng.standard_normal((N + 2,) * 3).astype(dtype)
+    side = min(N, 4)
+    d0[(slice(N + 1 - side, N + 1),) * 3] = T(-0.0)
+    if N >= 8:
+        for c, val in ((1, np.inf), (3, -1.5), (5, 2.5)):
+            for m in vel:
+                m[2, 2, c] = 0.0
+            d0[2, 2, c] = T(-0.0)
+            d0[2, 2, c + 1] = T(val)
+    u, v, w = ((m / float(dt0)).astype(dtype) for m in vel)
+    return d0, u, v, w
+
+
+def tracer_positions(N, dtype, seed, n=200):
+    """(n + specials, 3) positions: uniform over [-1, N + 2] and, cycled through the three coordinates of the rest,
+    0.5, N + 0.5 and one ulp either side of each, integers, +-0, +-inf and NaN."""
+    rng = np.random.RandomState(seed)
+    T = np.dtype(dtype).type
+    lo, hi = T(0.5), T(N) + T(0.5)
+    edge = [lo, hi, np.nextafter(lo, T(0)), np.nextafter(lo, T(1)), np.nextafter(hi, T(0)), np.nextafter(hi, T(2 * N + 2)),
+            T(0.0), T(-0.0), T(np.inf), T(-np.inf), T(np.nan), T(1), T(N), T(N + 1), T(max(N // 2, 1))]
+    pos = rng.uniform(-1.0, N + 2.0, size=(n + 3 * len(edge), 3)).astype(dtype)
+    for q, val in enumerate(edge):
+        for ax in range(3):
+            pos[n + 3 * q + ax, ax] = val
+            pos[n + 3 * q + ax, (ax + 1) % 3] = edge[(q + ax + 1) % len(edge)] if q % 2 else pos[n + 3 * q + ax, (ax + 1) % 3]
+    return pos

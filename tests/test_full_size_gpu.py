@@ -4,13 +4,13 @@ The dominant kernel instantiation of configs 2-5 — the plain four-sweep marchi
 `jacobi_sk_kernel<T,1,WL,NT=true,4,TJ,8,false,0>` — only runs when K >= 12 and the working set exceeds the Infinity
 Cache (N >~ 320). Every smaller test leaves it out, so these cases run the real sizes against the serial CPU oracle:
 the oracle sweeps ~1 G cells/s, i.e. seconds to tens of seconds per case. Comparison: every cell of every field, shells
-included, exact equality of the values (gpu_support.assert_equal_values; no tolerance).
+included, exact equality of the bits (gpu_support.assert_same_bits; no tolerance).
 """
 import numpy as np
 import pytest
 
 import oracle_lib as O
-from gpu_support import DIFF, DT, VISC, assert_equal_values, bench_state, check_transport, make, slab_kw
+from gpu_support import DIFF, DT, VISC, assert_same_bits, bench_state, check_transport, make, slab_kw
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +40,7 @@ def test_config2_full_size():
     bound sources (the second step starts from a developed state) — u, v, w, dens bit-identical to the oracle."""
     got, want = run_bench_steps(256, np.float32, 20, 2)
     for n in got:
-        assert_equal_values(got[n], want[n], f"config 2 (256^3 f32 K=20, 2 steps): {n}")
+        assert_same_bits(got[n], want[n], f"config 2 (256^3 f32 K=20, 2 steps): {n}")
     assert np.isfinite(got["dens"]).all() and got["dens"].max() > 1.0
 
 
@@ -50,7 +50,7 @@ def test_mid_size_default_thresholds():
     size class that does, with the most chunk ends per plane. One step of the benchmark inputs against the oracle."""
     got, want = run_bench_steps(144, np.float32, 20, 1)
     for n in got:
-        assert_equal_values(got[n], want[n], f"144^3 f32 K=20, default thresholds: {n}")
+        assert_same_bits(got[n], want[n], f"144^3 f32 K=20, default thresholds: {n}")
     with make(144, np.float32, K=20) as fs:
         assert fs.lin_solve_launches(20) == 5  # five four-sweep marching launches, no pair launch
 
@@ -74,7 +74,7 @@ def test_fields_in_one_grid_default_thresholds_caller_sources():
     f.update({n: src[n].copy() for n in src})
     O.step(N, f, dtype(DT), dtype(DIFF), dtype(VISC), K)
     for n in got:
-        assert_equal_values(got[n], f[n], f"192^3 f32 K=20, caller sources, default thresholds: {n}")
+        assert_same_bits(got[n], f[n], f"192^3 f32 K=20, caller sources, default thresholds: {n}")
 
 
 def roofline_inputs(N, dtype):
@@ -101,7 +101,7 @@ def test_config3_lin_solve_full_size(N, dtype, K):
         fs.sync()
         got = fs.download("dens")
     O.lin_solve(0, x, x0, dtype(a), dtype(c), K)
-    assert_equal_values(got, x, f"{N}^3 lin_solve K={K}")
+    assert_same_bits(got, x, f"{N}^3 lin_solve K={K}")
 
 
 def test_config3_step_full_size():
@@ -109,7 +109,7 @@ def test_config3_step_full_size():
     inputs, bound sources) against the oracle (~40 s of CPU)."""
     got, want = run_bench_steps(512, np.float32, 40, 1)
     for n in got:
-        assert_equal_values(got[n], want[n], f"config 3 (512^3 f32 K=40): {n}")
+        assert_same_bits(got[n], want[n], f"config 3 (512^3 f32 K=40): {n}")
 
 
 @pytest.mark.parametrize("N,dtype,K", [(1024, np.float32, 20), (512, np.float64, 40)], ids=["config4-1024-f32-K20", "config5-512-f64-K40"])
@@ -130,4 +130,4 @@ def test_decomposed_configs_lin_solve_eight_slabs_vs_oracle(N, dtype, K):
         check_transport(fs, "rccl-self", 8)
         got = fs.download("dens")
     O.lin_solve(0, x, x0, dtype(a), dtype(c), K)
-    assert_equal_values(got, x, f"{N}^3 lin_solve K={K}, 8 slabs (rccl-self) vs oracle")
+    assert_same_bits(got, x, f"{N}^3 lin_solve K={K}, 8 slabs (rccl-self) vs oracle")

@@ -1,6 +1,6 @@
-"""The shared comparisons and the context factory of tests/gpu_support.py hold what the GPU suites rely on (no GPU
-needed): assert_same_bits sees a signed zero, one ulp and a NaN payload; assert_equal_values sees one ulp and, by its
-definition, not the sign of a zero; make passes exactly the keyword arguments the suites passed before they shared it."""
+"""The shared comparison and the context factory of tests/gpu_support.py hold what the GPU suites rely on (no GPU
+needed): assert_same_bits sees a signed zero, one ulp and a NaN payload; make passes exactly the keyword arguments the
+suites passed before they shared it."""
 import numpy as np
 import pytest
 
@@ -50,17 +50,6 @@ def test_assert_same_bits(dtype):
         G.assert_same_bits(a, a.astype(np.float32 if dtype == np.float64 else np.float64), "other precision")
     with pytest.raises(AssertionError):
         G.assert_same_bits(a, a[1:], "other shape")
-
-
-@pytest.mark.parametrize("dtype", G.DTYPES, ids=G.DTYPE_IDS)
-def test_assert_equal_values(dtype):
-    a = field(dtype)
-    G.assert_equal_values(a, a.copy(), "equal")
-    G.assert_equal_values(with_cell(a, -0.0), with_cell(a, 0.0), "signed zero: not seen")
-    with pytest.raises(AssertionError, match=r"1 entries differ, Linf=\S+, first at \[k,j,i\]=\[1 2 3\]"):
-        G.assert_equal_values(with_cell(a, np.nextafter(dtype(1.5), dtype(2))), a, "one ulp")
-    with pytest.raises(AssertionError):
-        G.assert_equal_values(with_cell(a, np.nan), with_cell(a, np.nan), "a NaN equals nothing")
 
 
 class Recorder:

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from gpu_support import DIFF, DT, NAMES, VISC, assert_equal_values, make, rand_fields, slab_kw, small_velocity
+from gpu_support import DIFF, DT, NAMES, VISC, assert_same_bits, make, rand_fields, slab_kw, small_velocity
 
 pytestmark = pytest.mark.gpu
 
@@ -68,7 +68,7 @@ def test_switch_settings_against_the_oracle(env, monkeypatch):
                                       (96, 3, 20, 1, "copy"), (96, 2, 4, 1, "copy"), (96, 2, 6, 2, "rccl-self")):
         got, want = run_case(N, P, K, steps, transport)
         for n in got:
-            assert_equal_values(got[n], want[n], f"{env} N={N} P={P} K={K} {transport}: {n}")
+            assert_same_bits(got[n], want[n], f"{env} N={N} P={P} K={K} {transport}: {n}")
 
 
 @pytest.mark.parametrize("sweeps", ["2", "3"])
@@ -80,4 +80,4 @@ def test_two_and_three_sweep_marching_fp64(sweeps, monkeypatch):
     for N, P, K, steps, transport in ((64, 1, 7, 2, "copy"), (96, 3, 20, 1, "copy"), (72, 1, 9, 1, "copy")):
         got, want = run_case(N, P, K, steps, transport, dtype=np.float64)
         for n in got:
-            assert_equal_values(got[n], want[n], f"SK_S={sweeps} f64 N={N} P={P} K={K}: {n}")
+            assert_same_bits(got[n], want[n], f"SK_S={sweeps} f64 N={N} P={P} K={K}: {n}")

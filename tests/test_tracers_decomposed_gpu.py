@@ -1,6 +1,6 @@
 """Tracers on slab-decomposed contexts (docs/SPEC.md §6.1): ownership by the sampled plane, migration to the
 neighbouring slab through the ghost-plane transports, and output in id order. Every comparison is exact equality of the
-values (gpu_support.assert_equal_values), against the CPU oracle and against the undecomposed context."""
+bits (gpu_support.assert_same_bits), against the CPU oracle and against the undecomposed context."""
 import os
 import subprocess
 
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from gpu_support import DT, DTYPES, NAMES, ROOT, S, assert_equal_values, make
+from gpu_support import DT, DTYPES, NAMES, ROOT, S, assert_same_bits, make
 
 pytestmark = pytest.mark.gpu
 
@@ -69,8 +69,8 @@ def test_tracers_parity_with_oracle_and_one_slab(P, transport, dtype):
                 assert fs.transport_info()["rccl_groups"] - g0 == calls
             assert fs.tracers_owned() == len(pos)
     for q, (what, w) in enumerate((("positions", want), ("density", want_d), ("speed", want_s))):
-        assert_equal_values(out[P][q], w, f"P={P} {transport}: {what} vs oracle")
-        assert_equal_values(out[P][q], out[1][q], f"P={P} {transport}: {what} vs one slab")
+        assert_same_bits(out[P][q], w, f"P={P} {transport}: {what} vs oracle")
+        assert_same_bits(out[P][q], out[1][q], f"P={P} {transport}: {what} vs one slab")
 
 
 def test_set_then_get_returns_raw_positions():
@@ -105,7 +105,7 @@ def test_tracers_with_full_steps(transport):
             out[p] = fs.tracers_get()
             fs.sync()
     for q, what in enumerate(("positions", "density", "speed")):
-        assert_equal_values(out[P][q], out[1][q], f"{transport}: {what} after {rounds} full steps")
+        assert_same_bits(out[P][q], out[1][q], f"{transport}: {what} after {rounds} full steps")
 
 
 def test_get_owned_on_four_slabs():
@@ -122,9 +122,9 @@ def test_get_owned_on_four_slabs():
         kb, ke = fs.owned_planes()
     assert (kb, ke) == (1, N + 1)
     np.testing.assert_array_equal(ids, np.arange(len(pos)))
-    assert_equal_values(oxyz, xyz, "owned positions")
-    assert_equal_values(odens, dens, "owned density")
-    assert_equal_values(ospeed, speed, "owned speed")
+    assert_same_bits(oxyz, xyz, "owned positions")
+    assert_same_bits(odens, dens, "owned density")
+    assert_same_bits(ospeed, speed, "owned speed")
 
 
 def test_get_owned_per_slab_of_a_rank_share():
@@ -187,9 +187,9 @@ def test_capacity_overflow_is_reported_and_recoverable():
     want = pos.copy()
     O.tracers_advect(want, f["u"], f["v"], f["w"], np.float32(DT))
     want_d, want_s = O.tracers_sample(want, f["dens"], f["u"], f["v"], f["w"])
-    assert_equal_values(got[0], want, "positions after re-set")
-    assert_equal_values(got[1], want_d, "density after re-set")
-    assert_equal_values(got[2], want_s, "speed after re-set")
+    assert_same_bits(got[0], want, "positions after re-set")
+    assert_same_bits(got[1], want_d, "density after re-set")
+    assert_same_bits(got[2], want_s, "speed after re-set")
 
 
 def test_tracer_skipping_a_slab_is_reported():
