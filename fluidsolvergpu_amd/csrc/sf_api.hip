@@ -232,6 +232,14 @@ int sf_pressure_info_get(const sf_ctx* ctx, sf_pressure_info* out) {
     ctx->impl->pressure_info(out);
     return SF_OK;
 }
+int sf_set_pressure_sync(sf_ctx* ctx, int check_every) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_pressure_sync(check_every); });
+}
+int sf_pressure_sync_get(const sf_ctx* ctx, sf_pressure_sync* out) {
+    if (!ctx || !ctx->impl || !out) return SF_ERR_INVALID;
+    ctx->impl->pressure_sync(out);
+    return SF_OK;
+}
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });
 }

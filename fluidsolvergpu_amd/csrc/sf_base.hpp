@@ -108,6 +108,8 @@ public:
     virtual void project_cg(int u, int v, int w, int p, int div, double tol, int max_iters) = 0;
     virtual void poisson_residual(int p, int div, double* rel) = 0;
     virtual void pressure_info(sf_pressure_info* out) const = 0;
+    virtual void set_pressure_sync(int check_every) = 0;
+    virtual void pressure_sync(sf_pressure_sync* out) const = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

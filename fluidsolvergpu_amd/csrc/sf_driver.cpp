@@ -25,7 +25,7 @@
 //   sf_driver [--n 64] [--steps 20] [--iters 20] [--dtype f32|f64] [--every 10] [--out DIR]
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
-//             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]]
+//             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -39,6 +39,9 @@
 // cg with a relative tolerance (default 1e-3) and an iteration limit (default 100). With --monitor a second line
 //   pressure step=<t> solver=<jacobi|cg> status=<s> iterations=<n> rel_residual=<g> iterations_total=<n>
 // follows each monitor line: the step's last projection (sf_pressure_info_get).
+// --pressure-sync M (with --pressure cg): check_every of sf_set_pressure_sync. 0, the default: the host reads every inner
+// product of a solve; M >= 1: the solve's scalars stay on the device and the host looks at them every M iterations. The
+// frames and the monitor lines are the same bits either way.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -75,7 +78,7 @@ struct Options {
     double vorticity = 0.0, buoyancy = 0.0, ambient = 0.0;
     int buoyancy_axis = 1;
     int advect_vel = SF_ADVECT_SEMI_LAGRANGIAN, advect_dens = SF_ADVECT_SEMI_LAGRANGIAN;
-    int pressure = SF_PRESSURE_JACOBI, cg_max_iters = 100;
+    int pressure = SF_PRESSURE_JACOBI, cg_max_iters = 100, cg_check_every = 0;
     double cg_tol = 1e-3;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
@@ -181,6 +184,16 @@ static Options parse(int argc, char** argv) {
                 fprintf(stderr, "--monitor takes a step count >= 1\n");
                 exit(2);
             }
+        }
+        else if (s == "--pressure-sync") {
+            const std::string ms = next();
+            char* end = nullptr;
+            const long m = strtol(ms.c_str(), &end, 10);
+            if (ms.empty() || *end != 0 || m < 0 || m > 1000000) {
+                fprintf(stderr, "--pressure-sync takes a count of iterations >= 0, not %s\n", ms.c_str());
+                exit(2);
+            }
+            o.cg_check_every = (int)m;
         }
         else if (s == "--maccormack") {
             const std::string which = next();
@@ -365,6 +378,7 @@ static int run(const Options& o) {
     SF_CHECK_RETURN(sf_set_buoyancy(g_ctx, o.buoyancy, o.ambient, o.buoyancy_axis));
     SF_CHECK_RETURN(sf_set_advection(g_ctx, o.advect_vel, o.advect_dens));
     if (o.pressure != SF_PRESSURE_JACOBI) SF_CHECK_RETURN(sf_set_pressure_solver(g_ctx, o.pressure, o.cg_tol, o.cg_max_iters));
+    if (o.cg_check_every > 0) SF_CHECK_RETURN(sf_set_pressure_sync(g_ctx, o.cg_check_every));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

@@ -2954,6 +2954,20 @@ static __global__ void __launch_bounds__(256) fold_rows_kernel(const double* __r
 // inner product is the fold of the very lane accumulators §10 prescribes, and the field passes and the sums are one
 // launch. Per-cell expressions are in T as §11 brackets them; a term goes to double before it is multiplied.
 // Loads are unconditional and clamped to the row's last vector as above; lanes past the row end store nothing.
+
+// The scalars of one solve where they live on the device (SPEC §11 "Where the scalars are computed"): written by
+// cg_scalars_kernel only, from one lane, in plain stores; read by the device-scalar forms of the row kernels and, through
+// a pinned mirror, by the host. status holds the values of enum sf_cg_status (include/sfgpu.h).
+template <class T>
+struct CgState {
+    double rho0, rho, delta, rho_new, last;
+    T mu, aT, bT;
+    int status, iterations, active;
+};
+enum { CG_ST_CONVERGED = 0, CG_ST_MAX_ITERS = 1, CG_ST_BREAKDOWN = 2 };
+enum { STAGE_MU = 0, STAGE_RHO0 = 1, STAGE_DELTA = 2, STAGE_RHO = 3 };
+enum { CG_USE_MU = 0, CG_USE_ALPHA = 1, CG_USE_BETA = 2 };
+
 template <class T>
 struct CgArgs {
     const T* div;  // init: the right-hand side; residual: the right-hand side
@@ -2961,8 +2975,28 @@ struct CgArgs {
     T* r;          // init: written; update: r -= a*q; direction: read
     T* d;          // init: written; apply: read at the seven points; direction: d = r + b*d
     T* q;          // apply: written; update: read
-    T s;           // init: mu; update: (T)alpha; direction: (T)beta
+    union {
+        T s;                     // init: mu; update: (T)alpha; direction: (T)beta
+        const CgState<T>* st;    // the device-scalar forms (DEV): where those three and `active` live instead
+    };  // (8 bytes at the place T s and its padding had: the by-value forms keep their kernel arguments)
 };
+
+// By value (DEV false): always live, the scalar is A.s. From the state (DEV): one wave-uniform load each; a solve that
+// has stopped (active == 0) makes apply, update and direction return before they touch a field or a row record.
+template <bool DEV, int USE, class T>
+__device__ __forceinline__ T cg_scalar(const CgArgs<T>& A) {
+    if constexpr (DEV)
+        return USE == CG_USE_MU ? A.st->mu : (USE == CG_USE_ALPHA ? A.st->aT : A.st->bT);
+    else
+        return A.s;
+}
+template <bool DEV, class T>
+__device__ __forceinline__ bool cg_live(const CgArgs<T>& A) {
+    if constexpr (DEV)
+        return A.st->active != 0;
+    else
+        return true;
+}
 
 // valid cells of the lane's vector: W, fewer in the ragged last vector, <= 0 past the row end
 template <int W>
@@ -2971,12 +3005,14 @@ __device__ __forceinline__ int cg_valid(const Geom& g, int i0) {
     return nv > W ? W : nv;
 }
 
-// r = div - mu, d = r with set_bnd(0, d); row records of r.r
-template <class T>
+// r = div - mu, d = r with set_bnd(0, d); row records of r.r. It starts a solve, so with DEV it takes mu from the state and
+// does not look at `active` (what the solve before left).
+template <class T, bool DEV = false>
 __global__ void __launch_bounds__(256) cg_init_kernel(Geom g, CgArgs<T> A, double* __restrict__ rows, int npad) {
     constexpr int W = VecT<T>::W;
     int j, p;
     if (!reduce_row(g, j, p)) return;
+    const T mu = cg_scalar<DEV, CG_USE_MU>(A);
     const int kl = g.G + p;
     const long r = row0(g, j, kl);
     const int nm = (g.N + 64 * W - 1) / (64 * W);
@@ -2989,7 +3025,7 @@ __global__ void __launch_bounds__(256) cg_init_kernel(Geom g, CgArgs<T> A, doubl
         T out[W];
 #pragma unroll
         for (int e = 0; e < W; ++e) {
-            out[e] = dv[e] - A.s;
+            out[e] = dv[e] - mu;
             cs = cs + (e < nv ? (double)out[e] * (double)out[e] : 0.0);
         }
         if (nv > 0) {
@@ -3033,10 +3069,11 @@ __device__ __forceinline__ void cg_stencil(const Geom& g, const T* __restrict__ 
 
 // RES == false: q = A d, row records of d.q (the kernel that decides the cost of an iteration).
 // RES == true:  e = div - A p, row records of e.e (value 0) and div.div (value 1); nothing is written to a field.
-template <class T, bool RES>
+template <class T, bool RES, bool DEV = false>
 __global__ void __launch_bounds__(256) cg_apply_dot_kernel(Geom g, CgArgs<T> A, double* __restrict__ rows, int npad) {
     constexpr int W = VecT<T>::W;
     int j, p;
+    if (!cg_live<DEV>(A)) return;
     if (!reduce_row(g, j, p)) return;
     const long r = row0(g, j, g.G + p);
     const int nm = (g.N + 64 * W - 1) / (64 * W);
@@ -3072,11 +3109,13 @@ __global__ void __launch_bounds__(256) cg_apply_dot_kernel(Geom g, CgArgs<T> A, 
 }
 
 // p = p + a*d, r = r - a*q; row records of r.r
-template <class T>
+template <class T, bool DEV = false>
 __global__ void __launch_bounds__(256) cg_update_kernel(Geom g, CgArgs<T> A, double* __restrict__ rows, int npad) {
     constexpr int W = VecT<T>::W;
     int j, p;
+    if (!cg_live<DEV>(A)) return;
     if (!reduce_row(g, j, p)) return;
+    const T a = cg_scalar<DEV, CG_USE_ALPHA>(A);
     const long r = row0(g, j, g.G + p);
     const int nm = (g.N + 64 * W - 1) / (64 * W);
     double cs = 0.0;
@@ -3089,8 +3128,8 @@ __global__ void __launch_bounds__(256) cg_update_kernel(Geom g, CgArgs<T> A, dou
         T op[W], orr[W];
 #pragma unroll
         for (int e = 0; e < W; ++e) {
-            op[e] = pv[e] + A.s * dv[e];
-            orr[e] = rv[e] - A.s * qv[e];
+            op[e] = pv[e] + a * dv[e];
+            orr[e] = rv[e] - a * qv[e];
             cs = cs + (e < nv ? (double)orr[e] * (double)orr[e] : 0.0);
         }
         if (nv > 0) {
@@ -3103,11 +3142,13 @@ __global__ void __launch_bounds__(256) cg_update_kernel(Geom g, CgArgs<T> A, dou
 }
 
 // d = r + b*d with set_bnd(0, d): the shells go out with the cells they mirror, no set_bnd launch
-template <class T>
+template <class T, bool DEV = false>
 __global__ void __launch_bounds__(256) cg_direction_kernel(Geom g, CgArgs<T> A) {
     constexpr int W = VecT<T>::W;
     int j, p;
+    if (!cg_live<DEV>(A)) return;
     if (!reduce_row(g, j, p)) return;
+    const T b = cg_scalar<DEV, CG_USE_BETA>(A);
     const int kl = g.G + p;
     const long r = row0(g, j, kl);
     const int nm = (g.N + 64 * W - 1) / (64 * W);
@@ -3118,10 +3159,60 @@ __global__ void __launch_bounds__(256) cg_direction_kernel(Geom g, CgArgs<T> A) 
         const int nv = cg_valid<W>(g, i0);
         T out[W];
 #pragma unroll
-        for (int e = 0; e < W; ++e) out[e] = rv[e] + A.s * dv[e];
+        for (int e = 0; e < W; ++e) out[e] = rv[e] + b * dv[e];
         if (nv > 0) {
             store_cells<T, W>(A.d, r, i0, out, nv);
             emit_shells<T, W>(A.d, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
+// One workgroup: the Total of SPEC §10 over the plane records recs[k0 .. k1) — a +0.0-started sequential sum in
+// increasing global k, the loop at the end of Solver::finish_records — then what the host does with that sum at this
+// stage of a solve, in the same double operations (a correctly rounded divide, a round-to-nearest-even conversion to
+// T). c: N^3 (STAGE_MU) or tol * tol (STAGE_RHO), formed by the host. The records go through LDS so that the one lane
+// that adds them waits for an addition per record, not for a load. k1 - k0 <= 2048 (Solver::records_alloc).
+// Every stage but the two that start a solve does nothing once the solve has stopped.
+template <class T, int STAGE>
+__global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restrict__ recs, int k0, int k1, double c,
+                                                         CgState<T>* __restrict__ st) {
+    __shared__ double a[2048];
+    const int t = (int)threadIdx.x, n = k1 - k0;
+    if (STAGE != STAGE_MU && STAGE != STAGE_RHO0 && st->active == 0) return;  // (the whole workgroup)
+    for (int k = t; k < n; k += 256) a[k] = recs[k0 + k];
+    __syncthreads();
+    if (t != 0) return;
+    double s = 0.0;
+    for (int k = 0; k < n; ++k) s = s + a[k];
+    if constexpr (STAGE == STAGE_MU) {
+        st->mu = (T)(s / c);
+    } else if constexpr (STAGE == STAGE_RHO0) {
+        st->rho0 = st->rho = st->last = s;
+        st->delta = st->rho_new = 0.0;
+        st->aT = st->bT = T(0);
+        st->iterations = 0;
+        st->status = s == 0.0 ? CG_ST_CONVERGED : (isfinite(s) ? CG_ST_MAX_ITERS : CG_ST_BREAKDOWN);
+        st->active = (s != 0.0 && isfinite(s)) ? 1 : 0;
+    } else if constexpr (STAGE == STAGE_DELTA) {
+        st->delta = s;
+        if (!(s > 0.0)) {
+            st->status = CG_ST_BREAKDOWN;
+            st->active = 0;
+        } else {
+            st->aT = (T)(st->rho / s);
+        }
+    } else {
+        st->rho_new = st->last = s;
+        st->iterations = st->iterations + 1;
+        if (!isfinite(s)) {
+            st->status = CG_ST_BREAKDOWN;
+            st->active = 0;
+        } else if (s <= c * st->rho0) {
+            st->status = CG_ST_CONVERGED;
+            st->active = 0;
+        } else {
+            st->bT = (T)(s / st->rho);
+            st->rho = s;
         }
     }
 }

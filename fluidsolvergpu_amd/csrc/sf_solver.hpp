@@ -9,7 +9,8 @@
 //     between processes) while the interior sweep runs. No collective reduction exists anywhere in
 //     the step, only neighbour exchange; sf_reduce / sf_diagnostics_get (SPEC §10) are calls of
 //     their own that the step never makes. The one exception is opt-in: with the conjugate-gradient pressure solver
-//     selected (SPEC §11) the two projections of vel_step read their inner products on the host.
+//     selected (SPEC §11) the two projections of vel_step read their inner products on the host, or, with
+//     sf_set_pressure_sync, fold them on the device and let the host read the solve's state once per batch.
 //   * fields are named slots holding device pointers, so SPEC's "swap" is a pointer swap.
 //   * there is NO CPU fallback: without a gfx950 device sf_create fails with SF_ERR_NO_DEVICE.
 #pragma once
@@ -374,6 +375,8 @@ public:
         if (t1_) (void)hipEventDestroy(t1_);
         if (red_host_) (void)hipHostFree(red_host_);
         if (red_gather_) (void)hipFree(red_gather_);
+        if (cg_state_) (void)hipFree(cg_state_);
+        if (cg_state_host_) (void)hipHostFree(cg_state_host_);
         tracers_free();
         if (copy_src_) (void)hipFree(copy_src_);
         if (copy_dst_) (void)hipFree(copy_dst_);
@@ -1173,6 +1176,15 @@ public:
         *rel = r[1] == 0.0 ? 0.0 : std::sqrt(r[0] / r[1]);
     }
     void pressure_info(sf_pressure_info* out) const override { *out = info_; }
+    void set_pressure_sync(int check_every) override {
+        SF_REQUIRE(check_every >= 0, "pressure sync: check_every must be >= 0");
+        check_every_ = check_every;
+    }
+    void pressure_sync(sf_pressure_sync* out) const override {
+        out->check_every = check_every_;
+        out->host_waits = host_waits_;
+        out->host_waits_total = host_waits_total_;
+    }
 
     int lin_solve_launches(int iters) const override {
         return (int)plan_solve(iters, false, false, false).size();
@@ -2685,11 +2697,79 @@ private:
     // The work fields r, d, q are the three scratch buffers, addressed through internal slots while the operator is
     // issued (exchange() takes slots), as `hat` is in op_advect_mc. Every row kernel runs a slab's nzl planes in one
     // launch on its compute stream; d's ghost planes travel on the halo stream after every update of d while the host
-    // waits for the sum that follows. Two host synchronisations per iteration (finish_records).
+    // waits for the sum that follows. Two host synchronisations per iteration (finish_records) — or, with
+    // check_every_ = m >= 1, none: every sum is folded by cg_scalars(), which leaves alpha, beta and the outcome of the
+    // stop tests in cg_state_ for the kernels that follow, and the host reads that state once per m iterations.
     double one_sum() {
         double r[1];
         finish_records(1, 1, 0, r);
+        ++host_waits_;
         return r[0];
+    }
+    void cg_state_alloc() {
+        if (cg_state_) return;
+        // the plane records of all N planes in one buffer (the all-gather's, where there is a communicator)
+        if (!red_gather_) SF_HIP(hipMalloc(&red_gather_, (size_t)sfk::DIAG_NV * N_ * sizeof(double)));
+        SF_HIP(hipMalloc(&cg_state_, sizeof(sfk::CgState<T>)));
+        SF_HIP(hipMemset(cg_state_, 0, sizeof(sfk::CgState<T>)));
+        SF_HIP(hipHostMalloc(&cg_state_host_, sizeof(sfk::CgState<T>), hipHostMallocDefault));
+    }
+    // a slab's plane records inside red_gather_ (one value per plane)
+    double* cg_records(const Slab& sl) const { return red_gather_ + (size_t)sl.gid * nzl_; }
+    // the argument of the device-scalar forms: the state where the by-value forms have the scalar
+    sfk::CgArgs<T> cg_dev_args(Slab& sl, int p, int div) const {
+        sfk::CgArgs<T> A = cg_args(sl, p, div, T(0));
+        A.st = cg_state_;
+        return A;
+    }
+    // What one_sum() does, without the host: row records -> every slab's plane records, next to each other in
+    // red_gather_ -> (all ranks' records, gathered in place) -> cg_scalars_kernel on slab 0's compute stream, which the
+    // other slabs' compute streams wait for. c: the stage's constant (N^3, tol * tol).
+    template <int STAGE>
+    void cg_scalars(double c) {
+        Slab& s0 = slabs_[0];
+        for (Slab& sl : slabs_) {
+            hipLaunchKernelGGL(sfk::fold_rows_kernel, dim3(nzl_, 1), dim3(256), 0, sl.cs, sl.red_rows, cg_records(sl), N_,
+                               rows_pad(), 1, 0);
+            SF_HIP(hipGetLastError());
+            tr_op("fold_rows", sl, sl.cs, {{sl.red_rows, false, 0, nplanes_}, {cg_records(sl), true, 0, nplanes_}});
+        }
+        for (int s = 1; s < L_; ++s) {
+            ev_record(slabs_[s], &Slab::cs_mark, slabs_[s].cs);
+            st_wait(s0, s0.cs, slabs_[s], &Slab::cs_mark);
+        }
+        std::vector<Acc> acc;
+        for (Slab& sl : slabs_) acc.push_back({cg_records(sl), false, 0, nplanes_});
+        if (comm_) {
+            const size_t cnt = (size_t)L_ * nzl_;
+            SF_NCCL(ncclGroupStart());
+            SF_NCCL(ncclAllGather(red_gather_ + (size_t)rank_ * cnt, red_gather_, cnt, ncclDouble, comm_, s0.cs));
+            SF_NCCL(ncclGroupEnd());
+            ++rccl_groups_;
+            acc.push_back({red_gather_, true, 0, nplanes_});  // (the other ranks' records)
+            tr_op("records_allgather", s0, s0.cs, acc);
+            acc.back().write = false;
+        }
+        // a loopback context stands for one rank of several and has nobody to gather from: its own planes only
+        const bool own_only = nranks_ > 1 && !comm_;
+        const int k0 = own_only ? rank_ * L_ * nzl_ : 0, k1 = own_only ? k0 + L_ * nzl_ : N_;
+        hipLaunchKernelGGL((sfk::cg_scalars_kernel<T, STAGE>), dim3(1), dim3(256), 0, s0.cs, (const double*)red_gather_, k0, k1,
+                           c, cg_state_);
+        SF_HIP(hipGetLastError());
+        acc.push_back({cg_state_, false, 0, nplanes_});
+        acc.push_back({cg_state_, true, 0, nplanes_});
+        tr_op("cg_scalars", s0, s0.cs, acc);
+        if (L_ > 1) ev_record(s0, &Slab::cs_mark, s0.cs);
+        for (int s = 1; s < L_; ++s) st_wait(slabs_[s], slabs_[s].cs, s0, &Slab::cs_mark);
+    }
+    // the one host wait of a batch: the state, as the last enqueued cg_scalars left it
+    const sfk::CgState<T>& cg_state_read() {
+        Slab& s0 = slabs_[0];
+        SF_HIP(hipMemcpyAsync(cg_state_host_, cg_state_, sizeof(sfk::CgState<T>), hipMemcpyDeviceToHost, s0.cs));
+        tr_op("cg_state_out", s0, s0.cs, {{cg_state_, false, 0, nplanes_}});
+        SF_HIP(hipStreamSynchronize(s0.cs));
+        ++host_waits_;
+        return *cg_state_host_;
     }
     sfk::CgArgs<T> cg_args(Slab& sl, int p, int div, T s) const {
         sfk::CgArgs<T> A;
@@ -2721,6 +2801,11 @@ private:
     void op_project_cg(int u, int v, int w, int p, int div, double tol, int max_iters, bool mirror_u = false) {
         mirror_u = mirror_u && ishell_skip_;
         records_alloc();
+        static_assert(sfk::CG_ST_CONVERGED == SF_CG_CONVERGED && sfk::CG_ST_MAX_ITERS == SF_CG_MAX_ITERS &&
+                          sfk::CG_ST_BREAKDOWN == SF_CG_BREAKDOWN, "CgState::status holds sf_cg_status values");
+        const int m = check_every_;  // 0: the scalars on the host; m >= 1: on the device, read back every m iterations
+        if (m > 0) cg_state_alloc();
+        host_waits_ = 0;
         ScratchAlias work_slots(slabs_, 3);
         const int kb = G_, ke = G_ + nzl_;
         // d as a kernel writes it: the shell plane of a wall slab included
@@ -2729,6 +2814,27 @@ private:
             wr_range(sl, kb, ke, lo, hi);
             return Acc{sl.field[CG_D], true, lo, hi};
         };
+        // the fields each row kernel touches, in either form
+        auto init_acc = [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke}, d_written(sl)};
+        };
+        auto apply_acc = [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[CG_D], false, kb - 1, ke + 1}, {sl.field[CG_Q], true, kb, ke}};
+        };
+        auto update_acc = [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[CG_D], false, kb, ke}, {sl.field[CG_Q], false, kb, ke},
+                                    {sl.field[p], false, kb, ke},    {sl.field[p], true, kb, ke},
+                                    {sl.field[CG_R], false, kb, ke}, {sl.field[CG_R], true, kb, ke}};
+        };
+        auto direction_acc = [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[CG_R], false, kb, ke}, {sl.field[CG_D], false, kb, ke}, d_written(sl)};
+        };
+        // the device-scalar forms read the state as well
+        auto with_state = [&](std::vector<Acc> a) {
+            a.push_back({cg_state_, false, 0, nplanes_});
+            return a;
+        };
+        auto dev_args = [&](Slab& sl) { return cg_dev_args(sl, p, div); };
 
         project_first_half(u, v, w, p, div, mirror_u, false, true);
         join();
@@ -2736,58 +2842,80 @@ private:
                     [&](Slab& sl) { return (const T*)sl.field[div]; },
                     [&](Slab& sl) { return std::vector<Acc>{{sl.field[div], false, kb, ke}}; });
         const double n3 = (double)N_ * (double)N_ * (double)N_;
-        const T mu = (T)(one_sum() / n3);
-        launch_rows("cg_init", sfk::cg_init_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, mu); }, [&](Slab& sl) {
-            return std::vector<Acc>{{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke}, d_written(sl)};
-        });
-        publish_from_cs(CG_D);
-        const double rho0 = one_sum();
-        double rho = rho0, last = rho0;
+        double rho0, last;
         int status = SF_CG_MAX_ITERS, iters = 0;
-        if (rho0 == 0.0)
-            status = SF_CG_CONVERGED;
-        else if (!std::isfinite(rho0))
-            status = SF_CG_BREAKDOWN;
-        else
-            for (int n = 0; n < max_iters; ++n) {
-                join();  // d's ghost planes
-                launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false>,
-                            [&](Slab& sl) { return cg_args(sl, p, div, T(0)); }, [&](Slab& sl) {
-                                return std::vector<Acc>{{sl.field[CG_D], false, kb - 1, ke + 1}, {sl.field[CG_Q], true, kb, ke}};
-                            });
-                const double delta = one_sum();
-                if (!(delta > 0.0)) {
-                    status = SF_CG_BREAKDOWN;
-                    break;
+        if (m > 0) {
+            cg_scalars<sfk::STAGE_MU>(n3);
+            launch_rows("cg_init", sfk::cg_init_kernel<T, true>, dev_args, [&](Slab& sl) { return with_state(init_acc(sl)); });
+            publish_from_cs(CG_D);
+            cg_scalars<sfk::STAGE_RHO0>(0.0);
+            const sfk::CgState<T>* st = nullptr;
+            int n = 0;
+            do {
+                // past the iteration that stops the solve every kernel of this sequence is a no-op (cg_live), and the
+                // exchange ships d's planes as they were: what is left does not depend on m
+                for (const int end = n + std::min(m, max_iters - n); n < end; ++n) {
+                    join();  // d's ghost planes
+                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false, true>, dev_args,
+                                [&](Slab& sl) { return with_state(apply_acc(sl)); });
+                    cg_scalars<sfk::STAGE_DELTA>(0.0);
+                    launch_rows("cg_update", sfk::cg_update_kernel<T, true>, dev_args,
+                                [&](Slab& sl) { return with_state(update_acc(sl)); });
+                    cg_scalars<sfk::STAGE_RHO>(tol * tol);
+                    launch_rows<false>("cg_direction", sfk::cg_direction_kernel<T, true>, dev_args,
+                                       [&](Slab& sl) { return with_state(direction_acc(sl)); });
+                    publish_from_cs(CG_D);
                 }
-                const T aT = (T)(rho / delta);
-                launch_rows("cg_update", sfk::cg_update_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, aT); },
-                            [&](Slab& sl) {
-                                return std::vector<Acc>{{sl.field[CG_D], false, kb, ke}, {sl.field[CG_Q], false, kb, ke},
-                                                        {sl.field[p], false, kb, ke},    {sl.field[p], true, kb, ke},
-                                                        {sl.field[CG_R], false, kb, ke}, {sl.field[CG_R], true, kb, ke}};
-                            });
-                const double rho_new = one_sum();
-                last = rho_new;
-                iters = n + 1;
-                if (!std::isfinite(rho_new)) {
-                    status = SF_CG_BREAKDOWN;
-                    break;
+                st = &cg_state_read();
+            } while (st->active && n < max_iters);
+            status = st->active ? SF_CG_MAX_ITERS : st->status;
+            iters = st->iterations;
+            rho0 = st->rho0;
+            last = st->last;
+        } else {
+            const T mu = (T)(one_sum() / n3);
+            launch_rows("cg_init", sfk::cg_init_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, mu); }, init_acc);
+            publish_from_cs(CG_D);
+            rho0 = one_sum();
+            double rho = rho0;
+            last = rho0;
+            if (rho0 == 0.0)
+                status = SF_CG_CONVERGED;
+            else if (!std::isfinite(rho0))
+                status = SF_CG_BREAKDOWN;
+            else
+                for (int n = 0; n < max_iters; ++n) {
+                    join();  // d's ghost planes
+                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false>,
+                                [&](Slab& sl) { return cg_args(sl, p, div, T(0)); }, apply_acc);
+                    const double delta = one_sum();
+                    if (!(delta > 0.0)) {
+                        status = SF_CG_BREAKDOWN;
+                        break;
+                    }
+                    const T aT = (T)(rho / delta);
+                    launch_rows("cg_update", sfk::cg_update_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, aT); },
+                                update_acc);
+                    const double rho_new = one_sum();
+                    last = rho_new;
+                    iters = n + 1;
+                    if (!std::isfinite(rho_new)) {
+                        status = SF_CG_BREAKDOWN;
+                        break;
+                    }
+                    if (rho_new <= (tol * tol) * rho0) {
+                        status = SF_CG_CONVERGED;
+                        break;
+                    }
+                    const T bT = (T)(rho_new / rho);
+                    // the one row kernel that writes no row records
+                    launch_rows<false>("cg_direction", sfk::cg_direction_kernel<T>,
+                                       [&](Slab& sl) { return cg_args(sl, p, div, bT); }, direction_acc);
+                    publish_from_cs(CG_D);
+                    rho = rho_new;
                 }
-                if (rho_new <= (tol * tol) * rho0) {
-                    status = SF_CG_CONVERGED;
-                    break;
-                }
-                const T bT = (T)(rho_new / rho);
-                // the one row kernel that writes no row records
-                launch_rows<false>("cg_direction", sfk::cg_direction_kernel<T>,
-                                   [&](Slab& sl) { return cg_args(sl, p, div, bT); }, [&](Slab& sl) {
-                                       return std::vector<Acc>{{sl.field[CG_R], false, kb, ke}, {sl.field[CG_D], false, kb, ke},
-                                                               d_written(sl)};
-                                   });
-                publish_from_cs(CG_D);
-                rho = rho_new;
-            }
+        }
+        host_waits_total_ += host_waits_;
         op_set_bnd(0, p, "cg_set_bnd_p");
         project_second_half(u, v, w, p, div, false);
         note_solve(SF_PRESSURE_CG, status, iters, rho0 == 0.0 ? 0.0 : std::sqrt(last / rho0));
@@ -2906,6 +3034,8 @@ private:
     int mc_vel_ = SF_ADVECT_SEMI_LAGRANGIAN, mc_dens_ = SF_ADVECT_SEMI_LAGRANGIAN;  // advection schemes (SPEC §9)
     int pressure_ = SF_PRESSURE_JACOBI, cg_max_iters_ = 100;  // what vel_step's projections run (SPEC §11)
     double cg_tol_ = 1e-3;
+    int check_every_ = 0, host_waits_ = 0;  // sf_set_pressure_sync; host waits of the last CG projection
+    long long host_waits_total_ = 0;
     sf_pressure_info info_{SF_PRESSURE_JACOBI, SF_CG_MAX_ITERS, 0, -1.0, 0, 0};  // the last projection
     int num_cu_ = 256;
     int nzl_ = 0, lead_ = 0, px_ = 0, nplanes_ = 0;
@@ -2934,7 +3064,10 @@ private:
     void* copy_dst_ = nullptr;
     size_t copy_bytes_ = 0;
     double* red_host_ = nullptr;    // pinned: the plane records of all N planes ([global k - 1][value])
-    double* red_gather_ = nullptr;  // device: the same, the all-gather's buffer (contexts with a communicator)
+    double* red_gather_ = nullptr;  // device: the same, the all-gather's buffer (contexts with a communicator) and what
+                                    // cg_scalars_kernel folds (any context with check_every_ >= 1)
+    sfk::CgState<T>* cg_state_ = nullptr;       // device: the scalars of a CG solve (check_every_ >= 1)
+    sfk::CgState<T>* cg_state_host_ = nullptr;  // pinned: its mirror, filled by cg_state_read()
 };
 
 }  // namespace sfi

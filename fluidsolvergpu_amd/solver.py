@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "sf_set_advection", "sf_advect_maccormack",
     "sf_reduce", "sf_diagnostics_get",
     "sf_set_pressure_solver", "sf_project_cg", "sf_poisson_residual", "sf_pressure_info_get",
+    "sf_set_pressure_sync", "sf_pressure_sync_get",
 )
 
 
@@ -65,6 +66,11 @@ class SfPressureInfo(C.Structure):
     """sf_pressure_info of include/sfgpu.h (docs/SPEC.md §11)."""
     _fields_ = [("solver", C.c_int), ("status", C.c_int), ("iterations", C.c_int), ("rel_residual", C.c_double),
                 ("solves_total", C.c_longlong), ("iterations_total", C.c_longlong)]
+
+
+class SfPressureSync(C.Structure):
+    """sf_pressure_sync of include/sfgpu.h (docs/SPEC.md §11)."""
+    _fields_ = [("check_every", C.c_int), ("host_waits", C.c_int), ("host_waits_total", C.c_longlong)]
 
 
 _ctx = C.c_void_p
@@ -105,6 +111,8 @@ lib.sf_set_pressure_solver.argtypes = [_ctx, C.c_int, C.c_double, C.c_int]
 lib.sf_project_cg.argtypes = [_ctx] + [C.c_int] * 5 + [C.c_double, C.c_int]
 lib.sf_poisson_residual.argtypes = [_ctx, C.c_int, C.c_int, C.POINTER(C.c_double)]
 lib.sf_pressure_info_get.argtypes = [_ctx, C.POINTER(SfPressureInfo)]
+lib.sf_set_pressure_sync.argtypes = [_ctx, C.c_int]
+lib.sf_pressure_sync_get.argtypes = [_ctx, C.POINTER(SfPressureSync)]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -326,6 +334,18 @@ class FluidSolver:
         d = SfPressureInfo()
         self._ck(lib.sf_pressure_info_get(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in SfPressureInfo._fields_}
+
+    def set_pressure_sync(self, check_every=0):
+        """Where a CG solve keeps alpha, beta and its stop tests: 0 (the default) on the host, two waits per iteration;
+        m >= 1 on the device, the host reading the state once per m enqueued iterations. The same bits either way."""
+        self._ck(lib.sf_set_pressure_sync(self._h, int(check_every)))
+
+    @property
+    def pressure_sync(self):
+        """check_every, and the host waits of the last CG projection and of all of them (sf_pressure_sync_get)."""
+        d = SfPressureSync()
+        self._ck(lib.sf_pressure_sync_get(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in SfPressureSync._fields_}
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

@@ -261,7 +261,8 @@ int sf_diagnostics_get(sf_ctx* ctx, sf_diagnostics* out);
  * SF_ERR_INVALID. Status: CONVERGED (also: zero right-hand side, 0 iterations), MAX_ITERS, or BREAKDOWN when a sum is
  * not finite or d.Ad is not > 0 (a NaN in the velocity; fp32 iterated far beyond its residual floor near 1e-4). A
  * breakdown is a status, not an error: the call returns SF_OK, the fields hold what the iterations left, and sf_sync
- * stays SF_OK. The calls are collective and synchronise on the host twice per iteration. */
+ * stays SF_OK. The calls are collective and synchronise on the host twice per iteration, unless sf_set_pressure_sync
+ * has moved the scalars of the solve to the device (below). */
 enum sf_pressure_solver { SF_PRESSURE_JACOBI = 0, SF_PRESSURE_CG = 1 };
 enum sf_cg_status { SF_CG_CONVERGED = 0, SF_CG_MAX_ITERS = 1, SF_CG_BREAKDOWN = 2 };
 typedef struct sf_pressure_info { int solver, status, iterations; double rel_residual;
@@ -270,6 +271,24 @@ int sf_set_pressure_solver(sf_ctx* ctx, int solver, double tol, int max_iters);
 int sf_project_cg(sf_ctx* ctx, int u, int v, int w, int p, int div, double tol, int max_iters);
 int sf_poisson_residual(sf_ctx* ctx, int p, int div, double* rel);
 int sf_pressure_info_get(const sf_ctx* ctx, sf_pressure_info* out);
+
+/* Where the scalars of a CG solve are computed (docs/SPEC.md §11 "Where the scalars are computed").
+ *   sf_set_pressure_sync(check_every): 0 (the default) — the host folds every inner product and passes alpha and beta
+ *       to the next kernel by value: two host waits per iteration. m >= 1 — alpha, beta, the stop tests, status and the
+ *       iteration count live in device memory; the host enqueues min(m, max_iters - n) iterations at a time and reads
+ *       the state back once per batch. Iterations enqueued past the one that stops the solve change nothing, so p, u,
+ *       v, w, iterations, status and rel_residual are the same bits for every check_every. Applies to sf_project_cg
+ *       and to vel_step with SF_PRESSURE_CG; per context and the same on every rank (ranks that disagree issue
+ *       different collectives: that hangs, it is not detected). Negative: SF_ERR_INVALID. The host first looks after a
+ *       whole batch, so a solve that has nothing to do (a zero or non-finite right-hand side) or stops early still pays
+ *       for the rest of its batch as empty launches and unchanged halo exchanges: m near max_iters suits solves that
+ *       run to max_iters, a small m those that may stop at once.
+ *   sf_pressure_sync_get: check_every, and how often the host blocked on a stream inside the last CG projection
+ *       (host_waits: 2 + 2 * iterations with check_every = 0 for a solve that ends on the residual test; one per batch
+ *       otherwise, a single one when check_every >= max_iters) and since sf_create (host_waits_total). */
+typedef struct sf_pressure_sync { int check_every; int host_waits; long long host_waits_total; } sf_pressure_sync;
+int sf_set_pressure_sync(sf_ctx* ctx, int check_every);
+int sf_pressure_sync_get(const sf_ctx* ctx, sf_pressure_sync* out);
 
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);

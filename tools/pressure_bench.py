@@ -10,11 +10,17 @@ under its own time limit (--limit seconds, SIGALRM: the process ends with status
               r, q in, p, r out; direction: r, d in, d out); `ceiling_share` = the time those bytes take at the
               sf_measure_copy_bandwidth of the same run / the measured time. Kernel times: run one case under
               rocprofv3 --kernel-trace --stats; measured time - kernel time is the host's share.
+  sync        the same (t_M - t_0) / iterations on one context per grid and decomposition (one slab, and --sync-slabs
+              logical slabs with the device-local copy transport), for every check_every of --check-every (sf_set_pressure_sync;
+              "max" = max_iters: one host wait per solve; 0 = the host path, the yardstick) one after another in one
+              process, so that the variants see the same machine. The clock stops after sf_sync, so both paths are
+              timed to the end of the gradient subtraction on every slab. host_waits is that of the M-iteration solve.
   step        vel_step + dens_step per step (host wall time of --steps steps between syncs) with Jacobi K = 20 and with
               CG at each --tols, the iterations per step, and sf_poisson_residual / max_div of what the last step left.
 
   python tools/pressure_bench.py                       # iteration: 256^3 fp32, 512^3 fp32, 512^3 fp64; step: 256^3 fp32
   python tools/pressure_bench.py --cases 256:f32 --no-step   # e.g. under rocprofv3 --kernel-trace --stats
+  python tools/pressure_bench.py --sync --cases 64:f32 128:f32 256:f32 512:f32 256:f64   # where the scalars live
 """
 import argparse
 import json
@@ -30,11 +36,11 @@ DT, DIFF, VISC, K = 0.1, 1e-4, 1e-4, 20
 WORDS_PER_ITERATION = 11
 
 
-def context(N, dtype):
+def context(N, dtype, slabs=1):
     from bench import upload_inputs
     from fluidsolvergpu_amd import solver as S
 
-    fs = S.FluidSolver(N, dtype=dtype, iters=K, dt=DT, diff=DIFF, visc=VISC)
+    fs = S.FluidSolver(N, dtype=dtype, iters=K, dt=DT, diff=DIFF, visc=VISC, nslabs_local=slabs)
     upload_inputs(fs, N, DT)
     fs.bind_sources()
     return fs
@@ -68,6 +74,41 @@ def iteration_case(N, dtype, iters, reps):
             "solve_ms": round(tm, 4), "solve_0_iterations_ms": round(t0, 4), "iteration_ms": round(per, 4),
             "copy_gbps": round(gbps, 1), "iteration_compulsory_ms": round(compulsory, 4),
             "ceiling_share_incl_host": round(compulsory / per, 3)}
+
+
+def sync_case(N, dtype, slabs, iters, reps, check_every):
+    """One row per check_every: the time of one iteration with the scalars on the host (0) or on the device."""
+    fs = context(N, dtype, slabs)
+    for _ in range(2):
+        fs.vel_step()
+        fs.dens_step()
+    fs.sync()
+    state = {n: fs.download(n) for n in ("u", "v", "w")}
+
+    def solve(max_iters):
+        for n, a in state.items():
+            fs.upload(n, a)
+        fs.sync()
+        t0 = time.perf_counter()
+        info = fs.project_cg("u", "v", "w", "u0", "v0", 1e-30, max_iters)
+        fs.sync()  # the device path returns with the closing set_bnd, the gradient and other slabs' work in flight
+        return (time.perf_counter() - t0) * 1e3, info, fs.pressure_sync["host_waits"]
+
+    rows = []
+    for m in check_every:
+        fs.set_pressure_sync(iters if m == "max" else int(m))
+        solve(2)
+        t0 = min(solve(0)[0] for _ in range(reps))
+        tm, info, waits = min((solve(iters) for _ in range(reps)), key=lambda r: r[0])
+        rows.append({"case": "sync", "grid": N, "dtype": dtype, "slabs": slabs, "check_every": m,
+                     "iterations": info["iterations"], "status": info["status"], "host_waits": waits,
+                     "solve_ms": round(tm, 4), "solve_0_iterations_ms": round(t0, 4),
+                     "iteration_ms": round((tm - t0) / max(info["iterations"], 1), 5)})
+    base = rows[0]["iteration_ms"]
+    for r in rows:
+        r["vs_first"] = round(r["iteration_ms"] / base, 3) if base > 0 else None
+    fs.close()
+    return rows
 
 
 def step_case(N, dtype, steps, tols, max_iters):
@@ -123,7 +164,17 @@ def main():
     ap.add_argument("--max-iters", type=int, default=200)
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--limit", type=int, default=120)
+    ap.add_argument("--sync", action="store_true", help="only the sync cases")
+    ap.add_argument("--check-every", nargs="+", default=["0", "1", "8", "max"])
+    ap.add_argument("--sync-slabs", type=int, default=4)
     a = ap.parse_args()
+    if a.sync:
+        for c in a.cases:
+            n, t = c.split(":")
+            for slabs in (1, a.sync_slabs):
+                for row in limited(a.limit, lambda: sync_case(int(n), t, slabs, a.iters, a.reps, a.check_every)):
+                    print(json.dumps(row), flush=True)
+        return
     for c in a.cases:
         n, t = c.split(":")
         print(json.dumps(limited(a.limit, lambda: iteration_case(int(n), t, a.iters, a.reps))), flush=True)
