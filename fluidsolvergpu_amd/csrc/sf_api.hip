@@ -240,6 +240,14 @@ int sf_pressure_sync_get(const sf_ctx* ctx, sf_pressure_sync* out) {
     ctx->impl->pressure_sync(out);
     return SF_OK;
 }
+int sf_set_pressure_preconditioner(sf_ctx* ctx, int kind, int sweeps) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_pressure_preconditioner(kind, sweeps); });
+}
+int sf_pressure_preconditioner_get(const sf_ctx* ctx, sf_pressure_preconditioner* out) {
+    if (!ctx || !ctx->impl || !out) return SF_ERR_INVALID;
+    ctx->impl->pressure_preconditioner(out);
+    return SF_OK;
+}
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });
 }

@@ -110,6 +110,8 @@ public:
     virtual void pressure_info(sf_pressure_info* out) const = 0;
     virtual void set_pressure_sync(int check_every) = 0;
     virtual void pressure_sync(sf_pressure_sync* out) const = 0;
+    virtual void set_pressure_preconditioner(int kind, int sweeps) = 0;
+    virtual void pressure_preconditioner(sf_pressure_preconditioner* out) const = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

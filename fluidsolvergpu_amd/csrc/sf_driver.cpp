@@ -26,6 +26,7 @@
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
+//             [--pressure-precond none|jacobi:M]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -42,6 +43,8 @@
 // --pressure-sync M (with --pressure cg): check_every of sf_set_pressure_sync. 0, the default: the host reads every inner
 // product of a solve; M >= 1: the solve's scalars stay on the device and the host looks at them every M iterations. The
 // frames and the monitor lines are the same bits either way.
+// --pressure-precond none|jacobi:M (with --pressure cg): the preconditioner of the CG solve (docs/SPEC.md §11.2), M >= 1
+// undamped Jacobi sweeps from zero per iteration. none, the default: §11 as it stands.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -79,6 +82,7 @@ struct Options {
     int buoyancy_axis = 1;
     int advect_vel = SF_ADVECT_SEMI_LAGRANGIAN, advect_dens = SF_ADVECT_SEMI_LAGRANGIAN;
     int pressure = SF_PRESSURE_JACOBI, cg_max_iters = 100, cg_check_every = 0;
+    int cg_precond = SF_PRECOND_NONE, cg_precond_sweeps = 0;
     double cg_tol = 1e-3;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
@@ -194,6 +198,30 @@ static Options parse(int argc, char** argv) {
                 exit(2);
             }
             o.cg_check_every = (int)m;
+        }
+        else if (s == "--pressure-precond") {
+            // none | jacobi:M
+            const std::string spec = next();
+            const size_t c = spec.find(':');
+            bool ok = spec == "none";
+            if (!ok && spec.substr(0, c) == "jacobi" && c != std::string::npos) {
+                const std::string ms = spec.substr(c + 1);
+                char* end = nullptr;
+                const long m = strtol(ms.c_str(), &end, 10);
+                ok = !ms.empty() && ms.find_first_not_of("0123456789") == std::string::npos && *end == 0 && m >= 1 &&
+                     m <= 1000000;
+                if (ok) {
+                    o.cg_precond = SF_PRECOND_JACOBI;
+                    o.cg_precond_sweeps = (int)m;
+                }
+            } else if (ok) {
+                o.cg_precond = SF_PRECOND_NONE;
+                o.cg_precond_sweeps = 0;
+            }
+            if (!ok) {
+                fprintf(stderr, "--pressure-precond takes none or jacobi:M with M >= 1 sweeps, not %s\n", spec.c_str());
+                exit(2);
+            }
         }
         else if (s == "--maccormack") {
             const std::string which = next();
@@ -379,6 +407,8 @@ static int run(const Options& o) {
     SF_CHECK_RETURN(sf_set_advection(g_ctx, o.advect_vel, o.advect_dens));
     if (o.pressure != SF_PRESSURE_JACOBI) SF_CHECK_RETURN(sf_set_pressure_solver(g_ctx, o.pressure, o.cg_tol, o.cg_max_iters));
     if (o.cg_check_every > 0) SF_CHECK_RETURN(sf_set_pressure_sync(g_ctx, o.cg_check_every));
+    if (o.cg_precond != SF_PRECOND_NONE)
+        SF_CHECK_RETURN(sf_set_pressure_preconditioner(g_ctx, o.cg_precond, o.cg_precond_sweeps));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

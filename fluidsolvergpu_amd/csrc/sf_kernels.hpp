@@ -2963,14 +2963,21 @@ struct CgState {
     double rho0, rho, delta, rho_new, last;
     T mu, aT, bT;
     int status, iterations, active;
+    double gamma;  // r.z of a preconditioned solve (SPEC §11.2); last, so that every other member stays where it was
 };
 enum { CG_ST_CONVERGED = 0, CG_ST_MAX_ITERS = 1, CG_ST_BREAKDOWN = 2 };
-enum { STAGE_MU = 0, STAGE_RHO0 = 1, STAGE_DELTA = 2, STAGE_RHO = 3 };
+// the stages of §11, then those of a preconditioned solve (§11.2): gamma0 and gamma, and the forms of delta and rho'
+// that go with them (alpha = gamma / delta; rho' only counts and tests, beta is the gamma stage's)
+enum { STAGE_MU = 0, STAGE_RHO0 = 1, STAGE_DELTA = 2, STAGE_RHO = 3,
+       STAGE_GAMMA0 = 4, STAGE_GAMMA = 5, STAGE_DELTA_PC = 6, STAGE_RHO_PC = 7 };
 enum { CG_USE_MU = 0, CG_USE_ALPHA = 1, CG_USE_BETA = 2 };
 
 template <class T>
 struct CgArgs {
-    const T* div;  // init: the right-hand side; residual: the right-hand side
+    union {
+        const T* div;  // init: the right-hand side; residual: the right-hand side
+        const T* z;    // preconditioned solve (§11.2): z = M(r), read by the dot and by the direction from z. No kernel
+    };                 // takes both, so z has div's place and the kernels of §11 keep their arguments
     T* p;          // update: p += a*d; residual: read only
     T* r;          // init: written; update: r -= a*q; direction: read
     T* d;          // init: written; apply: read at the seven points; direction: d = r + b*d
@@ -3167,10 +3174,67 @@ __global__ void __launch_bounds__(256) cg_direction_kernel(Geom g, CgArgs<T> A) 
     }
 }
 
+// Preconditioned solve (SPEC §11.2): row records of r.z, with the lane loop and the fold of cg_update's sum. Reads two
+// fields, writes none.
+template <class T, bool DEV = false>
+__global__ void __launch_bounds__(256) cg_dot_kernel(Geom g, CgArgs<T> A, double* __restrict__ rows, int npad) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!cg_live<DEV>(A)) return;
+    if (!reduce_row(g, j, p)) return;
+    const long r = row0(g, j, g.G + p);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    double cs = 0.0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type rv = ldv(A.r + r + i0c), zv = ldv(A.z + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+#pragma unroll
+        for (int e = 0; e < W; ++e) cs = cs + (e < nv ? (double)rv[e] * (double)zv[e] : 0.0);
+    }
+    const double rec = wave_fold(cs, FoldSum());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = rec;
+}
+
+// The direction of a preconditioned solve, with set_bnd(0, d) as in cg_direction_kernel: d = z (INIT, the first
+// direction: cg_init_kernel has left d = r) or d = z + b*d.
+template <class T, bool DEV, bool INIT>
+__global__ void __launch_bounds__(256) cg_direction_z_kernel(Geom g, CgArgs<T> A) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!cg_live<DEV>(A)) return;
+    if (!reduce_row(g, j, p)) return;
+    T b = T(0);
+    if constexpr (!INIT) b = cg_scalar<DEV, CG_USE_BETA>(A);
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type zv = ldv(A.z + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+        if constexpr (INIT) {
+#pragma unroll
+            for (int e = 0; e < W; ++e) out[e] = zv[e];
+        } else {
+            const typename VecT<T>::type dv = ldv(A.d + r + i0c);
+#pragma unroll
+            for (int e = 0; e < W; ++e) out[e] = zv[e] + b * dv[e];
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.d, r, i0, out, nv);
+            emit_shells<T, W>(A.d, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
 // One workgroup: the Total of SPEC §10 over the plane records recs[k0 .. k1) — a +0.0-started sequential sum in
 // increasing global k, the loop at the end of Solver::finish_records — then what the host does with that sum at this
 // stage of a solve, in the same double operations (a correctly rounded divide, a round-to-nearest-even conversion to
-// T). c: N^3 (STAGE_MU) or tol * tol (STAGE_RHO), formed by the host. The records go through LDS so that the one lane
+// T). c: N^3 (STAGE_MU) or tol * tol (STAGE_RHO, STAGE_RHO_PC), formed by the host. The records go through LDS so that the one lane
 // that adds them waits for an addition per record, not for a load. k1 - k0 <= 2048 (Solver::records_alloc).
 // Every stage but the two that start a solve does nothing once the solve has stopped.
 template <class T, int STAGE>
@@ -3201,7 +3265,7 @@ __global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restric
         } else {
             st->aT = (T)(st->rho / s);
         }
-    } else {
+    } else if constexpr (STAGE == STAGE_RHO) {
         st->rho_new = st->last = s;
         st->iterations = st->iterations + 1;
         if (!isfinite(s)) {
@@ -3212,6 +3276,40 @@ __global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restric
             st->active = 0;
         } else {
             st->bT = (T)(s / st->rho);
+            st->rho = s;
+        }
+    } else if constexpr (STAGE == STAGE_GAMMA0) {
+        st->gamma = s;
+        if (!(s > 0.0)) {
+            st->status = CG_ST_BREAKDOWN;
+            st->active = 0;
+        }
+    } else if constexpr (STAGE == STAGE_GAMMA) {
+        if (!(s > 0.0)) {
+            st->status = CG_ST_BREAKDOWN;
+            st->active = 0;
+        } else {
+            st->bT = (T)(s / st->gamma);
+        }
+        st->gamma = s;
+    } else if constexpr (STAGE == STAGE_DELTA_PC) {
+        st->delta = s;
+        if (!(s > 0.0)) {
+            st->status = CG_ST_BREAKDOWN;
+            st->active = 0;
+        } else {
+            st->aT = (T)(st->gamma / s);
+        }
+    } else {  // STAGE_RHO_PC: the count and the stop tests of rho'; beta waits for gamma'
+        st->rho_new = st->last = s;
+        st->iterations = st->iterations + 1;
+        if (!isfinite(s)) {
+            st->status = CG_ST_BREAKDOWN;
+            st->active = 0;
+        } else if (s <= c * st->rho0) {
+            st->status = CG_ST_CONVERGED;
+            st->active = 0;
+        } else {
             st->rho = s;
         }
     }

@@ -24,18 +24,22 @@ class Solver final : public SolverBase {
     static constexpr int W = sfk::VecT<T>::W;
     static constexpr int NSCRATCH = 3;
     // Internal slots: field[WORK_SLOT + f] aliases scratch[f] while an operator whose work field must be addressed by
-    // slot is issued (exchange() and op_advect take slots). Invariant: an internal slot is non-null only while a
-    // ScratchAlias guard lives; guards do not nest; and nothing that swaps scratch pointers with slots (op_lin_solve)
-    // runs under a guard. ~Solver frees the named slots only, so a stale alias could not be freed twice.
+    // slot is issued (exchange() and op_advect take slots). Invariant: one of these NSCRATCH slots is non-null only
+    // while a ScratchAlias guard lives; guards do not nest; and nothing that swaps scratch pointers with slots (an
+    // op_lin_solve without a partner of its own) runs under a guard. ~Solver frees the named slots and the two owning
+    // slots below, so a stale alias could not be freed twice.
     static constexpr int WORK_SLOT = SF_NUM_FIELDS;
     static constexpr int MAG_SLOT = WORK_SLOT;  // |curl u| of the forces (SPEC §8)
     static constexpr int HAT_SLOT = WORK_SLOT;  // + f: `hat`, the first-order result inside advect_mc (SPEC §9)
     static constexpr int CG_R = WORK_SLOT, CG_D = WORK_SLOT + 1, CG_Q = WORK_SLOT + 2;  // CG's r, d, q (SPEC §11)
+    // z = M(r) of a preconditioned solve and the ping-pong partner of its sweeps (SPEC §11.2). No aliases: these two
+    // slots own their buffers, from the first preconditioned solve (pcg_alloc) to ~Solver.
+    static constexpr int CG_Z = WORK_SLOT + NSCRATCH, CG_ZP = CG_Z + 1;
 
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
         sfk::Geom geom{};
-        T* field[SF_NUM_FIELDS + NSCRATCH] = {};
+        T* field[SF_NUM_FIELDS + NSCRATCH + 2] = {};
         T* scratch[NSCRATCH] = {};
         T* snap[4] = {};               // snapshot buffers for asynchronous output
         hipStream_t os = nullptr;      // output (copy) stream
@@ -357,6 +361,7 @@ public:
         if (comm_) ncclCommDestroy(comm_);
         for (Slab& sl : slabs_) {
             for (int f = 0; f < SF_NUM_FIELDS; ++f) free_field(sl.field[f]);  // not the internal slots: aliases
+            for (int f : {CG_Z, CG_ZP}) free_field(sl.field[f]);               // ... but for these two
             for (T*& f : sl.scratch) free_field(f);
             if (sl.d_flag) (void)hipFree(sl.d_flag);
             if (sl.red_rows) (void)hipFree(sl.red_rows);
@@ -1179,6 +1184,17 @@ public:
     void set_pressure_sync(int check_every) override {
         SF_REQUIRE(check_every >= 0, "pressure sync: check_every must be >= 0");
         check_every_ = check_every;
+    }
+    void set_pressure_preconditioner(int kind, int sweeps) override {
+        SF_REQUIRE(kind == SF_PRECOND_NONE || kind == SF_PRECOND_JACOBI, "pressure preconditioner: unknown kind");
+        SF_REQUIRE(sweeps >= (kind == SF_PRECOND_JACOBI ? 1 : 0),
+                   "pressure preconditioner: sweeps must be >= 1 with SF_PRECOND_JACOBI (>= 0 with SF_PRECOND_NONE)");
+        precond_ = kind;
+        precond_sweeps_ = sweeps;
+    }
+    void pressure_preconditioner(sf_pressure_preconditioner* out) const override {
+        out->kind = precond_;
+        out->sweeps = precond_sweeps_;
     }
     void pressure_sync(sf_pressure_sync* out) const override {
         out->check_every = check_every_;
@@ -2376,19 +2392,23 @@ private:
         return plan;
     }
 
-    // K Jacobi sweeps on NF fields at once; scratch buffers are swapped into the slots. dead_ishell, x_zero: see
+    // K Jacobi sweeps on NF fields at once; scratch buffers are swapped into the slots — or, with `partner`, the buffers
+    // of those slots (the preconditioner of SPEC §11.2, whose caller holds the scratch buffers). dead_ishell, x_zero: see
     // plan_solve. src: diffuse with add_source folded in (op_diffuse_src) — the first pass reads the source as its
     // iterate and the field x before add_source, forms x + dt*src in registers and stores it to the x0 slot's buffer
     // (whose old content is dead) for the later passes.
     template <int NF>
     void op_lin_solve(const int (&x)[NF], const int (&x0)[NF], const int (&b)[NF], T a, T c, int K, bool dead_ishell,
-                      bool x_zero = false, const int (*src)[NF] = nullptr) {
+                      bool x_zero = false, const int (*src)[NF] = nullptr, const int (*partner)[NF] = nullptr) {
         static_assert(NF <= NSCRATCH, "not enough scratch buffers");
+        // the buffer a pass of field f writes: the ping-pong partner of x[f]
+        auto xn = [&](Slab& sl, int f) -> T*& { return partner ? sl.field[(*partner)[f]] : sl.scratch[f]; };
         if constexpr (NF > 1) {
             if (solve_apart(K)) {
                 for (int f = 0; f < NF; ++f) {
                     const int xf[1] = {x[f]}, x0f[1] = {x0[f]}, bf[1] = {b[f]}, sf[1] = {src ? (*src)[f] : 0};
-                    op_lin_solve<1>(xf, x0f, bf, a, c, K, dead_ishell, x_zero, src ? &sf : nullptr);
+                    const int pf[1] = {partner ? (*partner)[f] : 0};
+                    op_lin_solve<1>(xf, x0f, bf, a, c, K, dead_ishell, x_zero, src ? &sf : nullptr, partner ? &pf : nullptr);
                 }
                 return;
             }
@@ -2407,7 +2427,7 @@ private:
                 for (int f = 0; f < NF; ++f) {
                     if (p.first != First::ZERO) acc.push_back({sl.field[from_src ? (*src)[f] : x[f]], false, a - s, b + s});
                     acc.push_back({sl.field[from_src ? x[f] : x0[f]], false, a - (s - 1), b + (s - 1)});
-                    acc.push_back({sl.scratch[f], true, lo, hi});
+                    acc.push_back({xn(sl, f), true, lo, hi});
                     if (from_src) acc.push_back({sl.field[x0[f]], true, a, b});
                 }
             };
@@ -2416,7 +2436,7 @@ private:
                 for (int f = 0; f < NF; ++f) {
                     A.x[f] = L.sl.field[from_src ? (*src)[f] : x[f]];  // iterate (the source: Stam's initial guess)
                     A.x0[f] = L.sl.field[from_src ? x[f] : x0[f]];     // right-hand side (the field before add_source)
-                    A.xn[f] = L.sl.scratch[f];
+                    A.xn[f] = xn(L.sl, f);
                     if (from_src) A.x0out[f] = L.sl.field[x0[f]];  // right-hand side x + dt*src for the later passes
                     A.b[f] = b[f];
                 }
@@ -2431,7 +2451,7 @@ private:
             if (from_src) rhs_on_ghost_planes<NF>(x, x0, *src, p.depth);
             // the new iterate becomes the field; the old buffer becomes scratch
             for (Slab& sl : slabs_)
-                for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
+                for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], xn(sl, f));
             exchange<NF>(x);
         }
     }
@@ -2700,6 +2720,8 @@ private:
     // waits for the sum that follows. Two host synchronisations per iteration (finish_records) — or, with
     // check_every_ = m >= 1, none: every sum is folded by cg_scalars(), which leaves alpha, beta and the outcome of the
     // stop tests in cg_state_ for the kernels that follow, and the host reads that state once per m iterations.
+    // With a preconditioner selected (SPEC §11.2) every iteration also runs z = M(r) (op_precondition) and a third sum,
+    // r.z: three host synchronisations per iteration on the host path.
     double one_sum() {
         double r[1];
         finish_records(1, 1, 0, r);
@@ -2781,6 +2803,46 @@ private:
         A.s = s;
         return A;
     }
+    // ---- its Jacobi-sweep preconditioner (SPEC §11.2) ----
+    void pcg_alloc() {
+        for (Slab& sl : slabs_)
+            for (int f : {CG_Z, CG_ZP})
+                if (!sl.field[f]) sl.field[f] = alloc_field();
+    }
+    // the argument of the kernels that read z (it has div's place)
+    sfk::CgArgs<T> cg_z_args(Slab& sl, T s) const {
+        sfk::CgArgs<T> A{};
+        A.z = sl.field[CG_Z];
+        A.r = sl.field[CG_R];
+        A.d = sl.field[CG_D];
+        A.s = s;
+        return A;
+    }
+    sfk::CgArgs<T> cg_z_dev_args(Slab& sl) const {
+        sfk::CgArgs<T> A = cg_z_args(sl, T(0));
+        A.st = cg_state_;
+        return A;
+    }
+    // z = M(r): z = +0, then lin_solve(0, z, r, 1, 6, sweeps) as the pass planner lays any solve out, ping-pong between
+    // the two owning slots. A pass of s fused sweeps reads its right-hand side s - 1 planes beyond its own, so r's ghost
+    // planes go first; it runs whether or not the solve is still active (the Jacobi kernels know no state) and leaves the
+    // compute streams joined for the row kernel that follows.
+    void op_precondition(int sweeps) {
+        publish_from_cs(CG_R);
+        // as in op_project: a fused first pass takes the zero iterate as literal zeros, any other reads it
+        const bool implicit_zero = can_fuse2() && sweeps >= 2 && sw_.zero_skip;
+        if (!implicit_zero) {
+            join();
+            for (Slab& sl : slabs_) {
+                SF_HIP(hipMemsetAsync(sl.field[CG_Z], 0, (size_t)field_elems_ * sizeof(T), sl.cs));
+                tr_whole("zero_z", sl, {}, {sl.field[CG_Z]});
+            }
+        }
+        const int zs[1] = {CG_Z}, rs[1] = {CG_R}, b0[1] = {0}, zp[1] = {CG_ZP};
+        op_lin_solve<1>(zs, rs, b0, T(1), T(6), sweeps, false, implicit_zero, nullptr, &zp);
+        join();
+    }
+
     void op_set_bnd(int b, int x, const char* trace_name) {
         join();
         for (Slab& sl : slabs_) {
@@ -2805,6 +2867,8 @@ private:
                           sfk::CG_ST_BREAKDOWN == SF_CG_BREAKDOWN, "CgState::status holds sf_cg_status values");
         const int m = check_every_;  // 0: the scalars on the host; m >= 1: on the device, read back every m iterations
         if (m > 0) cg_state_alloc();
+        const int pm = precond_ == SF_PRECOND_JACOBI ? precond_sweeps_ : 0;  // sweeps of z = M(r); 0: §11 as it stands
+        if (pm > 0) pcg_alloc();
         host_waits_ = 0;
         ScratchAlias work_slots(slabs_, 3);
         const int kb = G_, ke = G_ + nzl_;
@@ -2835,6 +2899,14 @@ private:
             return a;
         };
         auto dev_args = [&](Slab& sl) { return cg_dev_args(sl, p, div); };
+        // ... and those of the preconditioned solve (z is whichever buffer the last pass of M(r) left in its slot)
+        auto dot_acc = [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[CG_R], false, kb, ke}, {sl.field[CG_Z], false, kb, ke}};
+        };
+        auto direction_z_acc = [&](Slab& sl) {
+            return std::vector<Acc>{{sl.field[CG_Z], false, kb, ke}, {sl.field[CG_D], false, kb, ke}, d_written(sl)};
+        };
+        auto z_dev_args = [&](Slab& sl) { return cg_z_dev_args(sl); };
 
         project_first_half(u, v, w, p, div, mirror_u, false, true);
         join();
@@ -2844,7 +2916,44 @@ private:
         const double n3 = (double)N_ * (double)N_ * (double)N_;
         double rho0, last;
         int status = SF_CG_MAX_ITERS, iters = 0;
-        if (m > 0) {
+        if (m > 0 && pm > 0) {
+            // SPEC §11.2 with the scalars on the device: the sweeps of M(r) run in every enqueued iteration, every other
+            // kernel is a no-op once the solve has stopped
+            cg_scalars<sfk::STAGE_MU>(n3);
+            launch_rows("cg_init", sfk::cg_init_kernel<T, true>, dev_args, [&](Slab& sl) { return with_state(init_acc(sl)); });
+            cg_scalars<sfk::STAGE_RHO0>(0.0);
+            op_precondition(pm);
+            launch_rows("cg_dot", sfk::cg_dot_kernel<T, true>, z_dev_args, [&](Slab& sl) { return with_state(dot_acc(sl)); });
+            cg_scalars<sfk::STAGE_GAMMA0>(0.0);
+            launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, true, true>, z_dev_args,
+                               [&](Slab& sl) { return with_state(direction_z_acc(sl)); });
+            publish_from_cs(CG_D);
+            const sfk::CgState<T>* st = nullptr;
+            int n = 0;
+            do {
+                for (const int end = n + std::min(m, max_iters - n); n < end; ++n) {
+                    join();  // d's ghost planes
+                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false, true>, dev_args,
+                                [&](Slab& sl) { return with_state(apply_acc(sl)); });
+                    cg_scalars<sfk::STAGE_DELTA_PC>(0.0);
+                    launch_rows("cg_update", sfk::cg_update_kernel<T, true>, dev_args,
+                                [&](Slab& sl) { return with_state(update_acc(sl)); });
+                    cg_scalars<sfk::STAGE_RHO_PC>(tol * tol);
+                    op_precondition(pm);
+                    launch_rows("cg_dot", sfk::cg_dot_kernel<T, true>, z_dev_args,
+                                [&](Slab& sl) { return with_state(dot_acc(sl)); });
+                    cg_scalars<sfk::STAGE_GAMMA>(0.0);
+                    launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, true, false>, z_dev_args,
+                                       [&](Slab& sl) { return with_state(direction_z_acc(sl)); });
+                    publish_from_cs(CG_D);
+                }
+                st = &cg_state_read();
+            } while (st->active && n < max_iters);
+            status = st->active ? SF_CG_MAX_ITERS : st->status;
+            iters = st->iterations;
+            rho0 = st->rho0;
+            last = st->last;
+        } else if (m > 0) {
             cg_scalars<sfk::STAGE_MU>(n3);
             launch_rows("cg_init", sfk::cg_init_kernel<T, true>, dev_args, [&](Slab& sl) { return with_state(init_acc(sl)); });
             publish_from_cs(CG_D);
@@ -2872,6 +2981,63 @@ private:
             iters = st->iterations;
             rho0 = st->rho0;
             last = st->last;
+        } else if (pm > 0) {
+            // SPEC §11.2 with the scalars on the host: three host waits per iteration
+            const T mu = (T)(one_sum() / n3);
+            launch_rows("cg_init", sfk::cg_init_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, mu); }, init_acc);
+            rho0 = one_sum();
+            last = rho0;
+            auto gamma_sum = [&] {
+                op_precondition(pm);
+                launch_rows("cg_dot", sfk::cg_dot_kernel<T>, [&](Slab& sl) { return cg_z_args(sl, T(0)); }, dot_acc);
+                return one_sum();
+            };
+            double gamma = 0.0;
+            if (rho0 == 0.0)
+                status = SF_CG_CONVERGED;
+            else if (!std::isfinite(rho0))
+                status = SF_CG_BREAKDOWN;
+            else if (!((gamma = gamma_sum()) > 0.0))
+                status = SF_CG_BREAKDOWN;
+            else {
+                launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, false, true>,
+                                   [&](Slab& sl) { return cg_z_args(sl, T(0)); }, direction_z_acc);
+                publish_from_cs(CG_D);
+                for (int n = 0; n < max_iters; ++n) {
+                    join();  // d's ghost planes
+                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false>,
+                                [&](Slab& sl) { return cg_args(sl, p, div, T(0)); }, apply_acc);
+                    const double delta = one_sum();
+                    if (!(delta > 0.0)) {
+                        status = SF_CG_BREAKDOWN;
+                        break;
+                    }
+                    const T aT = (T)(gamma / delta);
+                    launch_rows("cg_update", sfk::cg_update_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, aT); },
+                                update_acc);
+                    const double rho_new = one_sum();
+                    last = rho_new;
+                    iters = n + 1;
+                    if (!std::isfinite(rho_new)) {
+                        status = SF_CG_BREAKDOWN;
+                        break;
+                    }
+                    if (rho_new <= (tol * tol) * rho0) {
+                        status = SF_CG_CONVERGED;
+                        break;
+                    }
+                    const double gamma_new = gamma_sum();
+                    if (!(gamma_new > 0.0)) {
+                        status = SF_CG_BREAKDOWN;
+                        break;
+                    }
+                    const T bT = (T)(gamma_new / gamma);
+                    launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, false, false>,
+                                       [&](Slab& sl) { return cg_z_args(sl, bT); }, direction_z_acc);
+                    publish_from_cs(CG_D);
+                    gamma = gamma_new;
+                }
+            }
         } else {
             const T mu = (T)(one_sum() / n3);
             launch_rows("cg_init", sfk::cg_init_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, mu); }, init_acc);
@@ -3035,6 +3201,7 @@ private:
     int pressure_ = SF_PRESSURE_JACOBI, cg_max_iters_ = 100;  // what vel_step's projections run (SPEC §11)
     double cg_tol_ = 1e-3;
     int check_every_ = 0, host_waits_ = 0;  // sf_set_pressure_sync; host waits of the last CG projection
+    int precond_ = SF_PRECOND_NONE, precond_sweeps_ = 0;  // sf_set_pressure_preconditioner (SPEC §11.2)
     long long host_waits_total_ = 0;
     sf_pressure_info info_{SF_PRESSURE_JACOBI, SF_CG_MAX_ITERS, 0, -1.0, 0, 0};  // the last projection
     int num_cu_ = 256;

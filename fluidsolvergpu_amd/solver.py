@@ -29,6 +29,8 @@ REDUCE_OPS = {"sum": SF_RED_SUM, "sum_sq": SF_RED_SUM_SQ, "min": SF_RED_MIN, "ma
               "max_abs": SF_RED_MAX_ABS, "count_nonfinite": SF_RED_COUNT_NONFINITE}
 SF_PRESSURE_JACOBI, SF_PRESSURE_CG = 0, 1
 PRESSURE_SOLVERS = {"jacobi": SF_PRESSURE_JACOBI, "cg": SF_PRESSURE_CG}
+SF_PRECOND_NONE, SF_PRECOND_JACOBI = 0, 1
+PRECONDITIONERS = {"none": SF_PRECOND_NONE, "jacobi": SF_PRECOND_JACOBI}
 SF_CG_CONVERGED, SF_CG_MAX_ITERS, SF_CG_BREAKDOWN = 0, 1, 2
 CG_STATUS = ("converged", "max_iters", "breakdown")
 TRANSPORTS = ("none", "copy", "rccl", "rccl-self", "loopback")
@@ -47,6 +49,7 @@ ABI_SYMBOLS = (
     "sf_reduce", "sf_diagnostics_get",
     "sf_set_pressure_solver", "sf_project_cg", "sf_poisson_residual", "sf_pressure_info_get",
     "sf_set_pressure_sync", "sf_pressure_sync_get",
+    "sf_set_pressure_preconditioner", "sf_pressure_preconditioner_get",
 )
 
 
@@ -71,6 +74,11 @@ class SfPressureInfo(C.Structure):
 class SfPressureSync(C.Structure):
     """sf_pressure_sync of include/sfgpu.h (docs/SPEC.md §11)."""
     _fields_ = [("check_every", C.c_int), ("host_waits", C.c_int), ("host_waits_total", C.c_longlong)]
+
+
+class SfPressurePreconditioner(C.Structure):
+    """sf_pressure_preconditioner of include/sfgpu.h (docs/SPEC.md §11.2)."""
+    _fields_ = [("kind", C.c_int), ("sweeps", C.c_int)]
 
 
 _ctx = C.c_void_p
@@ -113,6 +121,8 @@ lib.sf_poisson_residual.argtypes = [_ctx, C.c_int, C.c_int, C.POINTER(C.c_double
 lib.sf_pressure_info_get.argtypes = [_ctx, C.POINTER(SfPressureInfo)]
 lib.sf_set_pressure_sync.argtypes = [_ctx, C.c_int]
 lib.sf_pressure_sync_get.argtypes = [_ctx, C.POINTER(SfPressureSync)]
+lib.sf_set_pressure_preconditioner.argtypes = [_ctx, C.c_int, C.c_int]
+lib.sf_pressure_preconditioner_get.argtypes = [_ctx, C.POINTER(SfPressurePreconditioner)]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -346,6 +356,20 @@ class FluidSolver:
         d = SfPressureSync()
         self._ck(lib.sf_pressure_sync_get(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in SfPressureSync._fields_}
+
+    def set_pressure_preconditioner(self, kind="none", sweeps=0):
+        """The preconditioner of the CG solve (SPEC §11.2): "none" (the default: §11 exactly) or "jacobi" with
+        sweeps = m >= 1 undamped Jacobi sweeps from zero as z = M(r). An even m needs about sqrt(2 m) times fewer
+        iterations; the stop test stays on r.r."""
+        kid = PRECONDITIONERS[kind] if isinstance(kind, str) else int(kind)
+        self._ck(lib.sf_set_pressure_preconditioner(self._h, kid, int(sweeps)))
+
+    @property
+    def pressure_preconditioner(self):
+        """kind (SF_PRECOND_*) and sweeps as last set (sf_pressure_preconditioner_get)."""
+        d = SfPressurePreconditioner()
+        self._ck(lib.sf_pressure_preconditioner_get(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in SfPressurePreconditioner._fields_}
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

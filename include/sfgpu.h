@@ -290,6 +290,25 @@ typedef struct sf_pressure_sync { int check_every; int host_waits; long long hos
 int sf_set_pressure_sync(sf_ctx* ctx, int check_every);
 int sf_pressure_sync_get(const sf_ctx* ctx, sf_pressure_sync* out);
 
+/* Preconditioner of the CG solve (docs/SPEC.md §11.2). Unpreconditioned CG needs on the order of N iterations.
+ *   sf_set_pressure_preconditioner(kind, sweeps): SF_PRECOND_NONE (the default; sweeps is kept but not used) is §11
+ *       exactly, with the same launches. SF_PRECOND_JACOBI with sweeps = m >= 1: z = M(r) is m undamped Jacobi sweeps
+ *       on A z = r from z = 0 — §3's lin_solve(0, z, r, 1, 6, m) bit for bit, run by the kernels of sf_project — a
+ *       symmetric polynomial in A that is positive on A's range. alpha = (r.z) / (d.Ad), beta = (r.z)' / (r.z),
+ *       d = z + beta d; the stop test, rel_residual and sf_pressure_info stay on r.r, so tol means the same with and
+ *       without a preconditioner. An even m cuts the iterations by about sqrt(2 m) (m = 4: about 2.8 x, m = 8: about
+ *       4 x); an odd m is worse than the even one below it and m = 1 is a plain scaling (the iterations of NONE).
+ *       m = 8 — two passes of the marching kernel on the grids it takes — is the measured optimum (docs/NEXT.md); m = 4
+ *       runs as two pair passes and costs almost as much. BREAKDOWN also when r.z is not > 0. The first
+ *       preconditioned solve allocates two more work fields per slab. Same bits for every decomposition, transport and
+ *       check_every; per context and the same on every rank. An unknown kind, or JACOBI with sweeps < 1 (NONE with
+ *       sweeps < 0): SF_ERR_INVALID, and the setting is unchanged.
+ *   sf_pressure_preconditioner_get: {kind, sweeps} as last set. */
+enum sf_pressure_precond { SF_PRECOND_NONE = 0, SF_PRECOND_JACOBI = 1 };
+typedef struct sf_pressure_preconditioner { int kind; int sweeps; } sf_pressure_preconditioner;
+int sf_set_pressure_preconditioner(sf_ctx* ctx, int kind, int sweeps);
+int sf_pressure_preconditioner_get(const sf_ctx* ctx, sf_pressure_preconditioner* out);
+
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);
 int sf_set_coefficients(sf_ctx* ctx, double dt, double diff, double visc);

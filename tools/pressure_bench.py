@@ -15,12 +15,17 @@ under its own time limit (--limit seconds, SIGALRM: the process ends with status
               "max" = max_iters: one host wait per solve; 0 = the host path, the yardstick) one after another in one
               process, so that the variants see the same machine. The clock stops after sf_sync, so both paths are
               timed to the end of the gradient subtraction on every slab. host_waits is that of the M-iteration solve.
+  precond     (--precond 0,2,4,8) one context per grid; for every sweep count M of the Jacobi preconditioner of SPEC §11.2
+              (0: none): the time of one iteration as in `sync` (with --sync M' the scalars on the device, read every M'
+              iterations; without, on the host), the iterations to tol = 1e-3 from the same state and the time of that
+              projection, and, for --step-case, the step with CG at each --tols.
   step        vel_step + dens_step per step (host wall time of --steps steps between syncs) with Jacobi K = 20 and with
               CG at each --tols, the iterations per step, and sf_poisson_residual / max_div of what the last step left.
 
   python tools/pressure_bench.py                       # iteration: 256^3 fp32, 512^3 fp32, 512^3 fp64; step: 256^3 fp32
   python tools/pressure_bench.py --cases 256:f32 --no-step   # e.g. under rocprofv3 --kernel-trace --stats
   python tools/pressure_bench.py --sync --cases 64:f32 128:f32 256:f32 512:f32 256:f64   # where the scalars live
+  python tools/pressure_bench.py --precond 0,2,4,8 --sync 8 --cases 64:f32 128:f32 256:f32 512:f32 256:f64
 """
 import argparse
 import json
@@ -111,12 +116,58 @@ def sync_case(N, dtype, slabs, iters, reps, check_every):
     return rows
 
 
-def step_case(N, dtype, steps, tols, max_iters):
+def set_precond(fs, sweeps):
+    if sweeps > 0:
+        fs.set_pressure_preconditioner("jacobi", sweeps)
+    else:
+        fs.set_pressure_preconditioner("none")
+
+
+def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters):
+    """One row per sweep count: an iteration's time, and the projection to tol = 1e-3 from the same state."""
+    fs = context(N, dtype)
+    for _ in range(2):
+        fs.vel_step()
+        fs.dens_step()
+    fs.sync()
+    state = {n: fs.download(n) for n in ("u", "v", "w")}
+    fs.set_pressure_sync(check_every)
+
+    def solve(tol, limit):
+        for n, a in state.items():
+            fs.upload(n, a)
+        fs.sync()
+        t0 = time.perf_counter()
+        info = fs.project_cg("u", "v", "w", "u0", "v0", tol, limit)
+        fs.sync()
+        return (time.perf_counter() - t0) * 1e3, info
+
+    rows = []
+    for m in sweeps:
+        set_precond(fs, m)
+        solve(1e-30, 2)
+        t0 = min(solve(1e-30, 0)[0] for _ in range(reps))
+        tm, info = min((solve(1e-30, iters) for _ in range(reps)), key=lambda r: r[0])
+        tp, done = min((solve(1e-3, max_iters) for _ in range(reps)), key=lambda r: r[0])
+        rows.append({"case": "precond", "grid": N, "dtype": dtype, "sweeps": m, "check_every": check_every,
+                     "iteration_ms": round((tm - t0) / max(info["iterations"], 1), 5),
+                     "iterations_1e-3": done["iterations"], "status_1e-3": done["status"],
+                     "rel_residual": done["rel_residual"], "poisson_residual": fs.poisson_residual("u0", "v0"),
+                     "projection_ms": round(tp, 4)})
+    fs.close()
+    return rows
+
+
+def step_case(N, dtype, steps, tols, max_iters, precond=0, check_every=0):
     out = []
     for tol in [None] + tols:
+        if tol is None and precond > 0:
+            continue  # (the Jacobi step has no preconditioner: timed once, with precond = 0)
         fs = context(N, dtype)
         if tol is not None:
             fs.set_pressure_solver("cg", tol, max_iters)
+            fs.set_pressure_sync(check_every)
+            set_precond(fs, precond)
         for _ in range(3):
             fs.vel_step()
             fs.dens_step()
@@ -133,6 +184,7 @@ def step_case(N, dtype, steps, tols, max_iters):
             its = (fs.pressure_info()["iterations_total"] - i0) / (2.0 * steps)
         info = fs.pressure_info()
         out.append({"case": "step", "grid": N, "dtype": dtype, "solver": "jacobi" if tol is None else "cg", "tol": tol,
+                    "precond_sweeps": precond, "check_every": check_every,
                     "step_ms": round(best, 4), "iterations_per_projection": round(its, 2), "last_status": info["status"],
                     "last_rel_residual": info["rel_residual"], "poisson_residual": fs.poisson_residual("u0", "v0"),
                     "max_div": fs.diagnostics()["max_div"]})
@@ -164,10 +216,25 @@ def main():
     ap.add_argument("--max-iters", type=int, default=200)
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--limit", type=int, default=120)
-    ap.add_argument("--sync", action="store_true", help="only the sync cases")
+    ap.add_argument("--sync", nargs="?", const=True, default=False,
+                    help="alone: only the sync cases; with --precond: --sync M keeps the scalars on the device")
+    ap.add_argument("--precond", default=None, help="comma-separated sweep counts, e.g. 0,2,4,8: only the precond cases")
     ap.add_argument("--check-every", nargs="+", default=["0", "1", "8", "max"])
     ap.add_argument("--sync-slabs", type=int, default=4)
     a = ap.parse_args()
+    if a.precond is not None:
+        sweeps = [int(m) for m in a.precond.split(",")]
+        every = 0 if a.sync in (False, True) else int(a.sync)
+        for c in a.cases:
+            n, t = c.split(":")
+            for row in limited(a.limit, lambda: precond_case(int(n), t, a.iters, a.reps, sweeps, every, a.max_iters)):
+                print(json.dumps(row), flush=True)
+        if not a.no_step:
+            n, t = a.step_case.split(":")
+            for m in sweeps:
+                for row in limited(3 * a.limit, lambda: step_case(int(n), t, a.steps, a.tols, a.max_iters, m, every)):
+                    print(json.dumps(row), flush=True)
+        return
     if a.sync:
         for c in a.cases:
             n, t = c.split(":")
