@@ -579,6 +579,9 @@ public:
         int mc_vel, mc_dens;  // advection schemes (SPEC §9): they decide which launches are captured
         int bound[4];
         hipGraphExec_t exec;
+        // what the captured body noted of its projections (note_solve is host code: a replay has to say it again)
+        sf_pressure_info info;
+        long long solves, iterations;
     };
     std::vector<T*> pointer_state() const {
         std::vector<T*> st;
@@ -611,9 +614,16 @@ public:
                 std::equal(e.bound, e.bound + 4, bound_) && e.before == before) {
                 SF_HIP(hipGraphLaunch(e.exec, sl.cs));
                 apply_state(e.after);
+                if (e.solves > 0) {  // sf_pressure_info: the step's last projection, and every projection counted
+                    const long long solves = info_.solves_total + e.solves, iters = info_.iterations_total + e.iterations;
+                    info_ = e.info;
+                    info_.solves_total = solves;
+                    info_.iterations_total = iters;
+                }
                 return;
             }
         hipGraph_t graph = nullptr;
+        const sf_pressure_info info_before = info_;
         SF_HIP(hipStreamBeginCapture(sl.cs, hipStreamCaptureModeThreadLocal));
         try {
             body();
@@ -621,6 +631,7 @@ public:
             (void)hipStreamEndCapture(sl.cs, &graph);
             if (graph) (void)hipGraphDestroy(graph);
             apply_state(before);
+            info_ = info_before;
             throw;
         }
         SF_HIP(hipStreamEndCapture(sl.cs, &graph));
@@ -639,6 +650,9 @@ public:
         e.mc_vel = mc_vel_;
         e.mc_dens = mc_dens_;
         std::copy(bound_, bound_ + 4, e.bound);
+        e.info = info_;
+        e.solves = info_.solves_total - info_before.solves_total;
+        e.iterations = info_.iterations_total - info_before.iterations_total;
         SF_HIP(hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0));
         SF_HIP(hipGraphDestroy(graph));
         graph_cache_.push_back(e);

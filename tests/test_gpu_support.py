@@ -1,6 +1,6 @@
 """The shared comparison and the context factory of tests/gpu_support.py hold what the GPU suites rely on (no GPU
 needed): assert_same_bits sees a signed zero, one ulp and a NaN payload; make passes exactly the keyword arguments the
-suites passed before they shared it."""
+suites passed before they shared it; traced_plans reads the pass plan of a preconditioned solve out of a schedule trace."""
 import numpy as np
 import pytest
 
@@ -96,3 +96,74 @@ def test_the_solver_flag_is_the_literal_of_slab_kw():
 
     assert solver.SF_FLAG_RCCL_SELF == G.slab_kw("rccl-self", 2)["flags"]
     assert G.NAMES == solver.FIELD_NAMES
+
+
+# ---- traced_plans on a hand-written trace ---------------------------------------------------------------------------
+def op(name, slab, stream, *acc):
+    return {"t": "op", "name": name, "slab": slab, "stream": stream, "acc": [list(a) for a in acc]}
+
+
+def two_slab_trace():
+    """A context of two slabs of 36 planes on G = 4 ghost planes (buffers: r 0, z 1, its partner 2 on slab 0; 5, 6, 7 on
+    slab 1). First M(r): 4Z 3+4 2 — the boundary launch of the three-sweep pass reaches 8 planes into the slab, the pair
+    snaps back to 4. Second M(r): zero_z, then 4C 4+4. Rows that the parser must skip stand in between."""
+    ctx = {"t": "ctx", "N": 72, "P": 2, "L": 2, "rank": 0, "G": 4, "nzl": 36, "np": 44, "trap": 5, "hs_is_bs": 0, "inject": 0}
+    dot = [op("cg_dot", s, "cs", ("r", 5 * s, 4, 40), ("r", 5 * s + 1, 4, 40)) for s in (0, 1)]
+    rows = [ctx, op("jacobi2", 0, "cs", ("w", 9, 3, 41)),  # (a Jacobi solve before the first r.z: no part of any M)
+            *dot,
+            op("cg_apply_dot", 0, "cs", ("r", 3, 3, 41)),
+            op("jacobi4", 0, "bs", ("r", 0, 1, 11), ("w", 2, 3, 8), ("r", 0, 33, 43), ("w", 2, 36, 40)),
+            op("jacobi4", 1, "bs", ("r", 5, 1, 11), ("w", 7, 4, 8), ("r", 5, 33, 43), ("w", 7, 36, 41)),
+            op("jacobi4", 0, "cs", ("r", 0, 5, 39), ("w", 2, 8, 36)),
+            {"t": "xchg", "seq": 7, "G": 4, "fields": [12]},
+            op("halo", 0, "hs", ("r", 7, 4, 8), ("w", 2, 40, 44)),
+            {"t": "rec", "slab": 0, "stream": "bs", "ev": "boundary"},
+            op("jacobi3", 0, "bs", ("r", 2, 0, 15), ("r", 0, 1, 14), ("w", 1, 3, 12), ("r", 2, 29, 43), ("w", 1, 32, 40)),
+            op("jacobi3", 0, "cs", ("r", 2, 9, 35), ("w", 1, 12, 32)),
+            op("jacobi2", 0, "bs", ("r", 1, 2, 10), ("w", 2, 3, 8), ("w", 2, 36, 40)),
+            op("jacobi2", 0, "cs", ("r", 1, 6, 38), ("w", 2, 8, 36)),
+            *dot,
+            op("zero_z", 0, "cs", ("w", 2, 0, 44)),
+            op("jacobi4", 0, "bs", ("r", 2, 0, 12), ("w", 1, 3, 8), ("w", 1, 36, 40)),
+            op("jacobi4", 0, "cs", ("r", 2, 4, 40), ("w", 1, 8, 36)),
+            op("jacobi4", 0, "bs", ("r", 1, 0, 16), ("w", 2, 3, 12), ("w", 2, 32, 40)),
+            op("jacobi4", 0, "cs", ("r", 1, 8, 36), ("w", 2, 12, 32)),
+            *dot,
+            op("jacobi1", 0, "cs", ("w", 1, 3, 41))]  # (after the last r.z: an unfinished window is no plan)
+    return rows
+
+
+def test_traced_plans(tmp_path):
+    import json
+
+    path = tmp_path / "trace.jsonl"
+    one_slab = [{"t": "ctx", "N": 40, "P": 1, "G": 1, "trap": 5},
+                op("cg_dot", 0, "cs"), op("zero_z", 0, "cs", ("w", 1, 0, 42)), op("jacobi1", 0, "cs", ("w", 2, 0, 42)),
+                op("cg_dot", 0, "cs"),
+                # two passes of one name: told apart by the buffer they write; pairs on G = 1 are two planes deep
+                op("jacobi2", 0, "cs", ("w", 2, 0, 42)), op("jacobi2", 0, "cs", ("w", 1, 0, 42)),
+                op("jacobi3", 0, "cs", ("w", 2, 0, 42)), op("jacobi1", 0, "cs", ("w", 1, 0, 42)),
+                op("cg_dot", 0, "cs")]
+    path.write_text("".join(json.dumps(r) + "\n" for r in two_slab_trace() + one_slab))
+    (ctx2, plans2), (ctx1, plans1) = G.traced_plans(str(path))
+    assert (ctx2["G"], ctx2["P"], ctx2["trap"]) == (4, 2, 5) and plans2 == ["4Z 3+4 2", "4C 4+4"]
+    assert ctx1["P"] == 1 and plans1 == ["1C", "2Z 2 3 1"]
+
+
+def test_passes_of_M_on_a_live_trace(tmp_path):
+    """slab0_ops leaves out other slabs, other records and a line still being written; passes_of_M counts the passes
+    that write the two buffers cg_dot reads z from, and no pass of another solve."""
+    import json
+
+    rows = [{"t": "ctx", "N": 40, "P": 1, "G": 1, "trap": 5},
+            op("jacobi2", 0, "cs", ("r", 3, 0, 42), ("w", 9, 0, 42)),   # diffuse: its buffers are not z's
+            op("jacobi2", 0, "cs", ("w", 1, 0, 42)), op("cg_dot", 0, "cs", ("r", 0, 1, 41), ("r", 1, 1, 41), ("w", 7, 0, 42)),
+            {"t": "rec", "slab": 0, "stream": "cs", "ev": "cs_mark"}, op("jacobi1", 1, "cs", ("w", 2, 0, 42)),
+            op("jacobi2", 0, "cs", ("w", 2, 0, 42)), op("cg_dot", 0, "cs", ("r", 0, 1, 41), ("r", 2, 1, 41), ("w", 7, 0, 42)),
+            op("jacobi2", 0, "cs", ("w", 1, 0, 42)), op("cg_dot", 0, "cs", ("r", 0, 1, 41), ("r", 1, 1, 41), ("w", 7, 0, 42))]
+    path = tmp_path / "trace.jsonl"
+    path.write_text("".join(json.dumps(r) + "\n" for r in rows) + '{"t":"op","name":"jaco')
+    ops = G.slab0_ops(str(path))
+    assert len(ops) == 7
+    assert G.passes_of_M(ops) == (3, {1, 2}, 1)
+    assert G.passes_of_M(ops[:3]) == (1, {1}, 1)

@@ -21,7 +21,7 @@ import pytest
 import diagnostics_ref as D
 import pressure_cg_ref as R
 import shape_cases as C
-from gpu_support import S, assert_same_bits, check_solve, make, random_fields, upload_all
+from gpu_support import CG_STEP_SETTINGS, S, assert_same_bits, check_solve, make, random_fields, upload_all
 
 pytestmark = pytest.mark.gpu
 
@@ -151,10 +151,7 @@ def test_edges_of_the_stop_tests(N, P, transport, dtype):
 
 
 # ---- (e) -----------------------------------------------------------------------------------------------------------
-SETTINGS = [{"SF_MARCH_MINCELLS_K": "0"},  # K = 9: the marching first pass leaves a dead i-shell in front of project_cg
-            {"SF_MARCH": "0"}, {"SF_ISHELL": "0"}, {"SF_ISHELL": "2"}, {"SF_GHOST": "1"}, {"SF_GHOST": "3"},
-            {"SF_FUSE2": "0"}, {"SF_FUSE_SRC": "0"}, {"SF_HALO_STREAM": "2"}, {"SF_SPLIT": "0"}, {"SF_SPLIT_FIELDS": "0"},
-            {"SF_ADVECT_ROW": "2"}, {"SF_GRAPH": "1"}]
+SETTINGS = CG_STEP_SETTINGS
 VEL_N, VEL_TOL, VEL_MAX, VEL_STEPS = 40, 1e-2, 10, 2
 VEL_NAMES = ("u", "v", "w")
 _DEFAULT_OUTCOMES = {}

@@ -4,7 +4,8 @@ iterations, status, rel_residual and the double of sf_poisson_residual.
 
 (1) the row shapes of the new dot kernel: project_cg with m = 4 at every size class, the second-trip sizes included;
 (2) m in {1, 2, 3, 4, 5, 8} at N = 34 and 65 with the default kernels and with the marching kernel forced: a single sweep
-    on a really zeroed z, the zero-iterate pair, pairs, and the zero-iterate and plain marching passes feed a solve;
+    on a really zeroed z everywhere, and at N = 34 in fp64 (the one case here that fuses) the zero-iterate pair, pairs,
+    and the zero-iterate and plain marching passes feed a solve;
 (3) every decomposition of shape_cases.DECOMPOSED with m = 4 and m = 3 (34 / 17: a ghost plane next to every plane, the
     exchange of r), scalars on the host and on the device;
 (4) check_every in {0, 1, 3, 8}: the same bits however the solve stops;
@@ -22,8 +23,7 @@ import pcg_cases as PC
 import pressure_cg_ref as R
 import pressure_pcg_ref as Q
 import shape_cases as C
-import stable_ref as S3
-from gpu_support import DT, VISC, S, assert_same_bits, check_solve, make, march_mode, random_fields, upload_all  # noqa: F401
+from gpu_support import S, assert_same_bits, check_solve, make, march_mode, random_fields, reference_vel_step, upload_all  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -87,10 +87,12 @@ def test_row_shapes_of_the_dot_kernel(N, dtype):
 @pytest.mark.parametrize("m", PC.SWEEPS, ids=[f"m{m}" for m in PC.SWEEPS])
 @pytest.mark.parametrize("N", PC.SWEEP_SIZES, ids=[f"N{n}" for n in PC.SWEEP_SIZES])
 def test_sweep_counts_and_kernel_forms(N, m, dtype, march_mode):
-    """To convergence. m = 1 and the last sweep of m = 3, 5 read a z that op_precondition (m = 1) or the pass before has
-    really stored; N = 34 in fp32 is no multiple of W and runs single sweeps throughout; with the marching kernel forced
-    m = 8 is its zero-iterate pass and a plain one, m = 5 a pair and a three-sweep pass. On the host path and with
-    check_every = 3 on the same context."""
+    """To convergence. m = 1 and the last sweep of m = 3 read a z that op_precondition (m = 1) or the pass before has
+    really stored. Only N = 34 in fp64 fuses sweeps (N a multiple of W = 2): pairs by default, and with the marching
+    kernel forced m = 5 is a pair and a three-sweep pass, m = 8 the zero-iterate marching pass and a plain one. N = 65
+    (odd) in both precisions and N = 34 in fp32 (no multiple of W = 4) run single sweeps on a stored zero for every m
+    and either kernel setting. The pass plans at sizes that fuse in both precisions, the fp32 marching tile among them,
+    are held by tests/test_pressure_pcg_plans_gpu.py. On the host path and with check_every = 3 on the same context."""
     seed = PC.seed(N)
     want = reference(N, dtype, seed, TOL, PC.TO_CONVERGENCE, m)
     assert want["status"] == R.CONVERGED and want["iterations"] >= 8
@@ -220,27 +222,6 @@ def test_none_selected_again_is_the_unpreconditioned_solve(P):
 
 
 # ---- (6) -----------------------------------------------------------------------------------------------------------
-def reference_vel_step(f, K, tol, max_iters, m):
-    """SPEC §3 vel_step on copies of the six velocity fields of f, both projections Q.project_cg (SPEC §11 "vel_step with
-    the solver selected"). Returns (u, v, w) and the second projection's outcome."""
-    u, v, w, u0, v0, w0 = (f[n].copy() for n in ("u", "v", "w", "u0", "v0", "w0"))
-    T = u.dtype.type
-    Nf = T(u.shape[0] - 2)
-    for x, s in ((u, u0), (v, v0), (w, w0)):
-        S3.add_source(x, s, DT)
-    u, u0, v, v0, w, w0 = u0, u, v0, v, w0, w
-    a = ((T(DT) * T(VISC)) * Nf) * Nf
-    for b, x, x0 in ((1, u, u0), (2, v, v0), (3, w, w0)):
-        S3.lin_solve(b, x, x0, a, T(1) + T(6) * a, K)
-    out = Q.project_cg(u, v, w, tol, max_iters, m)
-    u0, v0, w0 = out["u"], out["v"], out["w"]  # (after the swap: the projected velocity is what advect reads)
-    u, v, w = (np.zeros_like(u0) for _ in range(3))
-    for b, d, d0 in ((1, u, u0), (2, v, v0), (3, w, w0)):
-        S3.advect(b, d, d0, u0, v0, w0, DT)
-    out = Q.project_cg(u, v, w, tol, max_iters, m)
-    return out
-
-
 _STEP_REFERENCE = {}
 
 

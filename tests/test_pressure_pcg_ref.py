@@ -12,6 +12,13 @@ Mutants (pcg_copy):
   gamma_one_trip gamma summed with second-trip cells added to lane 0 one after another
   stale_r        slab emulation: every slab runs each fused pass of M(r) with the r of the update before on the planes
                  beyond its own (r's ghost planes not exchanged; zeros the first time)
+  shallow_r      slab emulation: r beyond a slab is current on the first plane only and stale on the planes beyond it
+                 (an exchange of r that ships one plane where a pass of three or four sweeps reads two or three)
+  stale_z        slab emulation: after a pass the iterate's ghost planes are not exchanged — the exchange ships the
+                 partner buffer — so the next pass reads, beyond the slab, the iterate of two passes before (+0 at the
+                 start of an M)
+The slab emulation runs the passes it is given: the sweep counts of a case's plan in pcg_cases.PLANS. With everything
+current ("emulated") it is the reference. The table test at the end shows that PLANS covers every pass kind.
 """
 import math
 
@@ -166,8 +173,13 @@ def sweeps(z, rhs, n, last_set_bnd=True):
     return cur
 
 
-def pcg_copy(u, v, w, tol, max_iters, m, mut=None, slabs=1):
-    """pressure_pcg_ref.project_cg (m >= 1) with mutation `mut` (None: the reference, line by line)."""
+SLAB_MUTANTS = ("stale_r", "shallow_r", "stale_z", "emulated")
+
+
+def pcg_copy(u, v, w, tol, max_iters, m, mut=None, slabs=1, passes=None):
+    """pressure_pcg_ref.project_cg (m >= 1) with mutation `mut` (None: the reference, line by line). passes: the sweep
+    counts of the fused passes the slab emulation runs (default passes_of(m))."""
+    assert passes is None or sum(passes) == m
     dtype = u.dtype
     T = dtype.type
     N = u.shape[0] - 2
@@ -177,20 +189,27 @@ def pcg_copy(u, v, w, tol, max_iters, m, mut=None, slabs=1):
         rhs = np.zeros((N + 2,) * 3, dtype)
         rhs[I, I, I] = r
         z0 = state["z"] if mut == "z_not_zeroed" else np.zeros_like(rhs)
-        if mut == "stale_r":
+        if mut in SLAB_MUTANTS:
             nzl = N // slabs
             stale = np.zeros_like(rhs)
             stale[I, I, I] = state["r_old"]
-            z = z0
-            for s in passes_of(m):
+            z, older = z0, np.zeros_like(rhs)  # the iterate, and the iterate of the pass before
+            for s in passes or passes_of(m):
                 nxt = np.zeros_like(z)
                 for g in range(slabs):
                     a, b = 1 + g * nzl, 1 + (g + 1) * nzl  # the slab's planes [a, b)
-                    seen = stale.copy()
-                    seen[a:b] = rhs[a:b]
                     lo, hi = (0 if g == 0 else a), (N + 2 if g == slabs - 1 else b)  # wall slabs own the shell planes
-                    nxt[lo:hi] = sweeps(z, seen, s)[lo:hi]
-                z = nxt
+                    seen, zseen = rhs, z
+                    if mut in ("stale_r", "shallow_r"):
+                        seen = stale.copy()
+                        seen[a:b] = rhs[a:b]
+                        if mut == "shallow_r":
+                            seen[a - 1], seen[b] = rhs[a - 1], rhs[b]
+                    if mut == "stale_z":
+                        zseen = older.copy()
+                        zseen[lo:hi] = z[lo:hi]
+                    nxt[lo:hi] = sweeps(zseen, seen, s)[lo:hi]
+                older, z = z, nxt
         else:
             z = sweeps(z0, rhs, m, mut != "no_last_set_bnd")
         state["z"], state["r_old"] = z, r
@@ -303,3 +322,115 @@ def test_decomposed_inputs_tell_stale_ghost_planes_of_r(N, P, dtype, m):
     assert not same_outcome(pcg_copy(u, v, w, 1e-3, 6, m, "stale_r", slabs=P), want)
     one = Q.project_cg(u, v, w, 1e-3, 6, 1, slabs=P)
     assert same_outcome(pcg_copy(u, v, w, 1e-3, 6, 1, "stale_r", slabs=P), one)
+
+
+# ---- the pass plans (pcg_cases.PLANS) --------------------------------------------------------------------------------
+def sweeps_of(plan):
+    return [s for s, _, _ in PC.parse_plan(plan)]
+
+
+# the slab cases of the GPU file the mutants are run on: every plan at N = 40 (two slabs of 20 planes), and one of the
+# longest plans of each other (N, P); fp64 at 40 and 72 / 3, fp32 elsewhere
+def mutant_cases():
+    out = [c for c in PC.ON_SLABS if c.N == 40 and c.dtype == np.float64 and "SF_ZERO_SKIP" not in c.env]
+    for N, P, m, dtype in ((64, 2, 12, np.float32), (64, 4, 12, np.float32), (72, 2, 10, np.float32), (72, 3, 10, np.float64)):
+        out += [c for c in PC.ON_SLABS if (c.N, c.P, c.m, c.dtype) == (N, P, m, dtype)]
+    return out
+
+
+MUTANT_CASES = mutant_cases()
+
+
+@pytest.mark.parametrize("case", MUTANT_CASES, ids=[c.id for c in MUTANT_CASES])
+def test_plan_inputs_tell_shallow_r_and_stale_z(case):
+    """Six iterations of cg_velocity, as tests/test_pressure_pcg_plans_gpu.py runs them, with the passes of the case's
+    plan. The emulation with everything current is the reference. stale_z differs wherever there is a second pass;
+    shallow_r differs wherever a pass has three or four sweeps, and is the reference where every pass has at most two
+    (such a pass reads r on one plane beyond the slab): the control, as m = 1 is for stale_r."""
+    assert len(MUTANT_CASES) == 12
+    u, v, w = C.cg_velocity(case.N, case.dtype, PC.seed(case.N))
+    passes = sweeps_of(case.plan)
+    want = Q.project_cg(u, v, w, PC.TOL, PC.DECOMPOSED_ITERS, case.m)
+    run = lambda mut: pcg_copy(u, v, w, PC.TOL, PC.DECOMPOSED_ITERS, case.m, mut, slabs=case.P, passes=passes)  # noqa: E731
+    assert same_outcome(run("emulated"), want), "the slab emulation is not the reference"
+    assert len(passes) >= 2 and not same_outcome(run("stale_z"), want)
+    assert not same_outcome(run("stale_r"), want)
+    assert same_outcome(run("shallow_r"), want) == (max(passes) <= 2), passes
+
+
+def test_one_pass_cannot_show_stale_z():
+    """m = 2 is one pass on the zero iterate: nothing of z is read beyond a slab."""
+    u, v, w = C.cg_velocity(40, np.float32, PC.seed(40))
+    assert same_outcome(pcg_copy(u, v, w, PC.TOL, 6, 2, "stale_z", slabs=2, passes=[2]), Q.project_cg(u, v, w, PC.TOL, 6, 2))
+
+
+def test_the_mutant_cases_hold_both_kinds_of_plan():
+    deep = [c for c in MUTANT_CASES if max(sweeps_of(c.plan)) >= 3]
+    assert len(deep) >= 8 and len(MUTANT_CASES) - len(deep) >= 2  # (40 / 2 m = 3 and 64 / 4: pairs and singles only)
+
+
+ONE_SLAB_PLANS = {2: "2Z", 5: "2Z 3", 6: "2Z 4", 7: "4Z 3", 8: "4Z 4", 9: "4Z 3 2", 10: "4Z 3 3", 11: "4Z 4 3", 12: "4Z 4 4"}
+SLAB_PLANS = {  # (N, P, MARCH_MINP=4?) -> {m: plan}
+    (72, 2, False): {5: "2Z 3+3", 7: "4Z 3+4", 8: "4Z 4+4", 9: "4Z 3+4 2", 10: "4Z 3+4 3+7", 11: "4Z 4+4 3+8", 12: "4Z 4+4 4+8"},
+    (64, 2, False): {5: "2Z 3+3", 7: "4Z 3+4", 8: "4Z 4+4", 9: "4Z 3+4 2"},
+    (64, 2, True): {10: "4Z 3+4 3+7", 11: "4Z 4+4 3+8", 12: "4Z 4+4 4+8"},
+    (40, 2, False): {3: "2Z 1", 5: "2Z 3", 7: "4Z 3", 8: "4Z 4", 9: "4Z 3 2", 10: "4Z 3 3", 11: "4Z 4 3", 12: "4Z 4 4"},
+    (72, 3, True): {7: "4Z 3+4", 8: "4Z 4+4", 10: "4Z 3+4 3", 12: "4Z 4+4 4"},
+    (64, 4, False): {8: "2Z 2+2 2+4 2", 9: "2Z 2+2 2+4 2 1", 12: "2Z 2+2 2+4 2 2+2 2+4"},
+}
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
+def test_the_plan_table_is_the_one_written_down(dtype):
+    """The plans of pcg_cases.PLANS (its model of plan_solve) against the table as it stands in docs/NEXT.md, which the
+    GPU file confirmed from the traces: a change of the model, or of the cases, shows here first."""
+    got_one, got_slabs = {}, {}
+    for c in PC.PLANS:
+        if c.dtype != dtype or "SF_ZERO_SKIP" in c.env or c.tuned:
+            continue
+        assert c.env.get("SF_MARCH_MINCELLS_K") == "0"
+        if c.P == 1:
+            assert c.G == 1
+            if c.m in ONE_SLAB_PLANS:
+                got_one.setdefault(c.N, {})[c.m] = c.plan
+        else:
+            assert c.G == (2 if (c.N, c.P) == (64, 4) else 4)
+            got_slabs.setdefault((c.N, c.P, "SF_MARCH_MINP" in c.env), {})[c.m] = c.plan
+    assert got_one == {40: ONE_SLAB_PLANS, 64: ONE_SLAB_PLANS}
+    assert got_slabs == SLAB_PLANS
+    # the rccl-self cases that grow say SF_TRAP=5 (such a context's default is 0 or what it measures), the copy cases
+    # say nothing; both transports occur at every (N, P)
+    for c in PC.ON_SLABS:
+        if not c.tuned:
+            assert ("SF_TRAP" in c.env) == (c.transport == "rccl-self" and "+" in c.plan), c.id
+    for key in {(c.N, c.P) for c in PC.ON_SLABS}:
+        assert {c.transport for c in PC.ON_SLABS if (c.N, c.P) == key} == {"copy", "rccl-self"}
+    assert sum(c.tuned for c in PC.PLANS) == 2
+    # what the issue's other statements about the model come to
+    assert PC.model(40, np.float64, 2, 8, dict(PC.MARCH, SF_GHOST="3")) == (3, "2Z 3 3")
+    assert PC.model(40, dtype, 1, 8, PC.NO_SKIP) == (1, "4C 4")
+    assert PC.model(34, np.float32, 2, 4) == (1, "1C 1 1 1") and PC.model(34, np.float64, 2, 4) == (2, "2Z 2+2")
+
+
+@pytest.mark.parametrize("slabs", [False, True], ids=["one-slab", "slabs"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
+def test_the_plan_table_covers_every_pass_kind(dtype, slabs):
+    """In each precision, on one slab and on slabs: passes of 1, 2, 3 and 4 sweeps; a first pass on the implicit zero
+    and one on the stored zero, of two and of four sweeps each; a four-sweep pass followed by a three-sweep one; and on
+    slabs a grown pass, a pass that snaps back after a grown one, a second block in one solve, and the growth of a 3
+    after a 4 by max(S_j, S_j-1) = 4. One slab has no boundary launch: no plan grows there."""
+    plans = [PC.parse_plan(c.plan) for c in PC.PLANS if c.dtype == dtype and (c.P > 1) == slabs and not c.tuned]
+    passes = [p for plan in plans for p in plan]
+    pairs = [(a, b) for plan in plans for a, b in zip(plan, plan[1:])]
+    assert {s for s, _, _ in passes} == {1, 2, 3, 4}
+    assert {(s, f) for s, f, _ in passes if f} >= {(2, "Z"), (4, "Z"), (2, "C"), (4, "C")}
+    assert any(a[0] == 4 and b[0] == 3 for a, b in pairs)
+    grown = [p for p in passes if p[2]]
+    if not slabs:
+        assert not grown and (1, "C", 0) in passes
+        return
+    assert {s for s, _, _ in grown} == {2, 3, 4}
+    assert any(a[2] and not b[2] for a, b in pairs), "no pass snaps back after a grown one"
+    assert any(a[2] and b[2] > a[2] for a, b in pairs), "no block of three passes"
+    assert any([bool(e) for _, _, e in plan] == [False, True, True, False, True, True] for plan in plans), "no second block"
+    assert any(a[0] == 4 and b[0] == 3 and b[2] == 4 for a, b in pairs)
