@@ -3231,23 +3231,11 @@ __global__ void __launch_bounds__(256) cg_direction_z_kernel(Geom g, CgArgs<T> A
     }
 }
 
-// One workgroup: the Total of SPEC §10 over the plane records recs[k0 .. k1) — a +0.0-started sequential sum in
-// increasing global k, the loop at the end of Solver::finish_records — then what the host does with that sum at this
-// stage of a solve, in the same double operations (a correctly rounded divide, a round-to-nearest-even conversion to
-// T). c: N^3 (STAGE_MU) or tol * tol (STAGE_RHO, STAGE_RHO_PC), formed by the host. The records go through LDS so that the one lane
-// that adds them waits for an addition per record, not for a load. k1 - k0 <= 2048 (Solver::records_alloc).
-// Every stage but the two that start a solve does nothing once the solve has stopped.
+// What a solve does with the sum s of one stage (SPEC §11, §11.2): the stop tests and their status, and alpha and beta
+// as T. The one statement of those rules: cg_scalars_kernel applies it where the scalars live on the device, the
+// host (Solver::cg_sum) where they do not. c: N^3 (STAGE_MU) or tol * tol (STAGE_RHO, STAGE_RHO_PC).
 template <class T, int STAGE>
-__global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restrict__ recs, int k0, int k1, double c,
-                                                         CgState<T>* __restrict__ st) {
-    __shared__ double a[2048];
-    const int t = (int)threadIdx.x, n = k1 - k0;
-    if (STAGE != STAGE_MU && STAGE != STAGE_RHO0 && st->active == 0) return;  // (the whole workgroup)
-    for (int k = t; k < n; k += 256) a[k] = recs[k0 + k];
-    __syncthreads();
-    if (t != 0) return;
-    double s = 0.0;
-    for (int k = 0; k < n; ++k) s = s + a[k];
+__host__ __device__ __forceinline__ void cg_stage(CgState<T>* st, double s, double c) {
     if constexpr (STAGE == STAGE_MU) {
         st->mu = (T)(s / c);
     } else if constexpr (STAGE == STAGE_RHO0) {
@@ -3255,8 +3243,8 @@ __global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restric
         st->delta = st->rho_new = 0.0;
         st->aT = st->bT = T(0);
         st->iterations = 0;
-        st->status = s == 0.0 ? CG_ST_CONVERGED : (isfinite(s) ? CG_ST_MAX_ITERS : CG_ST_BREAKDOWN);
-        st->active = (s != 0.0 && isfinite(s)) ? 1 : 0;
+        st->status = s == 0.0 ? CG_ST_CONVERGED : (__builtin_isfinite(s) ? CG_ST_MAX_ITERS : CG_ST_BREAKDOWN);
+        st->active = (s != 0.0 && __builtin_isfinite(s)) ? 1 : 0;
     } else if constexpr (STAGE == STAGE_DELTA) {
         st->delta = s;
         if (!(s > 0.0)) {
@@ -3268,7 +3256,7 @@ __global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restric
     } else if constexpr (STAGE == STAGE_RHO) {
         st->rho_new = st->last = s;
         st->iterations = st->iterations + 1;
-        if (!isfinite(s)) {
+        if (!__builtin_isfinite(s)) {
             st->status = CG_ST_BREAKDOWN;
             st->active = 0;
         } else if (s <= c * st->rho0) {
@@ -3303,7 +3291,7 @@ __global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restric
     } else {  // STAGE_RHO_PC: the count and the stop tests of rho'; beta waits for gamma'
         st->rho_new = st->last = s;
         st->iterations = st->iterations + 1;
-        if (!isfinite(s)) {
+        if (!__builtin_isfinite(s)) {
             st->status = CG_ST_BREAKDOWN;
             st->active = 0;
         } else if (s <= c * st->rho0) {
@@ -3313,6 +3301,26 @@ __global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restric
             st->rho = s;
         }
     }
+}
+
+// One workgroup: the Total of SPEC §10 over the plane records recs[k0 .. k1) — a +0.0-started sequential sum in
+// increasing global k, the loop at the end of Solver::finish_records — then cg_stage on that sum, in the double
+// operations the host has (a correctly rounded divide, a round-to-nearest-even conversion to T). c is formed by the
+// host. The records go through LDS so that the one lane that adds them waits for an addition per record, not for a
+// load. k1 - k0 <= 2048 (Solver::records_alloc).
+// Every stage but the two that start a solve does nothing once the solve has stopped.
+template <class T, int STAGE>
+__global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restrict__ recs, int k0, int k1, double c,
+                                                         CgState<T>* __restrict__ st) {
+    __shared__ double a[2048];
+    const int t = (int)threadIdx.x, n = k1 - k0;
+    if (STAGE != STAGE_MU && STAGE != STAGE_RHO0 && st->active == 0) return;  // (the whole workgroup)
+    for (int k = t; k < n; k += 256) a[k] = recs[k0 + k];
+    __syncthreads();
+    if (t != 0) return;
+    double s = 0.0;
+    for (int k = 0; k < n; ++k) s = s + a[k];
+    cg_stage<T, STAGE>(st, s, c);
 }
 
 }  // namespace sfk

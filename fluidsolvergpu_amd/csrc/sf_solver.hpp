@@ -2730,12 +2730,13 @@ private:
     // ---- conjugate-gradient projection (SPEC §11) ---------------------------------------------------------------
     // The work fields r, d, q are the three scratch buffers, addressed through internal slots while the operator is
     // issued (exchange() takes slots), as `hat` is in op_advect_mc. Every row kernel runs a slab's nzl planes in one
-    // launch on its compute stream; d's ghost planes travel on the halo stream after every update of d while the host
-    // waits for the sum that follows. Two host synchronisations per iteration (finish_records) — or, with
-    // check_every_ = m >= 1, none: every sum is folded by cg_scalars(), which leaves alpha, beta and the outcome of the
-    // stop tests in cg_state_ for the kernels that follow, and the host reads that state once per m iterations.
-    // With a preconditioner selected (SPEC §11.2) every iteration also runs z = M(r) (op_precondition) and a third sum,
-    // r.z: three host synchronisations per iteration on the host path.
+    // launch on its compute stream; d's ghost planes travel on the halo stream after every update of d.
+    // One skeleton, cg_iterate<DEV>, issues the solve: plain (§11) or with z = M(r) and a third sum, r.z, in every
+    // iteration (§11.2, op_precondition); with the scalars on the host (check_every_ = 0) or on the device (m >= 1).
+    // The two forms differ in what a sum's stage is (cg_sum), in the kernels' DEV parameter and argument (cg_args) and
+    // in the state that the DEV forms add to a kernel's trace; what a stage does with its sum (the stop tests, their
+    // status, alpha and beta as T) is sfk::cg_stage on both. Host waits: one per sum by value (2 + 2 per iteration,
+    // three per iteration preconditioned), one per m iterations with DEV (cg_state_read).
     double one_sum() {
         double r[1];
         finish_records(1, 1, 0, r);
@@ -2752,12 +2753,6 @@ private:
     }
     // a slab's plane records inside red_gather_ (one value per plane)
     double* cg_records(const Slab& sl) const { return red_gather_ + (size_t)sl.gid * nzl_; }
-    // the argument of the device-scalar forms: the state where the by-value forms have the scalar
-    sfk::CgArgs<T> cg_dev_args(Slab& sl, int p, int div) const {
-        sfk::CgArgs<T> A = cg_args(sl, p, div, T(0));
-        A.st = cg_state_;
-        return A;
-    }
     // What one_sum() does, without the host: row records -> every slab's plane records, next to each other in
     // red_gather_ -> (all ranks' records, gathered in place) -> cg_scalars_kernel on slab 0's compute stream, which the
     // other slabs' compute streams wait for. c: the stage's constant (N^3, tol * tol).
@@ -2807,14 +2802,32 @@ private:
         ++host_waits_;
         return *cg_state_host_;
     }
-    sfk::CgArgs<T> cg_args(Slab& sl, int p, int div, T s) const {
+    // One sum of a solve and what its stage does with it (sfk::cg_stage). By value: the host waits for the sum and
+    // applies the stage to st; false once the solve has stopped. DEV: cg_scalars() enqueues both, and issuing goes on.
+    template <bool DEV, int STAGE>
+    bool cg_sum(sfk::CgState<T>& st, double c) {
+        if constexpr (DEV) {
+            cg_scalars<STAGE>(c);
+            return true;
+        } else {
+            sfk::cg_stage<T, STAGE>(&st, one_sum(), c);
+            return st.active != 0;
+        }
+    }
+    // The argument of a CG row kernel. rhs: the field at div's place (z, for the kernels that read z: SPEC §11.2). The
+    // scalar goes by value, or (DEV) the state goes where the by-value forms have it.
+    template <bool DEV>
+    sfk::CgArgs<T> cg_args(Slab& sl, int p, int rhs, T s) const {
         sfk::CgArgs<T> A;
-        A.div = sl.field[div];
+        A.div = sl.field[rhs];
         A.p = sl.field[p];
         A.r = sl.field[CG_R];
         A.d = sl.field[CG_D];
         A.q = sl.field[CG_Q];
-        A.s = s;
+        if constexpr (DEV)
+            A.st = cg_state_;
+        else
+            A.s = s;
         return A;
     }
     // ---- its Jacobi-sweep preconditioner (SPEC §11.2) ----
@@ -2822,20 +2835,6 @@ private:
         for (Slab& sl : slabs_)
             for (int f : {CG_Z, CG_ZP})
                 if (!sl.field[f]) sl.field[f] = alloc_field();
-    }
-    // the argument of the kernels that read z (it has div's place)
-    sfk::CgArgs<T> cg_z_args(Slab& sl, T s) const {
-        sfk::CgArgs<T> A{};
-        A.z = sl.field[CG_Z];
-        A.r = sl.field[CG_R];
-        A.d = sl.field[CG_D];
-        A.s = s;
-        return A;
-    }
-    sfk::CgArgs<T> cg_z_dev_args(Slab& sl) const {
-        sfk::CgArgs<T> A = cg_z_args(sl, T(0));
-        A.st = cg_state_;
-        return A;
     }
     // z = M(r): z = +0, then lin_solve(0, z, r, 1, 6, sweeps) as the pass planner lays any solve out, ping-pong between
     // the two owning slots. A pass of s fused sweeps reads its right-hand side s - 1 planes beyond its own, so r's ghost
@@ -2874,25 +2873,22 @@ private:
         publish_from_cs(x);
     }
 
-    void op_project_cg(int u, int v, int w, int p, int div, double tol, int max_iters, bool mirror_u = false) {
-        mirror_u = mirror_u && ishell_skip_;
-        records_alloc();
-        static_assert(sfk::CG_ST_CONVERGED == SF_CG_CONVERGED && sfk::CG_ST_MAX_ITERS == SF_CG_MAX_ITERS &&
-                          sfk::CG_ST_BREAKDOWN == SF_CG_BREAKDOWN, "CgState::status holds sf_cg_status values");
-        const int m = check_every_;  // 0: the scalars on the host; m >= 1: on the device, read back every m iterations
-        if (m > 0) cg_state_alloc();
-        const int pm = precond_ == SF_PRECOND_JACOBI ? precond_sweeps_ : 0;  // sweeps of z = M(r); 0: §11 as it stands
-        if (pm > 0) pcg_alloc();
-        host_waits_ = 0;
-        ScratchAlias work_slots(slabs_, 3);
+    // The iteration of SPEC §11 (pm = 0) or §11.2 (pm sweeps of z = M(r)), written once. DEV false: every stage is a
+    // host wait, and nothing more is issued once a stage has stopped the solve. DEV: the stages are enqueued with the
+    // kernels, which are no-ops past the iteration that stops the solve (cg_live) while the sweeps of M(r) and the
+    // exchange of d go on as they were, so what is left does not depend on m; the state is read every m iterations.
+    // Returns the state the solve ended in.
+    template <bool DEV>
+    sfk::CgState<T> cg_iterate(int p, int div, double tol, int max_iters, int pm) {
         const int kb = G_, ke = G_ + nzl_;
+        const bool pc = pm > 0;
         // d as a kernel writes it: the shell plane of a wall slab included
         auto d_written = [&](Slab& sl) {
             int lo, hi;
             wr_range(sl, kb, ke, lo, hi);
             return Acc{sl.field[CG_D], true, lo, hi};
         };
-        // the fields each row kernel touches, in either form
+        // the fields each row kernel touches (z is whichever buffer the last pass of M(r) left in its slot)
         auto init_acc = [&](Slab& sl) {
             return std::vector<Acc>{{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke}, d_written(sl)};
         };
@@ -2907,198 +2903,89 @@ private:
         auto direction_acc = [&](Slab& sl) {
             return std::vector<Acc>{{sl.field[CG_R], false, kb, ke}, {sl.field[CG_D], false, kb, ke}, d_written(sl)};
         };
-        // the device-scalar forms read the state as well
-        auto with_state = [&](std::vector<Acc> a) {
-            a.push_back({cg_state_, false, 0, nplanes_});
-            return a;
-        };
-        auto dev_args = [&](Slab& sl) { return cg_dev_args(sl, p, div); };
-        // ... and those of the preconditioned solve (z is whichever buffer the last pass of M(r) left in its slot)
         auto dot_acc = [&](Slab& sl) {
             return std::vector<Acc>{{sl.field[CG_R], false, kb, ke}, {sl.field[CG_Z], false, kb, ke}};
         };
         auto direction_z_acc = [&](Slab& sl) {
             return std::vector<Acc>{{sl.field[CG_Z], false, kb, ke}, {sl.field[CG_D], false, kb, ke}, d_written(sl)};
         };
-        auto z_dev_args = [&](Slab& sl) { return cg_z_dev_args(sl); };
+        // ... to which the device-scalar forms add the state they read
+        auto acc = [&](auto fields) {
+            return [this, fields](Slab& sl) {
+                std::vector<Acc> a = fields(sl);
+                if (DEV) a.push_back({cg_state_, false, 0, nplanes_});
+                return a;
+            };
+        };
+        // rhs: the field at div's place; s: the scalar of the by-value forms
+        auto args = [&](int rhs, T s) { return [this, p, rhs, s](Slab& sl) { return cg_args<DEV>(sl, p, rhs, s); }; };
 
-        project_first_half(u, v, w, p, div, mirror_u, false, true);
-        join();
+        sfk::CgState<T> st{};
+        // z = M(r), gamma = r.z, then the direction from z: d = z (the first one) or z + beta * d
+        auto direction_pc = [&](auto first) {
+            constexpr bool INIT = decltype(first)::value;
+            op_precondition(pm);
+            launch_rows("cg_dot", sfk::cg_dot_kernel<T, DEV>, args(CG_Z, T(0)), acc(dot_acc));
+            if (!cg_sum<DEV, INIT ? sfk::STAGE_GAMMA0 : sfk::STAGE_GAMMA>(st, 0.0)) return false;
+            launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, DEV, INIT>, args(CG_Z, st.bT),
+                               acc(direction_z_acc));
+            publish_from_cs(CG_D);
+            return true;
+        };
+        auto iteration = [&] {
+            join();  // d's ghost planes
+            launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false, DEV>, args(div, T(0)), acc(apply_acc));
+            if (!(pc ? cg_sum<DEV, sfk::STAGE_DELTA_PC>(st, 0.0) : cg_sum<DEV, sfk::STAGE_DELTA>(st, 0.0))) return false;
+            launch_rows("cg_update", sfk::cg_update_kernel<T, DEV>, args(div, st.aT), acc(update_acc));
+            if (!(pc ? cg_sum<DEV, sfk::STAGE_RHO_PC>(st, tol * tol) : cg_sum<DEV, sfk::STAGE_RHO>(st, tol * tol)))
+                return false;
+            if (pc) return direction_pc(std::false_type{});
+            // the one row kernel of a plain solve that writes no row records
+            launch_rows<false>("cg_direction", sfk::cg_direction_kernel<T, DEV>, args(div, st.bT), acc(direction_acc));
+            publish_from_cs(CG_D);
+            return true;
+        };
+
         launch_rows("cg_sum_div", sfk::reduce_rows_kernel<T, sfk::RED_SUM>,
                     [&](Slab& sl) { return (const T*)sl.field[div]; },
                     [&](Slab& sl) { return std::vector<Acc>{{sl.field[div], false, kb, ke}}; });
-        const double n3 = (double)N_ * (double)N_ * (double)N_;
-        double rho0, last;
-        int status = SF_CG_MAX_ITERS, iters = 0;
-        if (m > 0 && pm > 0) {
-            // SPEC §11.2 with the scalars on the device: the sweeps of M(r) run in every enqueued iteration, every other
-            // kernel is a no-op once the solve has stopped
-            cg_scalars<sfk::STAGE_MU>(n3);
-            launch_rows("cg_init", sfk::cg_init_kernel<T, true>, dev_args, [&](Slab& sl) { return with_state(init_acc(sl)); });
-            cg_scalars<sfk::STAGE_RHO0>(0.0);
-            op_precondition(pm);
-            launch_rows("cg_dot", sfk::cg_dot_kernel<T, true>, z_dev_args, [&](Slab& sl) { return with_state(dot_acc(sl)); });
-            cg_scalars<sfk::STAGE_GAMMA0>(0.0);
-            launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, true, true>, z_dev_args,
-                               [&](Slab& sl) { return with_state(direction_z_acc(sl)); });
-            publish_from_cs(CG_D);
-            const sfk::CgState<T>* st = nullptr;
+        cg_sum<DEV, sfk::STAGE_MU>(st, (double)N_ * (double)N_ * (double)N_);
+        launch_rows("cg_init", sfk::cg_init_kernel<T, DEV>, args(div, st.mu), acc(init_acc));
+        if (!pc) publish_from_cs(CG_D);  // (a preconditioned solve replaces d before anything reads its ghost planes)
+        bool go = cg_sum<DEV, sfk::STAGE_RHO0>(st, 0.0);
+        if (go && pc) go = direction_pc(std::true_type{});
+        if constexpr (DEV) {
             int n = 0;
             do {
-                for (const int end = n + std::min(m, max_iters - n); n < end; ++n) {
-                    join();  // d's ghost planes
-                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false, true>, dev_args,
-                                [&](Slab& sl) { return with_state(apply_acc(sl)); });
-                    cg_scalars<sfk::STAGE_DELTA_PC>(0.0);
-                    launch_rows("cg_update", sfk::cg_update_kernel<T, true>, dev_args,
-                                [&](Slab& sl) { return with_state(update_acc(sl)); });
-                    cg_scalars<sfk::STAGE_RHO_PC>(tol * tol);
-                    op_precondition(pm);
-                    launch_rows("cg_dot", sfk::cg_dot_kernel<T, true>, z_dev_args,
-                                [&](Slab& sl) { return with_state(dot_acc(sl)); });
-                    cg_scalars<sfk::STAGE_GAMMA>(0.0);
-                    launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, true, false>, z_dev_args,
-                                       [&](Slab& sl) { return with_state(direction_z_acc(sl)); });
-                    publish_from_cs(CG_D);
-                }
-                st = &cg_state_read();
-            } while (st->active && n < max_iters);
-            status = st->active ? SF_CG_MAX_ITERS : st->status;
-            iters = st->iterations;
-            rho0 = st->rho0;
-            last = st->last;
-        } else if (m > 0) {
-            cg_scalars<sfk::STAGE_MU>(n3);
-            launch_rows("cg_init", sfk::cg_init_kernel<T, true>, dev_args, [&](Slab& sl) { return with_state(init_acc(sl)); });
-            publish_from_cs(CG_D);
-            cg_scalars<sfk::STAGE_RHO0>(0.0);
-            const sfk::CgState<T>* st = nullptr;
-            int n = 0;
-            do {
-                // past the iteration that stops the solve every kernel of this sequence is a no-op (cg_live), and the
-                // exchange ships d's planes as they were: what is left does not depend on m
-                for (const int end = n + std::min(m, max_iters - n); n < end; ++n) {
-                    join();  // d's ghost planes
-                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false, true>, dev_args,
-                                [&](Slab& sl) { return with_state(apply_acc(sl)); });
-                    cg_scalars<sfk::STAGE_DELTA>(0.0);
-                    launch_rows("cg_update", sfk::cg_update_kernel<T, true>, dev_args,
-                                [&](Slab& sl) { return with_state(update_acc(sl)); });
-                    cg_scalars<sfk::STAGE_RHO>(tol * tol);
-                    launch_rows<false>("cg_direction", sfk::cg_direction_kernel<T, true>, dev_args,
-                                       [&](Slab& sl) { return with_state(direction_acc(sl)); });
-                    publish_from_cs(CG_D);
-                }
-                st = &cg_state_read();
-            } while (st->active && n < max_iters);
-            status = st->active ? SF_CG_MAX_ITERS : st->status;
-            iters = st->iterations;
-            rho0 = st->rho0;
-            last = st->last;
-        } else if (pm > 0) {
-            // SPEC §11.2 with the scalars on the host: three host waits per iteration
-            const T mu = (T)(one_sum() / n3);
-            launch_rows("cg_init", sfk::cg_init_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, mu); }, init_acc);
-            rho0 = one_sum();
-            last = rho0;
-            auto gamma_sum = [&] {
-                op_precondition(pm);
-                launch_rows("cg_dot", sfk::cg_dot_kernel<T>, [&](Slab& sl) { return cg_z_args(sl, T(0)); }, dot_acc);
-                return one_sum();
-            };
-            double gamma = 0.0;
-            if (rho0 == 0.0)
-                status = SF_CG_CONVERGED;
-            else if (!std::isfinite(rho0))
-                status = SF_CG_BREAKDOWN;
-            else if (!((gamma = gamma_sum()) > 0.0))
-                status = SF_CG_BREAKDOWN;
-            else {
-                launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, false, true>,
-                                   [&](Slab& sl) { return cg_z_args(sl, T(0)); }, direction_z_acc);
-                publish_from_cs(CG_D);
-                for (int n = 0; n < max_iters; ++n) {
-                    join();  // d's ghost planes
-                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false>,
-                                [&](Slab& sl) { return cg_args(sl, p, div, T(0)); }, apply_acc);
-                    const double delta = one_sum();
-                    if (!(delta > 0.0)) {
-                        status = SF_CG_BREAKDOWN;
-                        break;
-                    }
-                    const T aT = (T)(gamma / delta);
-                    launch_rows("cg_update", sfk::cg_update_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, aT); },
-                                update_acc);
-                    const double rho_new = one_sum();
-                    last = rho_new;
-                    iters = n + 1;
-                    if (!std::isfinite(rho_new)) {
-                        status = SF_CG_BREAKDOWN;
-                        break;
-                    }
-                    if (rho_new <= (tol * tol) * rho0) {
-                        status = SF_CG_CONVERGED;
-                        break;
-                    }
-                    const double gamma_new = gamma_sum();
-                    if (!(gamma_new > 0.0)) {
-                        status = SF_CG_BREAKDOWN;
-                        break;
-                    }
-                    const T bT = (T)(gamma_new / gamma);
-                    launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, false, false>,
-                                       [&](Slab& sl) { return cg_z_args(sl, bT); }, direction_z_acc);
-                    publish_from_cs(CG_D);
-                    gamma = gamma_new;
-                }
-            }
+                for (const int end = n + std::min(check_every_, max_iters - n); n < end; ++n) iteration();
+                st = cg_state_read();
+            } while (st.active && n < max_iters);
         } else {
-            const T mu = (T)(one_sum() / n3);
-            launch_rows("cg_init", sfk::cg_init_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, mu); }, init_acc);
-            publish_from_cs(CG_D);
-            rho0 = one_sum();
-            double rho = rho0;
-            last = rho0;
-            if (rho0 == 0.0)
-                status = SF_CG_CONVERGED;
-            else if (!std::isfinite(rho0))
-                status = SF_CG_BREAKDOWN;
-            else
-                for (int n = 0; n < max_iters; ++n) {
-                    join();  // d's ghost planes
-                    launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false>,
-                                [&](Slab& sl) { return cg_args(sl, p, div, T(0)); }, apply_acc);
-                    const double delta = one_sum();
-                    if (!(delta > 0.0)) {
-                        status = SF_CG_BREAKDOWN;
-                        break;
-                    }
-                    const T aT = (T)(rho / delta);
-                    launch_rows("cg_update", sfk::cg_update_kernel<T>, [&](Slab& sl) { return cg_args(sl, p, div, aT); },
-                                update_acc);
-                    const double rho_new = one_sum();
-                    last = rho_new;
-                    iters = n + 1;
-                    if (!std::isfinite(rho_new)) {
-                        status = SF_CG_BREAKDOWN;
-                        break;
-                    }
-                    if (rho_new <= (tol * tol) * rho0) {
-                        status = SF_CG_CONVERGED;
-                        break;
-                    }
-                    const T bT = (T)(rho_new / rho);
-                    // the one row kernel that writes no row records
-                    launch_rows<false>("cg_direction", sfk::cg_direction_kernel<T>,
-                                       [&](Slab& sl) { return cg_args(sl, p, div, bT); }, direction_acc);
-                    publish_from_cs(CG_D);
-                    rho = rho_new;
-                }
+            for (int n = 0; go && n < max_iters; ++n) go = iteration();
         }
+        return st;
+    }
+
+    void op_project_cg(int u, int v, int w, int p, int div, double tol, int max_iters, bool mirror_u = false) {
+        mirror_u = mirror_u && ishell_skip_;
+        records_alloc();
+        static_assert(sfk::CG_ST_CONVERGED == SF_CG_CONVERGED && sfk::CG_ST_MAX_ITERS == SF_CG_MAX_ITERS &&
+                          sfk::CG_ST_BREAKDOWN == SF_CG_BREAKDOWN, "CgState::status holds sf_cg_status values");
+        const bool dev = check_every_ > 0;  // the scalars on the device, read back every check_every_ iterations
+        if (dev) cg_state_alloc();
+        const int pm = precond_ == SF_PRECOND_JACOBI ? precond_sweeps_ : 0;  // sweeps of z = M(r); 0: §11 as it stands
+        if (pm > 0) pcg_alloc();
+        host_waits_ = 0;
+        ScratchAlias work_slots(slabs_, 3);
+        project_first_half(u, v, w, p, div, mirror_u, false, true);
+        join();
+        // (a solve that max_iters ends is still active, with the status its rho0 stage left: SF_CG_MAX_ITERS)
+        const sfk::CgState<T> st =
+            dev ? cg_iterate<true>(p, div, tol, max_iters, pm) : cg_iterate<false>(p, div, tol, max_iters, pm);
         host_waits_total_ += host_waits_;
         op_set_bnd(0, p, "cg_set_bnd_p");
         project_second_half(u, v, w, p, div, false);
-        note_solve(SF_PRESSURE_CG, status, iters, rho0 == 0.0 ? 0.0 : std::sqrt(last / rho0));
+        note_solve(SF_PRESSURE_CG, st.status, st.iterations, st.rho0 == 0.0 ? 0.0 : std::sqrt(st.last / st.rho0));
     }
 
     // ---- external forces (SPEC §8) ------------------------------------------------------------------------------
