@@ -248,6 +248,17 @@ int sf_pressure_preconditioner_get(const sf_ctx* ctx, sf_pressure_preconditioner
     ctx->impl->pressure_preconditioner(out);
     return SF_OK;
 }
+int sf_set_pressure_multigrid(sf_ctx* ctx, int sweeps, int max_levels, int coarse_sweeps) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_pressure_multigrid(sweeps, max_levels, coarse_sweeps); });
+}
+int sf_pressure_multigrid_get(const sf_ctx* ctx, sf_pressure_multigrid* out) {
+    if (!ctx || !ctx->impl || !out) return SF_ERR_INVALID;
+    ctx->impl->pressure_multigrid(out);
+    return SF_OK;
+}
+int sf_precondition(sf_ctx* ctx, int z, int r) {
+    return guarded(ctx, [&](SolverBase& s) { s.precondition(z, r); });
+}
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });
 }

@@ -112,6 +112,9 @@ public:
     virtual void pressure_sync(sf_pressure_sync* out) const = 0;
     virtual void set_pressure_preconditioner(int kind, int sweeps) = 0;
     virtual void pressure_preconditioner(sf_pressure_preconditioner* out) const = 0;
+    virtual void set_pressure_multigrid(int sweeps, int max_levels, int coarse_sweeps) = 0;
+    virtual void pressure_multigrid(sf_pressure_multigrid* out) const = 0;
+    virtual void precondition(int z, int r) = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

@@ -26,7 +26,7 @@
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
-//             [--pressure-precond none|jacobi:M]
+//             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -45,6 +45,9 @@
 // frames and the monitor lines are the same bits either way.
 // --pressure-precond none|jacobi:M (with --pressure cg): the preconditioner of the CG solve (docs/SPEC.md §11.2), M >= 1
 // undamped Jacobi sweeps from zero per iteration. none, the default: §11 as it stands.
+// --pressure-mg NU[:LEVELS[:COARSE]] (with --pressure cg): the multigrid V-cycle preconditioner of docs/SPEC.md §11.3 with
+// NU >= 1 sweeps per level, at most LEVELS levels (0, the default: as many as the grid allows) and COARSE >= 1 sweeps on
+// the coarsest (default 8). In force it takes the place of --pressure-precond.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -83,6 +86,7 @@ struct Options {
     int advect_vel = SF_ADVECT_SEMI_LAGRANGIAN, advect_dens = SF_ADVECT_SEMI_LAGRANGIAN;
     int pressure = SF_PRESSURE_JACOBI, cg_max_iters = 100, cg_check_every = 0;
     int cg_precond = SF_PRECOND_NONE, cg_precond_sweeps = 0;
+    int mg_sweeps = 0, mg_levels = 0, mg_coarse = 8;
     double cg_tol = 1e-3;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
@@ -222,6 +226,33 @@ static Options parse(int argc, char** argv) {
                 fprintf(stderr, "--pressure-precond takes none or jacobi:M with M >= 1 sweeps, not %s\n", spec.c_str());
                 exit(2);
             }
+        }
+        else if (s == "--pressure-mg") {
+            // NU[:LEVELS[:COARSE]]: one to three counts, digits only
+            const std::string spec = next();
+            long val[3] = {0, 0, 8};
+            int n = 0;
+            bool ok = true;
+            for (size_t at = 0; ok; ++n) {
+                const size_t c = spec.find(':', at);
+                const std::string part = spec.substr(at, c == std::string::npos ? c : c - at);
+                ok = n < 3 && !part.empty() && part.size() <= 6 && part.find_first_not_of("0123456789") == std::string::npos;
+                if (ok) val[n] = strtol(part.c_str(), nullptr, 10);
+                if (c == std::string::npos) {
+                    ++n;
+                    break;
+                }
+                at = c + 1;
+            }
+            ok = ok && n >= 1 && val[0] >= 1 && val[2] >= 1;
+            if (!ok) {
+                fprintf(stderr, "--pressure-mg takes NU[:LEVELS[:COARSE]] with NU >= 1 sweeps, LEVELS >= 0 and COARSE >= 1, not %s\n",
+                        spec.c_str());
+                exit(2);
+            }
+            o.mg_sweeps = (int)val[0];
+            o.mg_levels = (int)val[1];
+            o.mg_coarse = (int)val[2];
         }
         else if (s == "--maccormack") {
             const std::string which = next();
@@ -409,6 +440,7 @@ static int run(const Options& o) {
     if (o.cg_check_every > 0) SF_CHECK_RETURN(sf_set_pressure_sync(g_ctx, o.cg_check_every));
     if (o.cg_precond != SF_PRECOND_NONE)
         SF_CHECK_RETURN(sf_set_pressure_preconditioner(g_ctx, o.cg_precond, o.cg_precond_sweeps));
+    if (o.mg_sweeps > 0) SF_CHECK_RETURN(sf_set_pressure_multigrid(g_ctx, o.mg_sweeps, o.mg_levels, o.mg_coarse));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

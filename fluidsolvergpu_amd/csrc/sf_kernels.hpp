@@ -3231,6 +3231,121 @@ __global__ void __launch_bounds__(256) cg_direction_z_kernel(Geom g, CgArgs<T> A
     }
 }
 
+// ---- Multigrid V-cycle preconditioner (SPEC §11.3) ----
+// Three row kernels on the fields of one level (a Geom of its own: n_l cells per axis, one ghost plane per side on the
+// coarse levels) with the row shape, the clamped unconditional loads and the stencil of the CG kernels above. They know
+// no solve state: a V-cycle runs in every enqueued iteration and writes only z, its partner and the coarse levels.
+template <class T>
+struct MgArgs {
+    const T* z;    // smooth: the iterate (not loaded by the FIRST form); restrict: the fine z; prolong: the coarse z
+    const T* r;    // smooth, restrict: the level's right-hand side, read on interior cells
+    T* out;        // smooth: the partner of z; restrict: the coarse right-hand side; prolong: the fine z, in place
+    Geom other;    // restrict: the fine level (the launch runs over the coarse rows); prolong: the coarse level
+};
+
+// One damped-Jacobi sweep z' = z + c_s * (r - A z) with set_bnd(0, z'), from z into its partner. FIRST: the sweep from
+// z = +0, which is T(0) + c_s * r bit for bit (A 0 = +0, r - 0 = r) and loads no z.
+template <class T, bool FIRST>
+__global__ void __launch_bounds__(256) mg_smooth_kernel(Geom g, MgArgs<T> A) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const T cs = (T)(1.0 / 7.0);
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type rv = ldv(A.r + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+        if constexpr (FIRST) {
+#pragma unroll
+            for (int e = 0; e < W; ++e) out[e] = T(0) + cs * rv[e];
+        } else {
+            typename VecT<T>::type zc;
+            T az[W];
+            cg_stencil<T, W>(g, A.z, r, m, i0, i0c, zc, az);
+#pragma unroll
+            for (int e = 0; e < W; ++e) out[e] = zc[e] + cs * (rv[e] - az[e]);
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.out, r, i0, out, nv);
+            emit_shells<T, W>(A.out, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
+// Residual and restriction in one pass: one wave per coarse row (J, K); e = r - A z on the four fine rows (2J-1, 2J) x
+// (2K-1, 2K) of the lane's vector, whose W cells start at an odd i and so hold W/2 whole pairs (2I-1, 2I); the eight
+// residuals of a coarse cell are summed pair, rows, planes as §11.3 brackets them and halved. Both levels belong to one
+// slab: local fine planes G + 2P and G + 2P + 1 are the children of local coarse plane G_c + P.
+template <class T>
+__global__ void __launch_bounds__(256) mg_restrict_kernel(Geom gc, MgArgs<T> A) {
+    constexpr int W = VecT<T>::W, H = W / 2;
+    const Geom& gf = A.other;
+    int J, P;
+    if (!reduce_row(gc, J, P)) return;
+    const T half = T(0.5);
+    const long rc = row0(gc, J, gc.G + P);
+    const int nm = (gf.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(gf, m, i0, i0c);
+        T s[2][2][H];
+#pragma unroll
+        for (int dk = 0; dk < 2; ++dk)
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const long rf = row0(gf, 2 * J - 1 + dj, gf.G + 2 * P + dk);
+                typename VecT<T>::type zc;
+                T az[W];
+                cg_stencil<T, W>(gf, A.z, rf, m, i0, i0c, zc, az);
+                const typename VecT<T>::type rv = ldv(A.r + rf + i0c);
+#pragma unroll
+                for (int h = 0; h < H; ++h) s[dk][dj][h] = (rv[2 * h] - az[2 * h]) + (rv[2 * h + 1] - az[2 * h + 1]);
+            }
+        const int I0 = (i0 + 1) / 2;
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+            const T v = half * ((s[0][0][h] + s[0][1][h]) + (s[1][0][h] + s[1][1][h]));
+            if (I0 + h <= gc.N) A.out[rc + I0 + h] = v;
+        }
+    }
+}
+
+// z[i, j, k] += zc[(i+1)/2, (j+1)/2, (k+1)/2] with set_bnd(0, z), in place: one wave per fine row, every lane reads and
+// writes its own cells only (and the shell cells that mirror them).
+template <class T>
+__global__ void __launch_bounds__(256) mg_prolong_kernel(Geom g, MgArgs<T> A) {
+    constexpr int W = VecT<T>::W, H = W / 2;
+    const Geom& gc = A.other;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const long rc = row0(gc, (j + 1) / 2, gc.G + p / 2);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type zv = ldv(A.out + r + i0c);
+        const int I0c = (i0c + 1) / 2;
+        T c[H];
+#pragma unroll
+        for (int h = 0; h < H; ++h) c[h] = A.z[rc + I0c + h];
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) out[e] = zv[e] + c[e / 2];
+        if (nv > 0) {
+            store_cells<T, W>(A.out, r, i0, out, nv);
+            emit_shells<T, W>(A.out, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
 // What a solve does with the sum s of one stage (SPEC §11, §11.2): the stop tests and their status, and alpha and beta
 // as T. The one statement of those rules: cg_scalars_kernel applies it where the scalars live on the device, the
 // host (Solver::cg_sum) where they do not. c: N^3 (STAGE_MU) or tol * tol (STAGE_RHO, STAGE_RHO_PC).

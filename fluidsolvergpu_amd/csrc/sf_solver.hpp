@@ -35,11 +35,25 @@ class Solver final : public SolverBase {
     // z = M(r) of a preconditioned solve and the ping-pong partner of its sweeps (SPEC §11.2). No aliases: these two
     // slots own their buffers, from the first preconditioned solve (pcg_alloc) to ~Solver.
     static constexpr int CG_Z = WORK_SLOT + NSCRATCH, CG_ZP = CG_Z + 1;
+    // The coarse levels l >= 1 of the multigrid preconditioner (SPEC §11.3): z, its partner and the level's right-hand
+    // side, three owning slots per level from the first multigrid solve (mg_alloc) to ~Solver. Level 0 is the z, the
+    // partner and the r of the solve itself.
+    static constexpr int MG_MAXL = 12, MG_SLOT = CG_ZP + 1;
+    static constexpr int mg_z(int l) { return MG_SLOT + 3 * (l - 1); }
+    static constexpr int mg_zp(int l) { return mg_z(l) + 1; }
+    static constexpr int mg_r(int l) { return mg_z(l) + 2; }
+
+    // The geometry of the fields an operator runs on: the solver-wide one (lv0_, the default everywhere) or a coarse
+    // level of the multigrid hierarchy, whose fields have n cells per axis, n / P planes per slab and one ghost plane.
+    struct Level {
+        int N = 0, nzl = 0, G = 1, np = 0, px = 0;
+        long plane = 0, elems = 0, pad_front = 0, pad_back = 0;
+    };
 
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
         sfk::Geom geom{};
-        T* field[SF_NUM_FIELDS + NSCRATCH + 2] = {};
+        T* field[SF_NUM_FIELDS + NSCRATCH + 2 + 3 * (MG_MAXL - 1)] = {};
         T* scratch[NSCRATCH] = {};
         T* snap[4] = {};               // snapshot buffers for asynchronous output
         hipStream_t os = nullptr;      // output (copy) stream
@@ -179,6 +193,8 @@ public:
         // stored to, and what is loaded there only feeds rows that are not stored.
         pad_front_ = (sfk::SK_PAD_ROWS_FRONT * (long)px_ + 63) / 64 * 64;
         pad_back_ = sfk::SK_PAD_ROWS_BACK * (long)px_;
+        lv0_.N = N_, lv0_.nzl = nzl_, lv0_.G = G_, lv0_.np = nplanes_, lv0_.px = px_;
+        lv0_.plane = plane_, lv0_.elems = field_elems_, lv0_.pad_front = pad_front_, lv0_.pad_back = pad_back_;
 
         slabs_.resize(L_);
         for (int s = 0; s < L_; ++s) {
@@ -362,6 +378,8 @@ public:
         for (Slab& sl : slabs_) {
             for (int f = 0; f < SF_NUM_FIELDS; ++f) free_field(sl.field[f]);  // not the internal slots: aliases
             for (int f : {CG_Z, CG_ZP}) free_field(sl.field[f]);               // ... but for these two
+            for (int f = MG_SLOT; f < MG_SLOT + 3 * (MG_MAXL - 1); ++f)        // ... and the coarse levels (no padding)
+                if (sl.field[f]) (void)hipFree(sl.field[f]);
             for (T*& f : sl.scratch) free_field(f);
             if (sl.d_flag) (void)hipFree(sl.d_flag);
             if (sl.red_rows) (void)hipFree(sl.red_rows);
@@ -1210,6 +1228,42 @@ public:
         out->kind = precond_;
         out->sweeps = precond_sweeps_;
     }
+    void set_pressure_multigrid(int sweeps, int max_levels, int coarse_sweeps) override {
+        SF_REQUIRE(sweeps >= 0, "pressure multigrid: sweeps must be >= 0 (0: off)");
+        SF_REQUIRE(max_levels >= 0, "pressure multigrid: max_levels must be >= 0 (0: as deep as N allows)");
+        SF_REQUIRE(coarse_sweeps >= 1, "pressure multigrid: coarse_sweeps must be >= 1");
+        if (sweeps >= 1) {
+            // every coarse level must split into whole planes per slab, so that no restriction crosses a slab
+            const std::vector<int> n = mg_sizes(max_levels);
+            int ok = 1;
+            while (ok < (int)n.size() && n[ok] % P_ == 0) ++ok;
+            if (ok < (int)n.size())
+                throw Failure{SF_ERR_INVALID, "pressure multigrid: level " + std::to_string(ok) + " of N = " + std::to_string(N_) +
+                                                  " has " + std::to_string(n[ok]) + " planes, not divisible by the " +
+                                                  std::to_string(P_) + " slabs: the largest admissible max_levels is " +
+                                                  std::to_string(ok)};
+        }
+        mg_nu_ = sweeps;
+        mg_maxl_ = max_levels;
+        mg_nuc_ = coarse_sweeps;
+    }
+    void pressure_multigrid(sf_pressure_multigrid* out) const override {
+        out->sweeps = mg_nu_;
+        out->max_levels = mg_maxl_;
+        out->coarse_sweeps = mg_nuc_;
+        out->levels = (int)mg_sizes(mg_maxl_).size();
+    }
+    void precondition(int z, int r) override {
+        check_distinct("precondition: z and r must be different fields", {z, r});
+        const int pm = precond_sweeps_in_force();
+        SF_REQUIRE(pm > 0, "precondition: no preconditioner is in force");
+        SF_HIP(hipSetDevice(device_));
+        pcg_alloc();
+        for (Slab& sl : slabs_)
+            for (int f : {z, r}) ensure(sl, f);
+        join();
+        op_precondition(pm, z, r);
+    }
     void pressure_sync(sf_pressure_sync* out) const override {
         out->check_every = check_every_;
         out->host_waits = host_waits_;
@@ -1428,15 +1482,16 @@ private:
         return c;
     }
 
-    T* alloc_field() {
+    T* alloc_field(const Level* lv = nullptr) {
+        const Level& h = lv ? *lv : lv0_;
         T* p = nullptr;
-        const size_t total = (size_t)(pad_front_ + field_elems_ + pad_back_) * sizeof(T);
+        const size_t total = (size_t)(h.pad_front + h.elems + h.pad_back) * sizeof(T);
         SF_HIP(hipMalloc(&p, total));
         SF_HIP(hipMemset(p, 0, total));
         // hipMemset on device memory may return before the fill has run, and the context's streams are
         // non-blocking (they do not order against the null stream): wait here.
         SF_HIP(hipDeviceSynchronize());
-        return p + pad_front_;
+        return p + h.pad_front;
     }
     void free_field(T* f) const {
         if (f) (void)hipFree(f - pad_front_);
@@ -1640,17 +1695,26 @@ private:
         if (comm_) SF_HIP(hipMalloc(&red_gather_, nv * N_ * sizeof(double)));
         SF_HIP(hipHostMalloc(&red_host_, nv * N_ * sizeof(double), hipHostMallocDefault));
     }
-    unsigned row_blocks() const { return (unsigned)ceil_div((long)N_ * nzl_, 4L); }
+    unsigned row_blocks(const Level& h) const { return (unsigned)ceil_div((long)h.N * h.nzl, 4L); }
+    // a slab's geometry on a level: its share of the level's planes, the wall flags of the slab
+    sfk::Geom level_geom(const Slab& sl, const Level& h) const {
+        sfk::Geom g = sl.geom;
+        g.N = h.N, g.nzl = h.nzl, g.G = h.G, g.np = h.np, g.px = h.px, g.plane = h.plane;
+        g.kg0 = sl.gid * h.nzl + 1 - h.G;
+        return g;
+    }
     // One row kernel (one wave per row, the nzl planes of a slab in one launch: SPEC §10, §11) on every slab's compute
     // stream, with its trace. args(sl): the kernel's argument after the geometry; acc(sl): its field accesses. RECORDS:
     // the kernel also takes, and writes, the slab's row records.
+    // lv: the level whose rows the launch runs over (the multigrid kernels; no row records there).
     template <bool RECORDS = true, class K, class ArgsF, class AccF>
-    void launch_rows(const char* name, K kernel, ArgsF args, AccF acc) {
+    void launch_rows(const char* name, K kernel, ArgsF args, AccF acc, const Level* lv = nullptr) {
+        const Level& h = lv ? *lv : lv0_;
         for (Slab& sl : slabs_) {
             if constexpr (RECORDS)
-                hipLaunchKernelGGL(kernel, dim3(row_blocks()), dim3(256), 0, sl.cs, sl.geom, args(sl), sl.red_rows, rows_pad());
+                hipLaunchKernelGGL(kernel, dim3(row_blocks(h)), dim3(256), 0, sl.cs, sl.geom, args(sl), sl.red_rows, rows_pad());
             else
-                hipLaunchKernelGGL(kernel, dim3(row_blocks()), dim3(256), 0, sl.cs, sl.geom, args(sl));
+                hipLaunchKernelGGL(kernel, dim3(row_blocks(h)), dim3(256), 0, sl.cs, lv ? level_geom(sl, h) : sl.geom, args(sl));
             SF_HIP(hipGetLastError());
             if (!trace_) continue;
             std::vector<Acc> a = acc(sl);
@@ -1785,24 +1849,24 @@ private:
     // process — or the loopback stand-in — the planes READ are this slab's own outgoing ones)
     template <int NF>
     void tr_halo(const char* name, Slab& sl, hipStream_t st, const int (&fields)[NF], Slab* lo, Slab* hi, bool lo_remote,
-                 bool hi_remote) {
+                 bool hi_remote, const Level& h) {
         if (!trace_) return;
         std::vector<Acc> acc;
         for (int f = 0; f < NF; ++f) {
             const T* mine = sl.field[fields[f]];
-            if (lo) acc.push_back({lo->field[fields[f]], false, nzl_, nzl_ + G_});
-            if (lo_remote) acc.push_back({mine, false, G_, 2 * G_});
-            if (lo || lo_remote) acc.push_back({mine, true, 0, G_});
-            if (hi) acc.push_back({hi->field[fields[f]], false, G_, 2 * G_});
-            if (hi_remote) acc.push_back({mine, false, nzl_, nzl_ + G_});
-            if (hi || hi_remote) acc.push_back({mine, true, G_ + nzl_, 2 * G_ + nzl_});
+            if (lo) acc.push_back({lo->field[fields[f]], false, h.nzl, h.nzl + h.G});
+            if (lo_remote) acc.push_back({mine, false, h.G, 2 * h.G});
+            if (lo || lo_remote) acc.push_back({mine, true, 0, h.G});
+            if (hi) acc.push_back({hi->field[fields[f]], false, h.G, 2 * h.G});
+            if (hi_remote) acc.push_back({mine, false, h.nzl, h.nzl + h.G});
+            if (hi || hi_remote) acc.push_back({mine, true, h.G + h.nzl, 2 * h.G + h.nzl});
         }
         tr_op(name, sl, st, acc);
     }
     template <int NF>
-    void tr_xchg(const int (&fields)[NF]) {
+    void tr_xchg(const int (&fields)[NF], const Level& h) {
         if (!trace_) return;
-        std::fprintf(trace_, "{\"t\":\"xchg\",\"seq\":%ld,\"G\":%d,\"fields\":[", xchg_seq_, G_);
+        std::fprintf(trace_, "{\"t\":\"xchg\",\"seq\":%ld,\"G\":%d,\"fields\":[", xchg_seq_, h.G);
         for (int f = 0; f < NF; ++f) std::fprintf(trace_, "%s%d", f ? "," : "", fields[f]);
         std::fprintf(trace_, "]}\n");
     }
@@ -1812,8 +1876,8 @@ private:
     struct HaloPlanes {
         size_t count, send_lo, send_hi, recv_lo, recv_hi;
     };
-    HaloPlanes halo_planes() const {
-        return {(size_t)G_ * plane_, (size_t)G_ * plane_, (size_t)nzl_ * plane_, 0, (size_t)(G_ + nzl_) * plane_};
+    HaloPlanes halo_planes(const Level& h) const {
+        return {(size_t)h.G * h.plane, (size_t)h.G * h.plane, (size_t)h.nzl * h.plane, 0, (size_t)(h.G + h.nzl) * h.plane};
     }
     // stream st of local slab s waits for event e of that slab and of its neighbours in this process
     void wait_neighbourhood(int s, hipStream_t st, hipEvent_t Slab::*e) {
@@ -1833,8 +1897,8 @@ private:
     // ghost planes from slab `hi` (null: that side is not copied). A neighbour gives the planes next to sl; sl itself
     // (the loopback stand-in) the planes it would send that way.
     template <int NF>
-    void halo_copy(Slab& sl, const int (&fields)[NF], const Slab* lo, const Slab* hi) {
-        const HaloPlanes h = halo_planes();
+    void halo_copy(Slab& sl, const int (&fields)[NF], const Slab* lo, const Slab* hi, const Level& lv) {
+        const HaloPlanes h = halo_planes(lv);
         sfk::HaloCopyArgs H;
         H.nseg = 0;
         H.n16 = (long)(h.count * sizeof(T) / 16);
@@ -1856,16 +1920,18 @@ private:
 
     // Halo exchange of NF fields: first / last interior plane -> neighbour's ghost plane.
     // Must follow for_planes (uses boundary_done). Compute streams wait on the result.
+    // lv: the level the fields live on (a coarse level of the multigrid hierarchy ships its one ghost plane).
     template <int NF>
-    void exchange(const int (&fields)[NF]) {
+    void exchange(const int (&fields)[NF], const Level* lvp = nullptr) {
         if (P_ == 1) return;
-        tr_xchg<NF>(fields);
+        const Level& lv = lvp ? *lvp : lv0_;
+        tr_xchg<NF>(fields, lv);
         ++xchg_seq_;
         if (rccl_self_) {
-            exchange_rccl_self<NF>(fields);
+            exchange_rccl_self<NF>(fields, lv);
             return;
         }
-        const HaloPlanes h = halo_planes();
+        const HaloPlanes h = halo_planes(lv);
         for (int s = 0; s < L_; ++s) {
             Slab& sl = slabs_[s];
             wait_neighbourhood(s, sl.hs, &Slab::boundary_done);
@@ -1873,15 +1939,15 @@ private:
             Slab* lo = s > 0 ? &slabs_[s - 1] : nullptr;
             Slab* hi = s < L_ - 1 ? &slabs_[s + 1] : nullptr;
             if (lo || hi) {
-                halo_copy<NF>(sl, fields, lo, hi);
-                tr_halo<NF>("halo_pull", sl, sl.hs, fields, lo, hi, false, false);
+                halo_copy<NF>(sl, fields, lo, hi, lv);
+                tr_halo<NF>("halo_pull", sl, sl.hs, fields, lo, hi, false, false, lv);
             }
             // neighbours in other processes: grouped send/recv over RCCL (xGMI point-to-point)
             const bool lo_remote = sl.gid > 0 && !lo, hi_remote = sl.gid < P_ - 1 && !hi;
             if ((lo_remote || hi_remote) && loopback_) {
                 // SF_FLAG_LOOPBACK_HALO: same bytes, same stream, same dependencies, but from this slab's own planes
-                halo_copy<NF>(sl, fields, lo_remote ? &sl : nullptr, hi_remote ? &sl : nullptr);
-                tr_halo<NF>("halo_loopback", sl, sl.hs, fields, nullptr, nullptr, lo_remote, hi_remote);
+                halo_copy<NF>(sl, fields, lo_remote ? &sl : nullptr, hi_remote ? &sl : nullptr, lv);
+                tr_halo<NF>("halo_loopback", sl, sl.hs, fields, nullptr, nullptr, lo_remote, hi_remote, lv);
             } else if (lo_remote || hi_remote) {
                 const ncclDataType_t dt = sizeof(T) == 4 ? ncclFloat : ncclDouble;
                 SF_NCCL(ncclGroupStart());
@@ -1898,7 +1964,7 @@ private:
                 }
                 SF_NCCL(ncclGroupEnd());
                 ++rccl_groups_;
-                tr_halo<NF>("halo_rccl", sl, sl.hs, fields, nullptr, nullptr, lo_remote, hi_remote);
+                tr_halo<NF>("halo_rccl", sl, sl.hs, fields, nullptr, nullptr, lo_remote, hi_remote, lv);
             }
             ev_record(sl, &Slab::halo_done, sl.hs);
         }
@@ -1913,9 +1979,9 @@ private:
     // the neighbour's ghost planes); one group spans all slabs because a send to self needs its receive in the same
     // group.
     template <int NF>
-    void exchange_rccl_self(const int (&fields)[NF]) {
+    void exchange_rccl_self(const int (&fields)[NF], const Level& lv) {
         const ncclDataType_t dt = sizeof(T) == 4 ? ncclFloat : ncclDouble;
-        const HaloPlanes h = halo_planes();
+        const HaloPlanes h = halo_planes(lv);
         for (int s = 0; s < L_; ++s) wait_neighbourhood(s, slabs_[s].hs, &Slab::boundary_done);
         SF_NCCL(ncclGroupStart());
         for (int s = 0; s + 1 < L_; ++s) {
@@ -1936,16 +2002,16 @@ private:
         ++rccl_groups_;
         for (int s = 0; s < L_; ++s)
             tr_halo<NF>("halo_rccl_self", slabs_[s], slabs_[s].hs, fields, s > 0 ? &slabs_[s - 1] : nullptr,
-                        s < L_ - 1 ? &slabs_[s + 1] : nullptr, false, false);
+                        s < L_ - 1 ? &slabs_[s + 1] : nullptr, false, false, lv);
         for (int s = 0; s < L_; ++s) ev_record(slabs_[s], &Slab::halo_done, slabs_[s].hs);
         consumers_wait_halo();
     }
     // after whole-field kernels wrote field x on every slab's compute stream: its ghost planes
-    void publish_from_cs(int x) {
+    void publish_from_cs(int x, const Level* lv = nullptr) {
         if (P_ == 1) return;
         for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
         const int fs[1] = {x};
-        exchange<1>(fs);
+        exchange<1>(fs, lv);
     }
 
     template <int NF>
@@ -2732,7 +2798,7 @@ private:
     // issued (exchange() takes slots), as `hat` is in op_advect_mc. Every row kernel runs a slab's nzl planes in one
     // launch on its compute stream; d's ghost planes travel on the halo stream after every update of d.
     // One skeleton, cg_iterate<DEV>, issues the solve: plain (§11) or with z = M(r) and a third sum, r.z, in every
-    // iteration (§11.2, op_precondition); with the scalars on the host (check_every_ = 0) or on the device (m >= 1).
+    // iteration (§11.2, op_precondition: the Jacobi sweeps, or the V-cycle of §11.3); with the scalars on the host (check_every_ = 0) or on the device (m >= 1).
     // The two forms differ in what a sum's stage is (cg_sum), in the kernels' DEV parameter and argument (cg_args) and
     // in the state that the DEV forms add to a kernel's trace; what a stage does with its sum (the stop tests, their
     // status, alpha and beta as T) is sfk::cg_stage on both. Host waits: one per sum by value (2 + 2 per iteration,
@@ -2840,19 +2906,127 @@ private:
     // the two owning slots. A pass of s fused sweeps reads its right-hand side s - 1 planes beyond its own, so r's ghost
     // planes go first; it runs whether or not the solve is still active (the Jacobi kernels know no state) and leaves the
     // compute streams joined for the row kernel that follows.
-    void op_precondition(int sweeps) {
-        publish_from_cs(CG_R);
+    // The one place that chooses M: the V-cycle of §11.3 while sf_set_pressure_multigrid has it in force, else the sweeps.
+    // z, r: the slots of the solve, or the two fields of sf_precondition.
+    void op_precondition(int sweeps, int z = CG_Z, int r = CG_R) {
+        if (mg_nu_ > 0) {
+            op_vcycle(z, r);
+            return;
+        }
+        publish_from_cs(r);
         // as in op_project: a fused first pass takes the zero iterate as literal zeros, any other reads it
         const bool implicit_zero = can_fuse2() && sweeps >= 2 && sw_.zero_skip;
         if (!implicit_zero) {
             join();
             for (Slab& sl : slabs_) {
-                SF_HIP(hipMemsetAsync(sl.field[CG_Z], 0, (size_t)field_elems_ * sizeof(T), sl.cs));
-                tr_whole("zero_z", sl, {}, {sl.field[CG_Z]});
+                SF_HIP(hipMemsetAsync(sl.field[z], 0, (size_t)field_elems_ * sizeof(T), sl.cs));
+                tr_whole("zero_z", sl, {}, {sl.field[z]});
             }
         }
-        const int zs[1] = {CG_Z}, rs[1] = {CG_R}, b0[1] = {0}, zp[1] = {CG_ZP};
+        const int zs[1] = {z}, rs[1] = {r}, b0[1] = {0}, zp[1] = {CG_ZP};
         op_lin_solve<1>(zs, rs, b0, T(1), T(6), sweeps, false, implicit_zero, nullptr, &zp);
+        join();
+    }
+    // sweeps of the z = M(r) in force: nu of the V-cycle, m of the Jacobi kind, 0 without a preconditioner
+    int precond_sweeps_in_force() const {
+        return mg_nu_ > 0 ? mg_nu_ : (precond_ == SF_PRECOND_JACOBI ? precond_sweeps_ : 0);
+    }
+
+    // ---- its multigrid preconditioner (SPEC §11.3) ----
+    // n_0 = N and n_{l+1} = n_l / 2 while n_l is even, n_l / 2 >= 4 and the depth allows: N and max_levels decide alone
+    std::vector<int> mg_sizes(int max_levels) const {
+        std::vector<int> n{N_};
+        while (n.back() % 2 == 0 && n.back() / 2 >= 4 && (max_levels == 0 || (int)n.size() < max_levels) &&
+               (int)n.size() < MG_MAXL)
+            n.push_back(n.back() / 2);
+        return n;
+    }
+    // Level 0 is the solver's own geometry; a coarse level has the row layout of §4 for its n, one ghost plane per
+    // side and no padding (the marching kernel never runs there).
+    std::vector<Level> mg_levels() const {
+        std::vector<Level> lv{lv0_};
+        const std::vector<int> n = mg_sizes(mg_maxl_);
+        const int line = 128 / (int)sizeof(T);
+        for (size_t l = 1; l < n.size(); ++l) {
+            Level h;
+            h.N = n[l];
+            h.nzl = n[l] / P_;
+            h.G = 1;
+            h.np = h.nzl + 2;
+            h.px = ceil_div(lead_ + n[l] + 1 + W, line) * line;
+            h.plane = (long)h.px * (n[l] + 2);
+            h.elems = (h.plane * h.np + 256 + W - 1) / W * W;
+            lv.push_back(h);
+        }
+        return lv;
+    }
+    // One symmetric V-cycle z = V(0, r) (SPEC §11.3): down with nu sweeps from zero and the restricted residual per
+    // level, nu_c sweeps on the coarsest, up with the correction and nu sweeps. Every kernel runs on the compute stream
+    // of its slab; the ghost planes of z on a level travel after every sweep and after the correction (so they are
+    // current before each sweep and before the residual), those of the coarse right-hand sides never (read on own planes
+    // only). Leaves the compute streams joined.
+    void op_vcycle(int z, int r) {
+        const std::vector<Level> lv = mg_levels();
+        const int nl = (int)lv.size();
+        for (Slab& sl : slabs_)
+            for (int l = 1; l < nl; ++l)
+                for (int f : {mg_z(l), mg_zp(l), mg_r(l)})
+                    if (!sl.field[f]) sl.field[f] = alloc_field(&lv[l]);
+        auto zs = [&](int l) { return l == 0 ? z : mg_z(l); };
+        auto ps = [&](int l) { return l == 0 ? CG_ZP : mg_zp(l); };
+        auto rs = [&](int l) { return l == 0 ? r : mg_r(l); };
+        auto lp = [&](int l) { return l == 0 ? (const Level*)nullptr : &lv[l]; };
+        auto geom = [&](Slab& sl, int l) { return l == 0 ? sl.geom : level_geom(sl, lv[l]); };
+        // planes a launch over the level's own planes writes: the shell plane of a wall slab included
+        auto written = [&](Slab& sl, int l, const T* buf) {
+            const Level& h = lv[l];
+            return Acc{buf, true, sl.geom.wall_lo ? h.G - 1 : h.G, h.G + h.nzl + (sl.geom.wall_hi ? 1 : 0)};
+        };
+        auto sweeps = [&](int l, int count, bool from_zero) {
+            const Level& h = lv[l];
+            for (int t = 0; t < count; ++t) {
+                join();  // z's ghost planes
+                const bool first = from_zero && t == 0;
+                auto args = [&](Slab& sl) { return sfk::MgArgs<T>{sl.field[zs(l)], sl.field[rs(l)], sl.field[ps(l)], sfk::Geom{}}; };
+                auto acc = [&](Slab& sl) {
+                    std::vector<Acc> a{{sl.field[rs(l)], false, h.G, h.G + h.nzl}, written(sl, l, sl.field[ps(l)])};
+                    if (!first) a.push_back({sl.field[zs(l)], false, h.G - 1, h.G + h.nzl + 1});
+                    return a;
+                };
+                if (first)
+                    launch_rows<false>("mg_smooth0", sfk::mg_smooth_kernel<T, true>, args, acc, lp(l));
+                else
+                    launch_rows<false>("mg_smooth", sfk::mg_smooth_kernel<T, false>, args, acc, lp(l));
+                swap_slots(zs(l), ps(l));
+                publish_from_cs(zs(l), lp(l));
+            }
+        };
+        for (int l = 0;; ++l) {
+            sweeps(l, l < nl - 1 ? mg_nu_ : mg_nuc_, true);
+            if (l == nl - 1) break;
+            const Level &hf = lv[l], &hc = lv[l + 1];
+            join();  // the residual reads z's ghost planes
+            launch_rows<false>("mg_restrict", sfk::mg_restrict_kernel<T>,
+                               [&](Slab& sl) { return sfk::MgArgs<T>{sl.field[zs(l)], sl.field[rs(l)], sl.field[rs(l + 1)], geom(sl, l)}; },
+                               [&](Slab& sl) {
+                                   return std::vector<Acc>{{sl.field[zs(l)], false, hf.G - 1, hf.G + hf.nzl + 1},
+                                                           {sl.field[rs(l)], false, hf.G, hf.G + hf.nzl},
+                                                           {sl.field[rs(l + 1)], true, hc.G, hc.G + hc.nzl}};
+                               }, &hc);
+        }
+        for (int l = nl - 2; l >= 0; --l) {
+            const Level &hf = lv[l], &hc = lv[l + 1];
+            join();
+            launch_rows<false>("mg_prolong", sfk::mg_prolong_kernel<T>,
+                               [&](Slab& sl) { return sfk::MgArgs<T>{sl.field[zs(l + 1)], nullptr, sl.field[zs(l)], geom(sl, l + 1)}; },
+                               [&](Slab& sl) {
+                                   return std::vector<Acc>{{sl.field[zs(l + 1)], false, hc.G, hc.G + hc.nzl},
+                                                           {sl.field[zs(l)], false, hf.G, hf.G + hf.nzl},
+                                                           written(sl, l, sl.field[zs(l)])};
+                               }, lp(l));
+            publish_from_cs(zs(l), lp(l));
+            sweeps(l, mg_nu_, false);
+        }
         join();
     }
 
@@ -2973,7 +3147,7 @@ private:
                           sfk::CG_ST_BREAKDOWN == SF_CG_BREAKDOWN, "CgState::status holds sf_cg_status values");
         const bool dev = check_every_ > 0;  // the scalars on the device, read back every check_every_ iterations
         if (dev) cg_state_alloc();
-        const int pm = precond_ == SF_PRECOND_JACOBI ? precond_sweeps_ : 0;  // sweeps of z = M(r); 0: §11 as it stands
+        const int pm = precond_sweeps_in_force();  // sweeps of z = M(r); 0: §11 as it stands
         if (pm > 0) pcg_alloc();
         host_waits_ = 0;
         ScratchAlias work_slots(slabs_, 3);
@@ -3103,6 +3277,7 @@ private:
     double cg_tol_ = 1e-3;
     int check_every_ = 0, host_waits_ = 0;  // sf_set_pressure_sync; host waits of the last CG projection
     int precond_ = SF_PRECOND_NONE, precond_sweeps_ = 0;  // sf_set_pressure_preconditioner (SPEC §11.2)
+    int mg_nu_ = 0, mg_maxl_ = 0, mg_nuc_ = 8;            // sf_set_pressure_multigrid (SPEC §11.3); nu = 0: off
     long long host_waits_total_ = 0;
     sf_pressure_info info_{SF_PRESSURE_JACOBI, SF_CG_MAX_ITERS, 0, -1.0, 0, 0};  // the last projection
     int num_cu_ = 256;
@@ -3111,6 +3286,7 @@ private:
     bool ishell_skip_ = true;
     long sk2_min_cells_ = 60000000;  // smallest launch a TWO-sweep marching pass takes (launch_pass)
     long plane_ = 0, field_elems_ = 0, pad_front_ = 0, pad_back_ = 0;
+    Level lv0_;  // the solver-wide geometry above as a Level: the default of every function that takes one
     std::vector<Slab> slabs_;
     FILE* trace_ = nullptr;  // SF_TRACE_SCHEDULE
     bool inject_trap_bug_ = false;

@@ -50,6 +50,7 @@ ABI_SYMBOLS = (
     "sf_set_pressure_solver", "sf_project_cg", "sf_poisson_residual", "sf_pressure_info_get",
     "sf_set_pressure_sync", "sf_pressure_sync_get",
     "sf_set_pressure_preconditioner", "sf_pressure_preconditioner_get",
+    "sf_set_pressure_multigrid", "sf_pressure_multigrid_get", "sf_precondition",
 )
 
 
@@ -79,6 +80,11 @@ class SfPressureSync(C.Structure):
 class SfPressurePreconditioner(C.Structure):
     """sf_pressure_preconditioner of include/sfgpu.h (docs/SPEC.md §11.2)."""
     _fields_ = [("kind", C.c_int), ("sweeps", C.c_int)]
+
+
+class SfPressureMultigrid(C.Structure):
+    """sf_pressure_multigrid of include/sfgpu.h (docs/SPEC.md §11.3)."""
+    _fields_ = [("sweeps", C.c_int), ("max_levels", C.c_int), ("coarse_sweeps", C.c_int), ("levels", C.c_int)]
 
 
 _ctx = C.c_void_p
@@ -123,6 +129,9 @@ lib.sf_set_pressure_sync.argtypes = [_ctx, C.c_int]
 lib.sf_pressure_sync_get.argtypes = [_ctx, C.POINTER(SfPressureSync)]
 lib.sf_set_pressure_preconditioner.argtypes = [_ctx, C.c_int, C.c_int]
 lib.sf_pressure_preconditioner_get.argtypes = [_ctx, C.POINTER(SfPressurePreconditioner)]
+lib.sf_set_pressure_multigrid.argtypes = [_ctx, C.c_int, C.c_int, C.c_int]
+lib.sf_pressure_multigrid_get.argtypes = [_ctx, C.POINTER(SfPressureMultigrid)]
+lib.sf_precondition.argtypes = [_ctx, C.c_int, C.c_int]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -370,6 +379,26 @@ class FluidSolver:
         d = SfPressurePreconditioner()
         self._ck(lib.sf_pressure_preconditioner_get(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in SfPressurePreconditioner._fields_}
+
+    def set_pressure_multigrid(self, sweeps, max_levels=0, coarse_sweeps=8):
+        """The multigrid preconditioner of the CG solve (SPEC §11.3): sweeps = nu >= 1 puts one symmetric V-cycle per
+        iteration in force (nu damped-Jacobi sweeps before and after each coarse-grid correction, coarse_sweeps on the
+        coarsest level, at most max_levels levels; 0: as many as N allows); sweeps = 0 switches it off again and the
+        setting of set_pressure_preconditioner, kept meanwhile, applies."""
+        self._ck(lib.sf_set_pressure_multigrid(self._h, int(sweeps), int(max_levels), int(coarse_sweeps)))
+
+    @property
+    def pressure_multigrid(self):
+        """sweeps, max_levels and coarse_sweeps as last set, and levels, the depth of the hierarchy for this N
+        (sf_pressure_multigrid_get)."""
+        d = SfPressureMultigrid()
+        self._ck(lib.sf_pressure_multigrid_get(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in SfPressureMultigrid._fields_}
+
+    def precondition(self, z, r):
+        """z = M(r) with the preconditioner in force (the V-cycle of §11.3, else the Jacobi sweeps of §11.2): r is read
+        on interior cells, z is written whole."""
+        self._ck(lib.sf_precondition(self._h, _fid(z), _fid(r)))
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

@@ -309,6 +309,32 @@ typedef struct sf_pressure_preconditioner { int kind; int sweeps; } sf_pressure_
 int sf_set_pressure_preconditioner(sf_ctx* ctx, int kind, int sweeps);
 int sf_pressure_preconditioner_get(const sf_ctx* ctx, sf_pressure_preconditioner* out);
 
+/* Multigrid preconditioner of the CG solve (docs/SPEC.md §11.3): z = M(r) is one symmetric V-cycle of cell-centred
+ * geometric multigrid on A, so the iteration count no longer grows with N (the Jacobi sweeps above cut it by sqrt(2 m)
+ * only). Levels n_0 = N, n_{l+1} = n_l / 2 while n_l is even, n_l / 2 >= 4 and the depth allows; the smoother is damped
+ * Jacobi (omega = 6/7), the restriction half the sum of the eight children's residuals, the prolongation the parent's
+ * value; an N that does not coarsen (odd, < 8) runs coarse_sweeps sweeps on the fine grid.
+ *   sf_set_pressure_multigrid(sweeps, max_levels, coarse_sweeps): sweeps = nu >= 1 puts the V-cycle in force for
+ *       sf_project_cg and for vel_step with SF_PRESSURE_CG: nu sweeps before and after every coarse-grid correction,
+ *       coarse_sweeps (>= 1) on the coarsest level, at most max_levels levels (0: as many as N allows). sweeps = 0 (the
+ *       default) is off; max_levels and coarse_sweeps are then kept but not used, and a context that never enables it
+ *       issues the launches it issued before. While the V-cycle is in force the kind and sweeps of
+ *       sf_set_pressure_preconditioner are kept, reported unchanged by its getter and not used; sweeps = 0 again
+ *       restores exactly the solve they describe. On a decomposed context every coarse level n_l (l >= 1) must be
+ *       divisible by the number of slabs, so that no restriction crosses a slab (64 over 4 slabs: all five levels; over
+ *       8: four; 40 over 2: three). Negative sweeps or max_levels, coarse_sweeps < 1 or such a decomposition:
+ *       SF_ERR_INVALID, the message names the largest admissible max_levels, and the setting is unchanged. The first
+ *       multigrid solve allocates the coarse levels (three fields each) and the two work fields of §11.2. Same bits for
+ *       every admissible decomposition, transport and check_every; per context and the same on every rank.
+ *   sf_pressure_multigrid_get: the three values as last set, and levels: the depth L of the hierarchy for this N.
+ *   sf_precondition(z, r): the operator singly, z = M(r) with whatever preconditioner is in force (the V-cycle, or with
+ *       SF_PRECOND_JACOBI lin_solve(0, z, r, 1, 6, m) from zero). r is read on interior cells; z is written whole,
+ *       shells included. SF_ERR_INVALID if none is in force or if z == r. */
+typedef struct sf_pressure_multigrid { int sweeps, max_levels, coarse_sweeps, levels; } sf_pressure_multigrid;
+int sf_set_pressure_multigrid(sf_ctx* ctx, int sweeps, int max_levels, int coarse_sweeps);
+int sf_pressure_multigrid_get(const sf_ctx* ctx, sf_pressure_multigrid* out);
+int sf_precondition(sf_ctx* ctx, int z, int r);
+
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);
 int sf_set_coefficients(sf_ctx* ctx, double dt, double diff, double visc);

@@ -18,7 +18,9 @@ under its own time limit (--limit seconds, SIGALRM: the process ends with status
   precond     (--precond 0,2,4,8) one context per grid; for every sweep count M of the Jacobi preconditioner of SPEC §11.2
               (0: none): the time of one iteration as in `sync` (with --sync M' the scalars on the device, read every M'
               iterations; without, on the host), the iterations to tol = 1e-3 from the same state and the time of that
-              projection, and, for --step-case, the step with CG at each --tols.
+              projection, and, for --step-case, the step with CG at each --tols. --mg NU[:LEVELS[:COARSE]],... adds the
+              multigrid V-cycle of SPEC §11.3 at each of those settings to the same table (rows with "mg"), measured
+              on the same context, after the sweep counts.
   step        vel_step + dens_step per step (host wall time of --steps steps between syncs) with Jacobi K = 20 and with
               CG at each --tols, the iterations per step, and sf_poisson_residual / max_div of what the last step left.
 
@@ -26,6 +28,7 @@ under its own time limit (--limit seconds, SIGALRM: the process ends with status
   python tools/pressure_bench.py --cases 256:f32 --no-step   # e.g. under rocprofv3 --kernel-trace --stats
   python tools/pressure_bench.py --sync --cases 64:f32 128:f32 256:f32 512:f32 256:f64   # where the scalars live
   python tools/pressure_bench.py --precond 0,2,4,8 --sync 8 --cases 64:f32 128:f32 256:f32 512:f32 256:f64
+  python tools/pressure_bench.py --precond 0,8 --mg 2,2:0:16,1,2:4 --cases 64:f32 128:f32 256:f32 512:f32 256:f64
 """
 import argparse
 import json
@@ -116,11 +119,28 @@ def sync_case(N, dtype, slabs, iters, reps, check_every):
     return rows
 
 
+def parse_mg(spec):
+    """NU[:LEVELS[:COARSE]] -> (nu, max_levels, coarse_sweeps), the driver's --pressure-mg."""
+    parts = [int(x) for x in spec.split(":")]
+    if not 1 <= len(parts) <= 3 or parts[0] < 1:
+        raise SystemExit(f"--mg takes NU[:LEVELS[:COARSE]] with NU >= 1, not {spec}")
+    return tuple(parts + [0, 8][len(parts) - 1:])
+
+
 def set_precond(fs, sweeps):
+    """sweeps: a count of Jacobi sweeps (0: none) or the (nu, max_levels, coarse_sweeps) of the V-cycle."""
+    if isinstance(sweeps, tuple):
+        fs.set_pressure_multigrid(*sweeps)
+        return
+    fs.set_pressure_multigrid(0)
     if sweeps > 0:
         fs.set_pressure_preconditioner("jacobi", sweeps)
     else:
         fs.set_pressure_preconditioner("none")
+
+
+def precond_label(sweeps):
+    return {"sweeps": None, "mg": "%d:%d:%d" % sweeps} if isinstance(sweeps, tuple) else {"sweeps": sweeps}
 
 
 def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters):
@@ -149,7 +169,7 @@ def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters):
         t0 = min(solve(1e-30, 0)[0] for _ in range(reps))
         tm, info = min((solve(1e-30, iters) for _ in range(reps)), key=lambda r: r[0])
         tp, done = min((solve(1e-3, max_iters) for _ in range(reps)), key=lambda r: r[0])
-        rows.append({"case": "precond", "grid": N, "dtype": dtype, "sweeps": m, "check_every": check_every,
+        rows.append({"case": "precond", "grid": N, "dtype": dtype, **precond_label(m), "check_every": check_every,
                      "iteration_ms": round((tm - t0) / max(info["iterations"], 1), 5),
                      "iterations_1e-3": done["iterations"], "status_1e-3": done["status"],
                      "rel_residual": done["rel_residual"], "poisson_residual": fs.poisson_residual("u0", "v0"),
@@ -161,7 +181,7 @@ def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters):
 def step_case(N, dtype, steps, tols, max_iters, precond=0, check_every=0):
     out = []
     for tol in [None] + tols:
-        if tol is None and precond > 0:
+        if tol is None and precond != 0:
             continue  # (the Jacobi step has no preconditioner: timed once, with precond = 0)
         fs = context(N, dtype)
         if tol is not None:
@@ -184,7 +204,8 @@ def step_case(N, dtype, steps, tols, max_iters, precond=0, check_every=0):
             its = (fs.pressure_info()["iterations_total"] - i0) / (2.0 * steps)
         info = fs.pressure_info()
         out.append({"case": "step", "grid": N, "dtype": dtype, "solver": "jacobi" if tol is None else "cg", "tol": tol,
-                    "precond_sweeps": precond, "check_every": check_every,
+                    "precond_sweeps": precond if not isinstance(precond, tuple) else None,
+                    "mg": "%d:%d:%d" % precond if isinstance(precond, tuple) else None, "check_every": check_every,
                     "step_ms": round(best, 4), "iterations_per_projection": round(its, 2), "last_status": info["status"],
                     "last_rel_residual": info["rel_residual"], "poisson_residual": fs.poisson_residual("u0", "v0"),
                     "max_div": fs.diagnostics()["max_div"]})
@@ -219,11 +240,14 @@ def main():
     ap.add_argument("--sync", nargs="?", const=True, default=False,
                     help="alone: only the sync cases; with --precond: --sync M keeps the scalars on the device")
     ap.add_argument("--precond", default=None, help="comma-separated sweep counts, e.g. 0,2,4,8: only the precond cases")
+    ap.add_argument("--mg", default=None, help="comma-separated V-cycle settings NU[:LEVELS[:COARSE]] (SPEC §11.3), e.g. "
+                    "2,2:0:16,1,2:4: added to the precond cases (alone: --precond 0)")
     ap.add_argument("--check-every", nargs="+", default=["0", "1", "8", "max"])
     ap.add_argument("--sync-slabs", type=int, default=4)
     a = ap.parse_args()
-    if a.precond is not None:
-        sweeps = [int(m) for m in a.precond.split(",")]
+    if a.precond is not None or a.mg is not None:
+        sweeps = [int(m) for m in (a.precond or "0").split(",")]
+        sweeps += [parse_mg(x) for x in a.mg.split(",")] if a.mg else []
         every = 0 if a.sync in (False, True) else int(a.sync)
         for c in a.cases:
             n, t = c.split(":")
