@@ -1,8 +1,9 @@
-// sf_base.hpp — what the translation units of libsfgpu.so share: the error type and macros, the type-erased solver
+// sf_base.hpp — what the translation units of libsfgpu.so share: the error type and macros (those that need only the
+// HIP runtime API come from sf_hip.hpp; SF_NCCL and whatever else needs rccl.h is here), the type-erased solver
 // interface behind the C ABI (include/sfgpu.h) and the per-precision factories (sf_solver_f32.hip / sf_solver_f64.hip
 // instantiate sfi::Solver<float> / <double> separately, so the two halves of the library compile in parallel).
 #pragma once
-#include "../../include/sfgpu.h"
+#include "sf_hip.hpp"
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <algorithm>
@@ -21,32 +22,12 @@
 
 namespace sfi {
 
-
-struct Failure {
-    int code;
-    std::string msg;
-};
-
-#define SF_HIP(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            throw Failure{SF_ERR_HIP, std::string("Error ") + hipGetErrorString(_e) + " at line " + \
-                                          std::to_string(__LINE__) + " in file " + __FILE__ +      \
-                                          " (" #expr ")"};                                         \
-    } while (0)
-
 #define SF_NCCL(expr)                                                                              \
     do {                                                                                           \
         ncclResult_t _r = (expr);                                                                  \
         if (_r != ncclSuccess)                                                                     \
             throw Failure{SF_ERR_RCCL, std::string("RCCL error ") + ncclGetErrorString(_r) +       \
                                            " at line " + std::to_string(__LINE__) + " (" #expr ")"}; \
-    } while (0)
-
-#define SF_REQUIRE(cond, text)                                          \
-    do {                                                                \
-        if (!(cond)) throw Failure{SF_ERR_INVALID, std::string(text)};  \
     } while (0)
 
 inline int env_int(const char* name, int dflt) {

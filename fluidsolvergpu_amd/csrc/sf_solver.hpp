@@ -26,18 +26,18 @@ class Solver final : public SolverBase {
     // Internal slots: field[WORK_SLOT + f] aliases scratch[f] while an operator whose work field must be addressed by
     // slot is issued (exchange() and op_advect take slots). Invariant: one of these NSCRATCH slots is non-null only
     // while a ScratchAlias guard lives; guards do not nest; and nothing that swaps scratch pointers with slots (an
-    // op_lin_solve without a partner of its own) runs under a guard. ~Solver frees the named slots and the two owning
-    // slots below, so a stale alias could not be freed twice.
+    // op_lin_solve without a partner of its own) runs under a guard. Every slot is a view, alias or not: own_ holds
+    // what exists and frees it, the slots say where it is now, and nothing is ever freed through a slot.
     static constexpr int WORK_SLOT = SF_NUM_FIELDS;
     static constexpr int MAG_SLOT = WORK_SLOT;  // |curl u| of the forces (SPEC §8)
     static constexpr int HAT_SLOT = WORK_SLOT;  // + f: `hat`, the first-order result inside advect_mc (SPEC §9)
     static constexpr int CG_R = WORK_SLOT, CG_D = WORK_SLOT + 1, CG_Q = WORK_SLOT + 2;  // CG's r, d, q (SPEC §11)
     // z = M(r) of a preconditioned solve and the ping-pong partner of its sweeps (SPEC §11.2). No aliases: these two
-    // slots own their buffers, from the first preconditioned solve (pcg_alloc) to ~Solver.
+    // slots have buffers of their own from the first preconditioned solve on (pcg_alloc).
     static constexpr int CG_Z = WORK_SLOT + NSCRATCH, CG_ZP = CG_Z + 1;
     // The coarse levels l >= 1 of the multigrid preconditioner (SPEC §11.3): z, its partner and the level's right-hand
-    // side, three owning slots per level from the first multigrid solve (mg_alloc) to ~Solver. Level 0 is the z, the
-    // partner and the r of the solve itself.
+    // side, three slots with buffers of their own per level from the first multigrid solve on (op_vcycle). Level 0 is
+    // the z, the partner and the r of the solve itself.
     static constexpr int MG_MAXL = 12, MG_SLOT = CG_ZP + 1;
     static constexpr int mg_z(int l) { return MG_SLOT + 3 * (l - 1); }
     static constexpr int mg_zp(int l) { return mg_z(l) + 1; }
@@ -138,7 +138,7 @@ class Solver final : public SolverBase {
     };
 
 public:
-    explicit Solver(const sf_params& p) : N_(p.N), K_(p.iters), device_(p.device) {
+    explicit Solver(const sf_params& p) : N_(p.N), K_(p.iters), device_(p.device), own_(p.device) {
         SF_REQUIRE(p.N >= 1, "N must be >= 1");
         SF_REQUIRE(p.iters >= 0, "iters must be >= 0");
         L_ = p.nslabs_local > 0 ? p.nslabs_local : 1;
@@ -210,14 +210,14 @@ public:
             sl.geom.plane = plane_;
             sl.geom.wall_lo = (sl.gid == 0);
             sl.geom.wall_hi = (sl.gid == P_ - 1);
-            SF_HIP(hipStreamCreateWithFlags(&sl.cs, hipStreamNonBlocking));
-            SF_HIP(hipStreamCreateWithFlags(&sl.bs, hipStreamNonBlocking));
+            sl.cs = own_.stream(hipStreamNonBlocking);
+            sl.bs = own_.stream(hipStreamNonBlocking);
             // Events that only order kernels of THIS device against each other skip the system-scope fence of the
             // default event (a cache write-back + invalidate per record: ~12 us between consecutive sweeps of a
             // decomposed grid). halo_done keeps it when the ghost planes are written by another GPU through RCCL.
             const unsigned ev_local = hipEventDisableTiming | (unsigned)hipEventDisableSystemFence;
             const unsigned ev_halo = ((nranks_ > 1 && !loopback_) || rccl_self_) ? (unsigned)hipEventDisableTiming : ev_local;
-            SF_HIP(hipEventCreateWithFlags(&sl.cs_mark, ev_local));
+            sl.cs_mark = own_.event(ev_local);
             {
                 // One slab per process (production): every halo is an RCCL message, and the chain
                 // boundary launch -> message -> next boundary launch is what limits a pair once the messages take as
@@ -228,32 +228,30 @@ public:
                 // parity tests to run the shared-stream ordering against the oracle). (A high-priority halo stream
                 // was measured in round 1: with logical slabs on one GPU the copy kernel pre-empts the sweeps, 2x slower.)
                 const int hmode = sw_.halo_stream;  // 0 as described, 1 always separate, 2 always shared
-                if ((L_ == 1 && nranks_ > 1 && hmode == 0) || hmode == 2)
-                    sl.hs = sl.bs;
-                else
-                    SF_HIP(hipStreamCreateWithFlags(&sl.hs, hipStreamNonBlocking));
+                const bool shared = (L_ == 1 && nranks_ > 1 && hmode == 0) || hmode == 2;
+                sl.hs = shared ? sl.bs : own_.stream(hipStreamNonBlocking);
             }
-            SF_HIP(hipEventCreateWithFlags(&sl.boundary_done, ev_local));
-            SF_HIP(hipEventCreateWithFlags(&sl.halo_done, ev_halo));
+            sl.boundary_done = own_.event(ev_local);
+            sl.halo_done = own_.event(ev_halo);
             for (int f = 0; f < SF_USER0; ++f) sl.field[f] = alloc_field();
             for (int f = 0; f < NSCRATCH; ++f) sl.scratch[f] = alloc_field();
-            SF_HIP(hipMalloc(&sl.d_flag, sizeof(int)));
+            sl.d_flag = own_.dev<int>(sizeof(int));
             SF_HIP(hipMemset(sl.d_flag, 0, sizeof(int)));
             SF_HIP(hipDeviceSynchronize());
         }
-        SF_HIP(hipEventCreate(&t0_));
-        SF_HIP(hipEventCreate(&t1_));
+        t0_ = own_.event(hipEventDefault);  // the default flags: these two are timed
+        t1_ = own_.event(hipEventDefault);
         if (nranks_ > 1 && !loopback_) {
             ncclUniqueId id;
             static_assert(sizeof(ncclUniqueId) <= SF_NCCL_ID_BYTES, "ncclUniqueId larger than ABI slot");
             std::memcpy(&id, p.nccl_id, sizeof id);
-            SF_NCCL(ncclCommInitRank(&comm_, nranks_, id, rank_));
+            SF_NCCL(ncclCommInitRank(&comm_.h, nranks_, id, rank_));
         } else if (rccl_self_) {
             // a real communicator of one rank: the logical slabs' ghost planes travel as grouped ncclSend / ncclRecv
             // to self (see exchange()), so the RCCL data plane runs on a one-GPU box
             ncclUniqueId id;
             SF_NCCL(ncclGetUniqueId(&id));
-            SF_NCCL(ncclCommInitRank(&comm_, 1, id, 0));
+            SF_NCCL(ncclCommInitRank(&comm_.h, 1, id, 0));
         }
         ishell_skip_ = sw_.ishell != 0;
         dead_ishell_opt_ = sw_.ishell == 1;
@@ -294,7 +292,7 @@ public:
         // rank by itself.) d_sync[0]: barrier word, d_sync[1]: the time in microseconds.
         long long* d_sync = nullptr;
         if (comm_) {
-            SF_HIP(hipMalloc(&d_sync, 2 * sizeof(long long)));
+            d_sync = own_.dev<long long>(2 * sizeof(long long));
             SF_HIP(hipMemset(d_sync, 0, 2 * sizeof(long long)));
             SF_HIP(hipDeviceSynchronize());
         }
@@ -354,55 +352,26 @@ public:
             // unlike the trapezoid depth this changes the sequence of exchanges, so the ranks must agree: they now compare
             // the same (slowest-rank) times, and the vote below stays as the guard that they really did
             if (comm_) {
-                int* d_vote = nullptr;
                 int vote = split_fields_ == 0 ? 1 : 0, sum = 0;
-                SF_HIP(hipMalloc(&d_vote, sizeof(int)));
+                int* d_vote = own_.dev<int>(sizeof(int));
                 SF_HIP(hipMemcpy(d_vote, &vote, sizeof(int), hipMemcpyHostToDevice));
                 SF_NCCL(ncclAllReduce(d_vote, d_vote, 1, ncclInt, ncclSum, comm_, slabs_[0].cs));
                 SF_HIP(hipStreamSynchronize(slabs_[0].cs));
                 SF_HIP(hipMemcpy(&sum, d_vote, sizeof(int), hipMemcpyDeviceToHost));
-                SF_HIP(hipFree(d_vote));
+                own_.release(d_vote);
                 split_fields_ = (sum == nranks_) ? 0 : 1;
             }
             tuned_split_ = split_fields_;
         }
-        if (d_sync) SF_HIP(hipFree(d_sync));
+        own_.release(d_sync);
     }
 
+    // The graph executables and the trace file only: comm_ and own_ release the rest, in that order, as members.
     ~Solver() override {
         (void)hipSetDevice(device_);
         (void)hipDeviceSynchronize();
         for (GraphEntry& e : graph_cache_) (void)hipGraphExecDestroy(e.exec);
         if (trace_) std::fclose(trace_);
-        if (comm_) ncclCommDestroy(comm_);
-        for (Slab& sl : slabs_) {
-            for (int f = 0; f < SF_NUM_FIELDS; ++f) free_field(sl.field[f]);  // not the internal slots: aliases
-            for (int f : {CG_Z, CG_ZP}) free_field(sl.field[f]);               // ... but for these two
-            for (int f = MG_SLOT; f < MG_SLOT + 3 * (MG_MAXL - 1); ++f)        // ... and the coarse levels (no padding)
-                if (sl.field[f]) (void)hipFree(sl.field[f]);
-            for (T*& f : sl.scratch) free_field(f);
-            if (sl.d_flag) (void)hipFree(sl.d_flag);
-            if (sl.red_rows) (void)hipFree(sl.red_rows);
-            if (sl.red_planes) (void)hipFree(sl.red_planes);
-            for (T*& f : sl.snap) free_field(f);
-            if (sl.os) (void)hipStreamDestroy(sl.os);
-            if (sl.snap_done) (void)hipEventDestroy(sl.snap_done);
-            if (sl.cs) (void)hipStreamDestroy(sl.cs);
-            if (sl.bs) (void)hipStreamDestroy(sl.bs);
-            if (sl.cs_mark) (void)hipEventDestroy(sl.cs_mark);
-            if (sl.hs && sl.hs != sl.bs) (void)hipStreamDestroy(sl.hs);
-            if (sl.boundary_done) (void)hipEventDestroy(sl.boundary_done);
-            if (sl.halo_done) (void)hipEventDestroy(sl.halo_done);
-        }
-        if (t0_) (void)hipEventDestroy(t0_);
-        if (t1_) (void)hipEventDestroy(t1_);
-        if (red_host_) (void)hipHostFree(red_host_);
-        if (red_gather_) (void)hipFree(red_gather_);
-        if (cg_state_) (void)hipFree(cg_state_);
-        if (cg_state_host_) (void)hipHostFree(cg_state_host_);
-        tracers_free();
-        if (copy_src_) (void)hipFree(copy_src_);
-        if (copy_dst_) (void)hipFree(copy_dst_);
     }
 
     // ---- host <-> device ------------------------------------------------------------------
@@ -833,12 +802,11 @@ public:
         SF_HIP(hipSetDevice(device_));
         bytes = (bytes + 4095) / 4096 * 4096;
         if (copy_bytes_ != bytes) {
-            if (copy_src_) (void)hipFree(copy_src_);
-            if (copy_dst_) (void)hipFree(copy_dst_);
-            copy_src_ = copy_dst_ = nullptr;
+            own_.release(copy_src_);
+            own_.release(copy_dst_);
             copy_bytes_ = 0;
-            SF_HIP(hipMalloc(&copy_src_, bytes));
-            SF_HIP(hipMalloc(&copy_dst_, bytes));
+            copy_src_ = own_.dev<void>(bytes);
+            copy_dst_ = own_.dev<void>(bytes);
             SF_HIP(hipMemset(copy_src_, 1, bytes));
             SF_HIP(hipMemset(copy_dst_, 0, bytes));
             SF_HIP(hipDeviceSynchronize());
@@ -869,8 +837,8 @@ public:
         SF_HIP(hipSetDevice(device_));
         for (int q = 0; q < nfields; ++q) check_field(fields[q]);
         for (Slab& sl : slabs_) {
-            if (!sl.os) SF_HIP(hipStreamCreateWithFlags(&sl.os, hipStreamNonBlocking));
-            if (!sl.snap_done) SF_HIP(hipEventCreateWithFlags(&sl.snap_done, hipEventDisableTiming));
+            if (!sl.os) sl.os = own_.stream(hipStreamNonBlocking);
+            if (!sl.snap_done) sl.snap_done = own_.event(hipEventDisableTiming);
             for (int q = 0; q < nfields; ++q) {
                 if (!sl.snap[q]) sl.snap[q] = alloc_field();
                 SF_HIP(hipMemcpyAsync(sl.snap[q], ensure(sl, fields[q]), (size_t)field_elems_ * sizeof(T),
@@ -917,9 +885,9 @@ public:
         tracers_free();
         tr_n_ = n;
         if (n == 0) return;
-        SF_HIP(hipMalloc(&tr_pos_, (size_t)3 * n * sizeof(T)));
-        SF_HIP(hipMalloc(&tr_dens_, (size_t)n * sizeof(T)));
-        SF_HIP(hipMalloc(&tr_speed_, (size_t)n * sizeof(T)));
+        tr_pos_ = own_.dev<T>((size_t)3 * n * sizeof(T));
+        tr_dens_ = own_.dev<T>((size_t)n * sizeof(T));
+        tr_speed_ = own_.dev<T>((size_t)n * sizeof(T));
         if (P_ == 1) {
             SF_HIP(hipMemcpyAsync(tr_pos_, xyz, (size_t)3 * n * sizeof(T), hipMemcpyHostToDevice, slabs_[0].cs));
             SF_HIP(hipStreamSynchronize(slabs_[0].cs));
@@ -933,12 +901,12 @@ public:
             const int s = tracer_owner(p[3 * t + 2]) - rank_ * L_;
             if (s >= 0 && s < L_) own[s].push_back(sfk::TracerRec<T>{p[3 * t], p[3 * t + 1], p[3 * t + 2], t});
         }
-        SF_HIP(hipMalloc(&tr_ids_, (size_t)n * sizeof(int)));
+        tr_ids_ = own_.dev<int>((size_t)n * sizeof(int));
         for (int s = 0; s < L_; ++s) {
             Slab& sl = slabs_[s];
-            for (auto*& l : sl.tr_list) SF_HIP(hipMalloc(&l, (size_t)n * sizeof(sfk::TracerRec<T>)));
-            SF_HIP(hipMalloc(&sl.tr_cnt, 2 * sizeof(int)));
-            SF_HIP(hipMalloc(&sl.tr_flag, sizeof(int)));
+            for (auto*& l : sl.tr_list) l = own_.dev<sfk::TracerRec<T>>((size_t)n * sizeof(sfk::TracerRec<T>));
+            sl.tr_cnt = own_.dev<int>(2 * sizeof(int));
+            sl.tr_flag = own_.dev<int>(sizeof(int));
             const int cnt[2] = {(int)own[s].size(), 0}, zero = 0;
             if (!own[s].empty())
                 SF_HIP(hipMemcpy(sl.tr_list[0], own[s].data(), own[s].size() * sizeof(sfk::TracerRec<T>),
@@ -1323,25 +1291,20 @@ private:
     unsigned tracer_grid(int n) const {
         return (unsigned)std::max(1L, std::min(ceil_div((long)n, 256L), (long)num_cu_ * 8));
     }
-    template <class P>
-    static void release(P*& p) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
     void tracers_free() {
         (void)hipDeviceSynchronize();  // earlier launches may still use the buffers
-        release(tr_pos_);
-        release(tr_dens_);
-        release(tr_speed_);
-        release(tr_ids_);
+        own_.release(tr_pos_);
+        own_.release(tr_dens_);
+        own_.release(tr_speed_);
+        own_.release(tr_ids_);
         for (Slab& sl : slabs_) {
             for (int q = 0; q < 2; ++q) {
-                release(sl.tr_list[q]);
-                release(sl.tr_send[q]);
-                release(sl.tr_recv[q]);
+                own_.release(sl.tr_list[q]);
+                own_.release(sl.tr_send[q]);
+                own_.release(sl.tr_recv[q]);
             }
-            release(sl.tr_cnt);
-            release(sl.tr_flag);
+            own_.release(sl.tr_cnt);
+            own_.release(sl.tr_flag);
         }
         tr_n_ = 0;
     }
@@ -1353,14 +1316,14 @@ private:
         for (int s = 0; s < L_; ++s) {
             Slab& sl = slabs_[s];
             for (int d = 0; d < 2; ++d) {
-                release(sl.tr_send[d]);
-                release(sl.tr_recv[d]);
+                own_.release(sl.tr_send[d]);
+                own_.release(sl.tr_recv[d]);
                 const int side = tr_side(s, d);
                 if (side == TR_NONE) continue;
-                SF_HIP(hipMalloc(&sl.tr_send[d], bytes));
+                sl.tr_send[d] = own_.dev<sfk::TracerRec<T>>(bytes);
                 SF_HIP(hipMemset(sl.tr_send[d], 0, bytes));
                 if (side == TR_MSG) {
-                    SF_HIP(hipMalloc(&sl.tr_recv[d], bytes));
+                    sl.tr_recv[d] = own_.dev<sfk::TracerRec<T>>(bytes);
                     SF_HIP(hipMemset(sl.tr_recv[d], 0, bytes));
                 }
             }
@@ -1484,17 +1447,13 @@ private:
 
     T* alloc_field(const Level* lv = nullptr) {
         const Level& h = lv ? *lv : lv0_;
-        T* p = nullptr;
         const size_t total = (size_t)(h.pad_front + h.elems + h.pad_back) * sizeof(T);
-        SF_HIP(hipMalloc(&p, total));
+        T* p = own_.dev<T>(total);
         SF_HIP(hipMemset(p, 0, total));
         // hipMemset on device memory may return before the fill has run, and the context's streams are
         // non-blocking (they do not order against the null stream): wait here.
         SF_HIP(hipDeviceSynchronize());
         return p + h.pad_front;
-    }
-    void free_field(T* f) const {
-        if (f) (void)hipFree(f - pad_front_);
     }
     T* ensure(Slab& sl, int f) {
         if (!sl.field[f]) {
@@ -1686,14 +1645,13 @@ private:
     }
     void records_alloc() {
         SF_REQUIRE(rows_pad() <= 2048, "reductions take N <= 2048");
-        if (red_host_) return;
         const size_t nv = sfk::DIAG_NV;
         for (Slab& sl : slabs_) {
-            SF_HIP(hipMalloc(&sl.red_rows, nv * nzl_ * (size_t)rows_pad() * sizeof(double)));
-            SF_HIP(hipMalloc(&sl.red_planes, nv * nzl_ * sizeof(double)));
+            if (!sl.red_rows) sl.red_rows = own_.dev<double>(nv * nzl_ * (size_t)rows_pad() * sizeof(double));
+            if (!sl.red_planes) sl.red_planes = own_.dev<double>(nv * nzl_ * sizeof(double));
         }
-        if (comm_) SF_HIP(hipMalloc(&red_gather_, nv * N_ * sizeof(double)));
-        SF_HIP(hipHostMalloc(&red_host_, nv * N_ * sizeof(double), hipHostMallocDefault));
+        if (comm_ && !red_gather_) red_gather_ = own_.dev<double>(nv * N_ * sizeof(double));
+        if (!red_host_) red_host_ = own_.pinned<double>(nv * N_ * sizeof(double));
     }
     unsigned row_blocks(const Level& h) const { return (unsigned)ceil_div((long)h.N * h.nzl, 4L); }
     // a slab's geometry on a level: its share of the level's planes, the wall flags of the slab
@@ -2810,12 +2768,13 @@ private:
         return r[0];
     }
     void cg_state_alloc() {
-        if (cg_state_) return;
         // the plane records of all N planes in one buffer (the all-gather's, where there is a communicator)
-        if (!red_gather_) SF_HIP(hipMalloc(&red_gather_, (size_t)sfk::DIAG_NV * N_ * sizeof(double)));
-        SF_HIP(hipMalloc(&cg_state_, sizeof(sfk::CgState<T>)));
-        SF_HIP(hipMemset(cg_state_, 0, sizeof(sfk::CgState<T>)));
-        SF_HIP(hipHostMalloc(&cg_state_host_, sizeof(sfk::CgState<T>), hipHostMallocDefault));
+        if (!red_gather_) red_gather_ = own_.dev<double>((size_t)sfk::DIAG_NV * N_ * sizeof(double));
+        if (!cg_state_) {
+            cg_state_ = own_.dev<sfk::CgState<T>>(sizeof(sfk::CgState<T>));
+            SF_HIP(hipMemset(cg_state_, 0, sizeof(sfk::CgState<T>)));
+        }
+        if (!cg_state_host_) cg_state_host_ = own_.pinned<sfk::CgState<T>>(sizeof(sfk::CgState<T>));
     }
     // a slab's plane records inside red_gather_ (one value per plane)
     double* cg_records(const Slab& sl) const { return red_gather_ + (size_t)sl.gid * nzl_; }
@@ -3261,7 +3220,21 @@ private:
         exchange<3>(dst);
     }
 
+    // Communicator guard: destroyed before own_ (declared after it), so before the streams its calls were issued on.
+    struct Comm {
+        ncclComm_t h = nullptr;
+        Comm() = default;
+        Comm(const Comm&) = delete;
+        Comm& operator=(const Comm&) = delete;
+        ~Comm() {
+            if (h) ncclCommDestroy(h);
+        }
+        operator ncclComm_t() const { return h; }
+    };
+
     int N_, K_, device_;
+    Owned own_;  // every device and pinned block, stream and event of this context; before all that refer to them
+    Comm comm_;
     int L_ = 1, nranks_ = 1, rank_ = 0, P_ = 1, G_ = 1;
     const Switches sw_{};
     int fuse_maxvec_ = 512;  // widest row (vectors) the fused kernels take
@@ -3292,7 +3265,6 @@ private:
     bool inject_trap_bug_ = false;
     std::map<const void*, int> buf_ids_;
     long xchg_seq_ = 0;
-    ncclComm_t comm_ = nullptr;
     bool loopback_ = false, rccl_self_ = false;
     long rccl_groups_ = 0;  // RCCL send/recv groups issued so far (sf_schedule_info: proof the transport ran)
     hipEvent_t t0_ = nullptr, t1_ = nullptr;
