@@ -259,6 +259,15 @@ int sf_pressure_multigrid_get(const sf_ctx* ctx, sf_pressure_multigrid* out) {
 int sf_precondition(sf_ctx* ctx, int z, int r) {
     return guarded(ctx, [&](SolverBase& s) { s.precondition(z, r); });
 }
+int sf_render(sf_ctx* ctx, const sf_render_params* p) {
+    return guarded(ctx, [&](SolverBase& s) { s.render(p); });
+}
+int sf_render_read(sf_ctx* ctx, void* colour, void* transmittance) {
+    return guarded(ctx, [&](SolverBase& s) { s.render_read(colour, transmittance); });
+}
+int sf_light(sf_ctx* ctx, int dst, int dens, int axis, int from_high, double sigma) {
+    return guarded(ctx, [&](SolverBase& s) { s.light(dst, dens, axis, from_high, sigma); });
+}
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });
 }

@@ -26,7 +26,8 @@
 //             [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
-//             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]]
+//             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
+//             [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -48,6 +49,14 @@
 // --pressure-mg NU[:LEVELS[:COARSE]] (with --pressure cg): the multigrid V-cycle preconditioner of docs/SPEC.md §11.3 with
 // NU >= 1 sweeps per level, at most LEVELS levels (0, the default: as many as the grid allows) and COARSE >= 1 sweeps on
 // the coarsest (default 8). In force it takes the place of --pressure-precond.
+// --render VIEW:SIGMA[:LIGHT]: at every output step an image of the density (docs/SPEC.md §12) next to the frame,
+// "render_<frame, 4 digits>.pgm" (several processes: "render_GPU<rank>_<frame>.pgm", each rank the pixel rows it holds).
+// VIEW and LIGHT are one of i+ i- j+ j- k+ k-: the axis of the rays and the side they enter from (+: at index 1). SIGMA
+// >= 0 is the extinction per unit length. With LIGHT the smoke is lit from that side first: sf_light writes the
+// transmittance towards the light into a slot that is free at an output step — an SF_USER slot that is not a bound
+// source, else SF_DENS0, which is scratch between steps while a density source is bound — and the view takes it as its
+// emission. The file is binary PGM (P5), maxval 65535, big-endian, q = (int)(min(max(C, 0), 1) * 65535 + 0.5) with
+// NaN -> 0, the row with the highest b first.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -88,6 +97,8 @@ struct Options {
     int cg_precond = SF_PRECOND_NONE, cg_precond_sweeps = 0;
     int mg_sweeps = 0, mg_levels = 0, mg_coarse = 8;
     double cg_tol = 1e-3;
+    int render_axis = -1, render_high = 0, light_axis = -1, light_high = 0;  // --render (axis -1: off / no light)
+    double render_sigma = 0.0;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
     int rank = 0, world = 1, local_rank = 0;
@@ -152,6 +163,25 @@ static void share_nccl_id(const Options& o, unsigned char* id) {
         fprintf(stderr, "Error: rank %d timed out waiting for %s\n", o.rank, path.c_str());
         exit(1);
     }
+}
+
+static void usage(FILE* to) {
+    fprintf(to,
+            "usage: sf_driver [--n 64] [--steps 20] [--iters 20] [--dtype f32|f64] [--every 10] [--out DIR]\n"
+            "                 [--binary] [--device 0] [--slabs 1] [--plumbing] [--quiet] [--sync-output] [--tracers 0]\n"
+            "                 [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1]\n"
+            "                 [--maccormack vel|dens|both] [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]]\n"
+            "                 [--pressure-sync M] [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]]\n"
+            "                 [--render VIEW:SIGMA[:LIGHT]]   VIEW, LIGHT: i+ i- j+ j- k+ k- (+ enters at the low index)\n"
+            "                 [--loopback --rank R --world W] [--help]\n");
+}
+
+// "i+" .. "k-" -> axis 0..2 and from_high (+ enters at the low index)
+static bool parse_view(const std::string& v, int& axis, int& high) {
+    if (v.size() != 2 || (v[0] != 'i' && v[0] != 'j' && v[0] != 'k') || (v[1] != '+' && v[1] != '-')) return false;
+    axis = v[0] - 'i';
+    high = v[1] == '-' ? 1 : 0;
+    return true;
 }
 
 static Options parse(int argc, char** argv) {
@@ -254,6 +284,29 @@ static Options parse(int argc, char** argv) {
             o.mg_levels = (int)val[1];
             o.mg_coarse = (int)val[2];
         }
+        else if (s == "--render") {
+            // VIEW:SIGMA[:LIGHT]
+            const std::string spec = next();
+            const size_t c1 = spec.find(':'), c2 = c1 == std::string::npos ? c1 : spec.find(':', c1 + 1);
+            bool ok = c1 != std::string::npos && parse_view(spec.substr(0, c1), o.render_axis, o.render_high);
+            if (ok) {
+                const std::string ss = spec.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+                char* end = nullptr;
+                o.render_sigma = strtod(ss.c_str(), &end);
+                ok = !ss.empty() && *end == 0 && std::isfinite(o.render_sigma) && o.render_sigma >= 0.0;
+            }
+            o.light_axis = -1;
+            if (ok && c2 != std::string::npos) ok = parse_view(spec.substr(c2 + 1), o.light_axis, o.light_high);
+            if (!ok) {
+                fprintf(stderr, "--render takes VIEW:SIGMA[:LIGHT] (VIEW, LIGHT one of i+ i- j+ j- k+ k-, SIGMA >= 0), not %s\n",
+                        spec.c_str());
+                exit(2);
+            }
+        }
+        else if (s == "--help") {
+            usage(stdout);
+            exit(0);
+        }
         else if (s == "--maccormack") {
             const std::string which = next();
             if (which != "vel" && which != "dens" && which != "both") {
@@ -295,6 +348,7 @@ static Options parse(int argc, char** argv) {
         else if (s == "--world") { o.world = atoi(next()); rank_or_world_given = true; }
         else {
             fprintf(stderr, "unknown option %s\n", s.c_str());
+            usage(stderr);
             exit(2);
         }
     }
@@ -383,6 +437,36 @@ static void write_frame(const Options& o, int frame, int kb, int ke, const std::
     }
 }
 
+// The image of one output step (docs/SPEC.md §12): the pixel rows [row_b, row_e) of colour this rank holds as binary PGM,
+// 16 bits big-endian, the highest row first.
+template <class T>
+static void write_render(const Options& o, int frame, const std::vector<T>& colour, int row_b, int row_e) {
+    char name[64];
+    if (o.world == 1)
+        snprintf(name, sizeof name, "/render_%04d.pgm", frame);
+    else
+        snprintf(name, sizeof name, "/render_GPU%d_%04d.pgm", o.rank, frame);
+    const std::string path = o.out + name;
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) {
+        fprintf(stderr, "Error: cannot write %s\n", path.c_str());
+        exit(1);
+    }
+    fprintf(f, "P5\n%d %d\n65535\n", o.n, row_e - row_b);
+    std::vector<unsigned char> row(2 * (size_t)o.n);
+    for (int b = row_e - 1; b >= row_b; --b) {
+        for (int a = 0; a < o.n; ++a) {
+            const double c = (double)colour[(size_t)a + (size_t)o.n * b];
+            const double cl = c > 0.0 ? (c < 1.0 ? c : 1.0) : 0.0;  // NaN -> 0
+            const int q = (int)(cl * 65535.0 + 0.5);
+            row[2 * a] = (unsigned char)(q >> 8);
+            row[2 * a + 1] = (unsigned char)(q & 255);
+        }
+        fwrite(row.data(), 1, row.size(), f);
+    }
+    fclose(f);
+}
+
 template <class T>
 static int run(const Options& o) {
     const double dt = 0.1, diff = 1e-4, visc = 1e-4;
@@ -431,7 +515,26 @@ static int run(const Options& o) {
     for (int f : {SF_U, SF_V, SF_W}) SF_CHECK_RETURN(sf_set_bnd(g_ctx, f + 1, f));
     SF_CHECK_RETURN(sf_set_bnd(g_ctx, 0, SF_DENS));
     // sources stay resident in HBM (SF_USER0..3) and are re-injected every step
-    SF_CHECK_RETURN(sf_bind_sources(g_ctx, SF_USER0, SF_USER1, SF_USER2, SF_USER3));
+    const int bound[4] = {SF_USER0, SF_USER1, SF_USER2, SF_USER3};
+    SF_CHECK_RETURN(sf_bind_sources(g_ctx, bound[0], bound[1], bound[2], bound[3]));
+    // --render with a light: the slot the transmittance towards the light is written to at an output step
+    int light_slot = -1;
+    if (o.render_axis >= 0 && o.light_axis >= 0) {
+        for (int f = SF_USER0; f <= SF_USER3 && light_slot < 0; ++f)
+            if (std::find(bound, bound + 4, f) == bound + 4) light_slot = f;
+        if (light_slot < 0 && bound[3] >= 0) light_slot = SF_DENS0;  // scratch between steps: its source is bound
+        if (light_slot < 0) {
+            fprintf(stderr, "--render: no free slot for the light (every SF_USER slot is a bound source)\n");
+            exit(2);
+        }
+    }
+    // the pixel rows of the image this rank holds: those of its planes (i / j views), all on the rank a k view leaves from
+    int img_b = own_kb - 1, img_e = own_ke - 1;
+    if (o.render_axis == 2) {
+        const bool mine = o.loopback || o.rank == (o.render_high ? 0 : o.world - 1);
+        img_b = 0, img_e = mine ? o.n : 0;
+    }
+    std::vector<T> colour(o.render_axis >= 0 ? (size_t)o.n * o.n : 0);
     // forces (SPEC §8): added by every vel_step to copies of the bound sources
     SF_CHECK_RETURN(sf_set_vorticity_confinement(g_ctx, o.vorticity));
     SF_CHECK_RETURN(sf_set_buoyancy(g_ctx, o.buoyancy, o.ambient, o.buoyancy_axis));
@@ -540,6 +643,14 @@ static int run(const Options& o) {
         if (o.every > 0 && t % o.every == 0) {
             const int frame = t / o.every;
             if (writer.joinable()) writer.join();  // the previous frame must be out before its buffers are reused
+            if (o.render_axis >= 0) {
+                if (light_slot >= 0)
+                    SF_CHECK_RETURN(sf_light(g_ctx, light_slot, SF_DENS, o.light_axis, o.light_high, o.render_sigma));
+                const sf_render_params rp = {o.render_axis, o.render_high, o.render_sigma, SF_DENS, light_slot};
+                SF_CHECK_RETURN(sf_render(g_ctx, &rp));
+                SF_CHECK_RETURN(sf_render_read(g_ctx, colour.data(), nullptr));
+                if (img_e > img_b) write_render<T>(o, frame, colour, img_b, img_e);
+            }
             if (ntr > 0) fetch_tracers();
             if (o.sync_output) {
                 SF_CHECK_RETURN(sf_sync(g_ctx));

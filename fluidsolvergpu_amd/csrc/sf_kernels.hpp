@@ -3438,4 +3438,151 @@ __global__ void __launch_bounds__(256) cg_scalars_kernel(const double* __restric
     cg_stage<T, STAGE>(st, s, c);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Volume rendering and light marching (docs/SPEC.md §12). One lane owns one ray and applies the recurrence cell by
+// cell in the order the SPEC fixes, so nothing depends on the launch geometry. A march has N^2 / 64 waves where a row
+// kernel has N^2, so the bytes in flight come from the unroll: every trip issues RAY_U independent loads per field
+// and lane before the first cell is applied.
+//   ray_march_kernel  rays along k (a lane owns a pixel (i, j) and walks the slab's planes) and along j (a lane owns
+//                     (i, k) and walks the rows of its plane): the same strided march, coalesced along i.
+//   ray_row_kernel    rays along i: a wave takes 64 rows and every lane walks its own row in 16-byte vectors; the
+//                     eight vectors of a 128-byte line are loaded in one trip, so a line is fetched once.
+// MODE: the image forms (final C and Tr of every ray; with and without an emission field) and the field form of
+// `light` (the exclusive transmittance of every cell). from_high maps the visit order onto the cells; the recurrence
+// is ray_step alone. Lanes past the row end march the last ray again (loads stay unconditional) and store nothing.
+enum { RAY_IMAGE = 0, RAY_IMAGE_EMIT = 1, RAY_FIELD = 2 };
+constexpr int RAY_U = 16;   // cells per trip of the strided march
+constexpr int RAY_UV = 8;   // vectors per trip of the row march: one 128-byte line per lane
+
+template <class T>
+struct RayArgs {
+    const T* dens;
+    const T* emit;  // RAY_IMAGE_EMIT only
+    T* dst;         // RAY_FIELD only
+    const T* in;    // the (C, Tr) image pair the slab the rays come from left (k-march); null: the rays start here
+    T* img;         // C at [0, N^2), Tr at [N^2, 2 N^2): pixel (a, b) at (a - 1) + N (b - 1)
+    T s;            // T(sigma) * h
+    int from_high;
+};
+
+// opacity of a cell: the select form of SPEC §12 (NaN and negative densities are transparent, t >= 1 opaque)
+template <class T>
+__device__ __forceinline__ T ray_opacity(T s, T d) {
+    const T t = s * d;
+    return (t > T(0)) ? ((t < T(1)) ? t : T(1)) : T(0);
+}
+// the recurrence, stated once: C from the old Tr, then Tr
+template <class T, int MODE>
+__device__ __forceinline__ void ray_step(T a, T e, T& C, T& Tr) {
+    if constexpr (MODE == RAY_IMAGE_EMIT) C = C + (Tr * a) * e;
+    if constexpr (MODE == RAY_IMAGE) C = C + Tr * a;
+    Tr = Tr * (T(1) - a);
+}
+
+template <class T, int AXIS, int MODE>
+__global__ void __launch_bounds__(64) ray_march_kernel(Geom g, RayArgs<T> A) {
+    static_assert(AXIS == 1 || AXIS == 2, "rays along j or k");
+    const int wpr = (g.N + 63) >> 6;
+    const int row = (int)blockIdx.x / wpr;  // k-march: j - 1; j-march: the local interior plane
+    const int i = 1 + 64 * ((int)blockIdx.x - row * wpr) + (int)threadIdx.x;
+    const bool live = i <= g.N;
+    const int ic = live ? i : g.N;
+    const int n = AXIS == 2 ? g.nzl : g.N;  // cells of the ray inside this slab
+    const long stride = AXIS == 2 ? g.plane : (long)g.px;
+    const long first = (AXIS == 2 ? row0(g, row + 1, g.G) : row0(g, 1, g.G + row)) + ic;
+    const long step = A.from_high ? -stride : stride;
+    long q = A.from_high ? first + (long)(n - 1) * stride : first;
+    const long NN = (long)g.N * g.N;
+    const long pix = (ic - 1) + (long)g.N * (AXIS == 2 ? row : g.kg0 + g.G + row - 1);
+    T C = T(0), Tr = T(1);
+    if (AXIS == 2 && A.in != nullptr) {
+        if (MODE != RAY_FIELD) C = A.in[pix];
+        Tr = A.in[NN + pix];
+    }
+    int t = 0;
+    for (; t + RAY_U <= n; t += RAY_U) {
+        T d[RAY_U], e[RAY_U];
+#pragma unroll
+        for (int u = 0; u < RAY_U; ++u) {
+            d[u] = A.dens[q + u * step];
+            e[u] = MODE == RAY_IMAGE_EMIT ? A.emit[q + u * step] : T(0);
+        }
+#pragma unroll
+        for (int u = 0; u < RAY_U; ++u) {
+            if (MODE == RAY_FIELD && live) A.dst[q + u * step] = Tr;
+            ray_step<T, MODE>(ray_opacity(A.s, d[u]), e[u], C, Tr);
+        }
+        q += RAY_U * step;
+    }
+    for (; t < n; ++t) {
+        const T d = A.dens[q];
+        const T e = MODE == RAY_IMAGE_EMIT ? A.emit[q] : T(0);
+        if (MODE == RAY_FIELD && live) A.dst[q] = Tr;
+        ray_step<T, MODE>(ray_opacity(A.s, d), e, C, Tr);
+        q += step;
+    }
+    if (live) {
+        if (MODE != RAY_FIELD) A.img[pix] = C;
+        A.img[NN + pix] = Tr;
+    }
+}
+
+// NV vectors of a row, the m-th visited one first: all loads, then the cells in visit order
+template <class T, int MODE, bool HIGH, int NV>
+__device__ __forceinline__ void ray_row_vectors(const RayArgs<T>& A, long r, int nfull, int m, bool live, T& C, T& Tr) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    V d[NV], e[NV];
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const long off = r + (long)W * (HIGH ? nfull - 1 - (m + u) : m + u);
+        d[u] = ldv(A.dens + off);
+        if (MODE == RAY_IMAGE_EMIT) e[u] = ldv(A.emit + off);
+    }
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        V o;
+#pragma unroll
+        for (int x = 0; x < W; ++x) {
+            const int el = HIGH ? W - 1 - x : x;
+            o[el] = Tr;
+            ray_step<T, MODE>(ray_opacity(A.s, d[u][el]), MODE == RAY_IMAGE_EMIT ? e[u][el] : T(0), C, Tr);
+        }
+        if (MODE == RAY_FIELD && live) stv(A.dst + r + (long)W * (HIGH ? nfull - 1 - (m + u) : m + u), o);
+    }
+}
+
+template <class T, int MODE, bool HIGH>
+__global__ void __launch_bounds__(64) ray_row_kernel(Geom g, RayArgs<T> A) {
+    constexpr int W = VecT<T>::W;
+    const int wpp = (g.N + 63) >> 6;
+    const int p = (int)blockIdx.x / wpp;  // local interior plane
+    const int j = 1 + 64 * ((int)blockIdx.x - p * wpp) + (int)threadIdx.x;
+    const bool live = j <= g.N;
+    const int jc = live ? j : g.N;
+    const long r = row0(g, jc, g.G + p) + 1;  // cell i = 1 of the row: the start of a 128-byte line
+    const int nfull = g.N / W;                // whole vectors of interior cells; the cells behind them go one by one
+    T C = T(0), Tr = T(1);
+    auto tail = [&] {
+        for (int t = nfull * W; t < g.N; ++t) {
+            const long q = r + (HIGH ? nfull * W + (g.N - 1 - t) : t);
+            const T d = A.dens[q];
+            const T e = MODE == RAY_IMAGE_EMIT ? A.emit[q] : T(0);
+            if (MODE == RAY_FIELD && live) A.dst[q] = Tr;
+            ray_step<T, MODE>(ray_opacity(A.s, d), e, C, Tr);
+        }
+    };
+    if (HIGH) tail();
+    int m = 0;
+    for (; m + RAY_UV <= nfull; m += RAY_UV) ray_row_vectors<T, MODE, HIGH, RAY_UV>(A, r, nfull, m, live, C, Tr);
+    for (; m < nfull; ++m) ray_row_vectors<T, MODE, HIGH, 1>(A, r, nfull, m, live, C, Tr);
+    if (!HIGH) tail();
+    if (live) {
+        const long NN = (long)g.N * g.N;
+        const long pix = (j - 1) + (long)g.N * (g.kg0 + g.G + p - 1);
+        if (MODE != RAY_FIELD) A.img[pix] = C;
+        A.img[NN + pix] = Tr;
+    }
+}
+
 }  // namespace sfk

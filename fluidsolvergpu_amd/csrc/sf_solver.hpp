@@ -77,6 +77,10 @@ class Solver final : public SolverBase {
         // [value][plane][rows_pad()] and plane records [plane][value]
         double* red_rows = nullptr;
         double* red_planes = nullptr;
+        // rays (SPEC §12), allocated by the first sf_render [0] / sf_light [1]: the slab's (C, Tr) image pair, 2 N^2
+        // values, and, where the pair of the slab a k-ray comes from arrives as a message, the buffer it arrives in
+        T* ray_img[2] = {};
+        T* ray_in[2] = {};
     };
 
     // The first n internal slots of every slab alias its scratch buffers while this lives (invariant at WORK_SLOT). The
@@ -1232,6 +1236,58 @@ public:
         join();
         op_precondition(pm, z, r);
     }
+    // ---- volume rendering and light marching (SPEC §12) ----------------------------------------------------------
+    static void check_rays(int axis, int from_high, double sigma) {
+        SF_REQUIRE(axis >= 0 && axis <= 2, "ray axis must be 0 (i), 1 (j) or 2 (k)");
+        SF_REQUIRE(from_high == 0 || from_high == 1, "from_high must be 0 or 1");
+        SF_REQUIRE(std::isfinite(sigma) && sigma >= 0.0, "sigma must be finite and >= 0");
+    }
+    void render(const sf_render_params* p) override {
+        SF_REQUIRE(p != nullptr, "null render params");
+        check_rays(p->axis, p->from_high, p->sigma);
+        check_field(p->dens);
+        SF_REQUIRE(p->emit >= -1 && p->emit < SF_NUM_FIELDS, "emit must be a field id, or -1 for none");
+        SF_HIP(hipSetDevice(device_));
+        op_rays(p->emit >= 0 ? sfk::RAY_IMAGE_EMIT : sfk::RAY_IMAGE, p->axis, p->from_high, p->sigma, p->dens, p->emit, -1);
+        ray_axis_ = p->axis;
+        ray_high_ = p->from_high;
+    }
+    // Each slab's pixels go to pinned memory on its compute stream, so the copy waits for the render alone; then to the
+    // caller's arrays at their place in the image.
+    void render_read(void* colour, void* transmittance) override {
+        SF_REQUIRE(ray_axis_ >= 0, "render_read before any render");
+        SF_HIP(hipSetDevice(device_));
+        const size_t NN = (size_t)N_ * N_;
+        if (!ray_stage_) ray_stage_ = own_.pinned<T>(2 * NN * sizeof(T));
+        std::vector<std::pair<size_t, size_t>> parts;  // pixels [first, second) held by this context
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            size_t b = (size_t)sl.gid * nzl_ * N_, e = b + (size_t)nzl_ * N_;  // i / j views: the rows of the owned planes
+            if (ray_axis_ == 2) {
+                if (!ray_leaves_here(s, ray_high_)) continue;
+                b = 0, e = NN;  // k view: the whole image, on the slab the rays leave the grid from
+            }
+            for (size_t half : {(size_t)0, NN})
+                SF_HIP(hipMemcpyAsync(ray_stage_ + half + b, sl.ray_img[0] + half + b, (e - b) * sizeof(T),
+                                      hipMemcpyDeviceToHost, sl.cs));
+            tr_op("render_out", sl, sl.cs, {{sl.ray_img[0], false, 0, nplanes_}});
+            parts.push_back({b, e});
+        }
+        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        for (const auto& pr : parts) {
+            const size_t bytes = (pr.second - pr.first) * sizeof(T);
+            if (colour) std::memcpy(static_cast<T*>(colour) + pr.first, ray_stage_ + pr.first, bytes);
+            if (transmittance) std::memcpy(static_cast<T*>(transmittance) + pr.first, ray_stage_ + NN + pr.first, bytes);
+        }
+    }
+    void light(int dst, int dens, int axis, int from_high, double sigma) override {
+        check_rays(axis, from_high, sigma);
+        check_distinct("light: dst and dens must be different fields", {dst, dens});
+        SF_HIP(hipSetDevice(device_));
+        op_rays(sfk::RAY_FIELD, axis, from_high, sigma, dens, -1, dst);
+        op_set_bnd(0, dst, "light_set_bnd");
+    }
+
     void pressure_sync(sf_pressure_sync* out) const override {
         out->check_every = check_every_;
         out->host_waits = host_waits_;
@@ -3220,6 +3276,121 @@ private:
         exchange<3>(dst);
     }
 
+    // ---- volume rendering and light marching (SPEC §12) ----------------------------------------------------------
+    // How the image pair of the slab below (d = 0) / above (d = 1) of local slab s reaches it when a k-ray crosses that
+    // boundary: the routes of the tracer records (tr_side), except that a loopback context has nobody to receive from
+    // and starts its rays afresh.
+    int ray_side(int s, int d) const {
+        const int side = tr_side(s, d);
+        return (side == TR_MSG && loopback_) ? (int)TR_NONE : side;
+    }
+    // the k-rays of direction `high` end in local slab s (the last slab of the grid, or of a loopback context)
+    bool ray_leaves_here(int s, int high) const { return ray_side(s, high ? 0 : 1) == TR_NONE; }
+
+    template <int MODE>
+    void launch_rays(Slab& sl, int axis, int high, const sfk::RayArgs<T>& A) {
+        const unsigned wpr = (unsigned)ceil_div(N_, 64);
+        if (axis == 2)
+            hipLaunchKernelGGL((sfk::ray_march_kernel<T, 2, MODE>), dim3(wpr * N_), dim3(64), 0, sl.cs, sl.geom, A);
+        else if (axis == 1)
+            hipLaunchKernelGGL((sfk::ray_march_kernel<T, 1, MODE>), dim3(wpr * nzl_), dim3(64), 0, sl.cs, sl.geom, A);
+        else if (high)
+            hipLaunchKernelGGL((sfk::ray_row_kernel<T, MODE, true>), dim3(wpr * nzl_), dim3(64), 0, sl.cs, sl.geom, A);
+        else
+            hipLaunchKernelGGL((sfk::ray_row_kernel<T, MODE, false>), dim3(wpr * nzl_), dim3(64), 0, sl.cs, sl.geom, A);
+        SF_HIP(hipGetLastError());
+    }
+
+    // One march over the owned planes of every slab, on its compute stream. Rays along i and j stay inside a plane: the
+    // slabs run side by side and each writes the pixel rows of its planes. Rays along k cross the slabs in visit order:
+    // a slab starts from the image pair the one before it left — read in place when that slab is in this process, a
+    // message otherwise (to self through the communicator with SF_FLAG_RCCL_SELF) — so the chain has P stages. At the
+    // end every compute stream has waited for the last stage: the next march may overwrite any pair.
+    void op_rays(int mode, int axis, int high, double sigma, int dens, int emit, int dst) {
+        const int w = mode == sfk::RAY_FIELD ? 1 : 0;
+        const size_t cnt = 2 * (size_t)N_ * N_;
+        const bool chain = axis == 2 && P_ > 1;
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            for (int f : {dens, emit, dst})
+                if (f >= 0) ensure(sl, f);
+            for (T** buf : {&sl.ray_img[w], (chain && ray_side(s, high ? 1 : 0) == TR_MSG) ? &sl.ray_in[w] : nullptr}) {
+                if (!buf || *buf) continue;
+                *buf = own_.dev<T>(cnt * sizeof(T));
+                SF_HIP(hipMemset(*buf, 0, cnt * sizeof(T)));
+                SF_HIP(hipDeviceSynchronize());  // (as alloc_field: the streams do not order against the null stream)
+            }
+        }
+        join();
+        const T h = T(1) / (T)N_;
+        const ncclDataType_t dt = sizeof(T) == 4 ? ncclFloat : ncclDouble;
+        const int kb = G_, ke = G_ + nzl_;
+        const char* names[3][3] = {{"render_i", "render_j", "render_k"},
+                                   {"render_emit_i", "render_emit_j", "render_emit_k"},
+                                   {"light_i", "light_j", "light_k"}};
+        for (int n = 0; n < L_; ++n) {
+            const int s = (chain && high) ? L_ - 1 - n : n;  // k-rays from the high side visit the slabs downwards
+            Slab& sl = slabs_[s];
+            sfk::RayArgs<T> A{};
+            A.dens = sl.field[dens];
+            A.emit = emit >= 0 ? sl.field[emit] : nullptr;
+            A.dst = dst >= 0 ? sl.field[dst] : nullptr;
+            A.img = sl.ray_img[w];
+            A.s = (T)sigma * h;
+            A.from_high = high;
+            if (chain) {
+                const int from = high ? 1 : 0, side = ray_side(s, from);
+                Slab* prev = (high ? s < L_ - 1 : s > 0) ? &slabs_[s + (high ? 1 : -1)] : nullptr;
+                if (side != TR_NONE && prev) st_wait(sl, sl.cs, *prev, &Slab::cs_mark);
+                if (side == TR_LOCAL) {
+                    A.in = prev->ray_img[w];
+                } else if (side == TR_MSG) {
+                    SF_NCCL(ncclGroupStart());
+                    if (prev) {  // SF_FLAG_RCCL_SELF: the pair (send from the slab the rays left, receive here)
+                        SF_NCCL(ncclSend(prev->ray_img[w], cnt, dt, 0, comm_, prev->cs));
+                        SF_NCCL(ncclRecv(sl.ray_in[w], cnt, dt, 0, comm_, sl.cs));
+                    } else {
+                        SF_NCCL(ncclRecv(sl.ray_in[w], cnt, dt, rank_ + (high ? 1 : -1), comm_, sl.cs));
+                    }
+                    SF_NCCL(ncclGroupEnd());
+                    ++rccl_groups_;
+                    if (trace_) {
+                        std::vector<Acc> acc{{sl.ray_in[w], true, 0, nplanes_}};
+                        if (prev) acc.push_back({prev->ray_img[w], false, 0, nplanes_});
+                        tr_op(prev ? "rays_carry_rccl_self" : "rays_carry_recv", sl, sl.cs, acc);
+                    }
+                    A.in = sl.ray_in[w];
+                }
+            }
+            switch (mode) {
+                case sfk::RAY_IMAGE: launch_rays<sfk::RAY_IMAGE>(sl, axis, high, A); break;
+                case sfk::RAY_IMAGE_EMIT: launch_rays<sfk::RAY_IMAGE_EMIT>(sl, axis, high, A); break;
+                default: launch_rays<sfk::RAY_FIELD>(sl, axis, high, A); break;
+            }
+            if (trace_) {
+                std::vector<Acc> acc{{A.dens, false, kb, ke}, {A.img, true, 0, nplanes_}};
+                if (A.emit) acc.push_back({A.emit, false, kb, ke});
+                if (A.dst) acc.push_back({A.dst, true, kb, ke});
+                if (A.in) acc.push_back({A.in, false, 0, nplanes_});
+                tr_op(names[mode][axis], sl, sl.cs, acc);
+            }
+            if (!chain) continue;
+            if (L_ > 1) ev_record(sl, &Slab::cs_mark, sl.cs);
+            if (nranks_ > 1 && !loopback_ && !ray_leaves_here(s, high) && tr_side(s, high ? 0 : 1) == TR_MSG) {
+                SF_NCCL(ncclGroupStart());
+                SF_NCCL(ncclSend(sl.ray_img[w], cnt, dt, rank_ + (high ? -1 : 1), comm_, sl.cs));
+                SF_NCCL(ncclGroupEnd());
+                ++rccl_groups_;
+                tr_op("rays_carry_send", sl, sl.cs, {{sl.ray_img[w], false, 0, nplanes_}});
+            }
+        }
+        if (chain && L_ > 1) {
+            Slab& last = slabs_[high ? 0 : L_ - 1];
+            for (Slab& sl : slabs_)
+                if (&sl != &last) st_wait(sl, sl.cs, last, &Slab::cs_mark);
+        }
+    }
+
     // Communicator guard: destroyed before own_ (declared after it), so before the streams its calls were issued on.
     struct Comm {
         ncclComm_t h = nullptr;
@@ -3282,6 +3453,8 @@ private:
     double* red_host_ = nullptr;    // pinned: the plane records of all N planes ([global k - 1][value])
     double* red_gather_ = nullptr;  // device: the same, the all-gather's buffer (contexts with a communicator) and what
                                     // cg_scalars_kernel folds (any context with check_every_ >= 1)
+    T* ray_stage_ = nullptr;         // pinned: the image pair on its way to the caller (sf_render_read)
+    int ray_axis_ = -1, ray_high_ = 0;  // view of the last sf_render (-1: none yet)
     sfk::CgState<T>* cg_state_ = nullptr;       // device: the scalars of a CG solve (check_every_ >= 1)
     sfk::CgState<T>* cg_state_host_ = nullptr;  // pinned: its mirror, filled by cg_state_read()
 };

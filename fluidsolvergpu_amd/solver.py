@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "sf_set_pressure_sync", "sf_pressure_sync_get",
     "sf_set_pressure_preconditioner", "sf_pressure_preconditioner_get",
     "sf_set_pressure_multigrid", "sf_pressure_multigrid_get", "sf_precondition",
+    "sf_render", "sf_render_read", "sf_light",
 )
 
 
@@ -85,6 +86,11 @@ class SfPressurePreconditioner(C.Structure):
 class SfPressureMultigrid(C.Structure):
     """sf_pressure_multigrid of include/sfgpu.h (docs/SPEC.md §11.3)."""
     _fields_ = [("sweeps", C.c_int), ("max_levels", C.c_int), ("coarse_sweeps", C.c_int), ("levels", C.c_int)]
+
+
+class SfRenderParams(C.Structure):
+    """sf_render_params of include/sfgpu.h (docs/SPEC.md §12)."""
+    _fields_ = [("axis", C.c_int), ("from_high", C.c_int), ("sigma", C.c_double), ("dens", C.c_int), ("emit", C.c_int)]
 
 
 _ctx = C.c_void_p
@@ -132,6 +138,9 @@ lib.sf_pressure_preconditioner_get.argtypes = [_ctx, C.POINTER(SfPressurePrecond
 lib.sf_set_pressure_multigrid.argtypes = [_ctx, C.c_int, C.c_int, C.c_int]
 lib.sf_pressure_multigrid_get.argtypes = [_ctx, C.POINTER(SfPressureMultigrid)]
 lib.sf_precondition.argtypes = [_ctx, C.c_int, C.c_int]
+lib.sf_render.argtypes = [_ctx, C.POINTER(SfRenderParams)]
+lib.sf_render_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
+lib.sf_light.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -399,6 +408,25 @@ class FluidSolver:
         """z = M(r) with the preconditioner in force (the V-cycle of §11.3, else the Jacobi sweeps of §11.2): r is read
         on interior cells, z is written whole."""
         self._ck(lib.sf_precondition(self._h, _fid(z), _fid(r)))
+
+    # -- volume rendering and light marching (docs/SPEC.md §12) ---------------------------------
+    def render(self, dens="dens", emit=None, axis=2, from_high=0, sigma=1.0):
+        """One ray per pixel along axis (0: i, 1: j, 2: k), entering at index 1 (from_high = 0) or N (1), through the
+        density slot `dens` with opacity sigma * h * dens per cell and the emission slot `emit` (None: none). Returns
+        (colour, transmittance): two (N, N) arrays indexed [b - 1, a - 1] over the two remaining axes a < b, zeros
+        where this context holds no pixel. Collective on several ranks; waits for the image."""
+        p = SfRenderParams(axis=int(axis), from_high=int(from_high), sigma=float(sigma), dens=_fid(dens),
+                           emit=-1 if emit is None else _fid(emit))
+        self._ck(lib.sf_render(self._h, C.byref(p)))
+        colour = np.zeros((self.N, self.N), self.np_dtype)
+        trans = np.zeros((self.N, self.N), self.np_dtype)
+        self._ck(lib.sf_render_read(self._h, colour.ctypes.data_as(C.c_void_p), trans.ctypes.data_as(C.c_void_p)))
+        return colour, trans
+
+    def light(self, dst, dens="dens", axis=1, from_high=1, sigma=1.0):
+        """dst = the transmittance of the ray along axis in front of every cell (1 on the first cell visited), then
+        set_bnd(0, dst): what render takes as `emit` for self-shadowed smoke. dst must not be dens."""
+        self._ck(lib.sf_light(self._h, _fid(dst), _fid(dens), int(axis), int(from_high), float(sigma)))
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

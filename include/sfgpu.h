@@ -335,6 +335,33 @@ int sf_set_pressure_multigrid(sf_ctx* ctx, int sweeps, int max_levels, int coars
 int sf_pressure_multigrid_get(const sf_ctx* ctx, sf_pressure_multigrid* out);
 int sf_precondition(sf_ctx* ctx, int z, int r);
 
+/* Axis-aligned volume rendering and light marching of docs/SPEC.md §12: an N x N image of the smoke from data that
+ * already sits in device memory, instead of a (N+2)^3 frame over the bus. One ray per pixel runs along axis (0: i,
+ * 1: j, 2: k) through the N interior cells of a line, entering at index 1 (from_high = 0) or N (from_high = 1). A cell
+ * has the opacity a = clamp(sigma * h * dens, 0, 1) (NaN and negative densities are transparent) and, front to back,
+ *     C = C + (Tr * a) * emit;  Tr = Tr * (1 - a)       from (C, Tr) = (0, 1); emit == -1: C = C + Tr * a.
+ * The order along a ray is strictly sequential, so the bits are the same for every decomposition and transport and equal
+ * the numpy reference tests/render_ref.py.
+ *   sf_render: asynchronous; writes no field and changes no later step by a bit. Collective on several ranks: rays along
+ *       k cross the slabs in order and each slab starts from the (C, Tr) image pair the one before it left; rays along i
+ *       and j stay inside a plane. dens and emit are read on owned planes only (no halo exchange); emit == dens is allowed.
+ *   sf_render_read: waits for the last sf_render, then writes the final C (colour) and Tr (transmittance) of every ray
+ *       this context holds into dense N * N arrays of the context's dtype; either pointer may be NULL. The pixel of the
+ *       ray at (a, b) — the two remaining axes in increasing order: (j, k), (i, k) or (i, j) — is at (a-1) + N*(b-1). A
+ *       context writes the pixels it holds, as sf_download does for planes: for i and j views the pixel rows b = k of its
+ *       owned planes, for a k view the whole image on the context that owns the plane the rays leave from and nothing
+ *       elsewhere.
+ *   sf_light: dst = the exclusive transmittance (the Tr of the ray before the cell is applied; exactly 1 on the first
+ *       cell visited), then set_bnd(0, dst) and its ghost planes. Rendering with emit = dst and another axis gives
+ *       self-shadowed smoke.
+ * SF_ERR_INVALID: a NULL params pointer, an axis outside 0..2, from_high outside {0, 1}, a sigma that is negative or
+ * not finite, a slot out of range, dst == dens, sf_render_read before any sf_render. An SF_USER slot not yet used is
+ * allocated (zeros) first, as elsewhere. The image buffers are allocated by the first call. */
+typedef struct sf_render_params { int axis, from_high; double sigma; int dens, emit; } sf_render_params; /* emit = -1: none */
+int sf_render(sf_ctx* ctx, const sf_render_params* p);
+int sf_render_read(sf_ctx* ctx, void* colour, void* transmittance);
+int sf_light(sf_ctx* ctx, int dst, int dens, int axis, int from_high, double sigma);
+
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);
 int sf_set_coefficients(sf_ctx* ctx, double dt, double diff, double visc);

@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Time volume rendering and light marching of docs/SPEC.md §12 (measurement aid, not the benchmark).
+
+SPEC §5 inputs with bound sources (the benchmark's workload), K = 20, after two steps. sf_render and sf_light are
+asynchronous, so they are timed on the device: the context's event pair around --reps calls, per call. Per case, in one
+process:
+  render_<axis>_ms / render_emit_<axis>_ms   one sf_render of the density along i, j, k, without / with an emission field
+  light_<axis>_ms       one sf_light (the march and the set_bnd of its result)
+  reduce_sum_ms         one sf_reduce(SF_RED_SUM) of the density, host wall time of the synchronising call, and
+  reduce_rows_ms        its device time: the row pass, which reads the bytes a march reads with N^2 waves instead of
+                        N^2 / 64, the fold of its records and their copy to the host
+  *_over_reduce         march time / reduce_rows_ms
+  snapshot_ms           sf_snapshot + sf_snapshot_read of the density: the path an image replaces (host wall time)
+  render_read_ms        sf_render + sf_render_read (host wall time)
+  step_ms               vel_step + dens_step per step, host wall time of --steps steps after a sync
+  render1 / render10    the same loop with light + render + read after every step / every 10th step, and its share
+
+  python tools/render_bench.py                          # 64^3, 128^3, 256^3, 512^3 fp32 and 256^3 fp64
+  python tools/render_bench.py --cases 256:f32 --reps 5 # one case (e.g. under rocprofv3 --kernel-trace --stats)
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DT, DIFF, VISC, K, SIGMA = 0.1, 1e-4, 1e-4, 20, 4.0
+AXES = "ijk"
+
+
+def device_ms(fs, call, reps, warmup=2, trials=3):
+    for _ in range(warmup):
+        call()
+    fs.sync()
+    best = float("inf")
+    for _ in range(trials):
+        fs.timer_start()
+        for _ in range(reps):
+            call()
+        best = min(best, fs.timer_stop() / reps)
+    return best
+
+
+def wall_ms(fs, call, reps, warmup=2):
+    t = []
+    for _ in range(warmup + reps):
+        fs.sync()
+        t0 = time.perf_counter()
+        call()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return min(t[warmup:])
+
+
+def loop_ms(fs, steps, every):
+    fs.sync()
+    t0 = time.perf_counter()
+    for s in range(steps):
+        fs.vel_step()
+        fs.dens_step()
+        if every and s % every == 0:
+            fs.light("dens0", "dens", 2, 1, SIGMA)  # (dens0 is scratch between steps while its source is bound)
+            fs.render("dens", "dens0", 1, 0, SIGMA)
+    fs.sync()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def make(N, dtype):
+    from bench import upload_inputs
+    from fluidsolvergpu_amd import solver as S
+
+    fs = S.FluidSolver(N, dtype=dtype, iters=K, dt=DT, diff=DIFF, visc=VISC)
+    upload_inputs(fs, N, DT)
+    fs.bind_sources()
+    for _ in range(2):
+        fs.vel_step()
+        fs.dens_step()
+    fs.sync()
+    return S, fs
+
+
+def marches(S, fs, reps, axes, suffix=""):
+    out = {}
+    for axis in axes:
+        for emit, tag in ((-1, "render"), (S.FIELD_IDS["dens0"], "render_emit")):
+            p = S.SfRenderParams(axis=axis, from_high=0, sigma=SIGMA, dens=S.FIELD_IDS["dens"], emit=emit)
+            out[f"{tag}_{AXES[axis]}{suffix}_ms"] = device_ms(fs, lambda: S.lib.sf_render(fs._h, C.byref(p)), reps)
+        out[f"light_{AXES[axis]}{suffix}_ms"] = device_ms(fs, lambda: fs.light("dens0", "dens", axis, 0, SIGMA), reps)
+    return out
+
+
+def time_case(N, dtype, reps, steps):
+    S, fs = make(N, dtype)
+    out = {"grid": N, "dtype": dtype, "K": K, "reps": reps, "steps": steps}
+    out.update(marches(S, fs, reps, (0, 1, 2)))
+    red = C.c_double()
+    out["reduce_sum_ms"] = wall_ms(fs, lambda: fs.reduce("sum", "dens"), reps)
+    # (the call synchronises: one call per event pair, so that no host gap is timed)
+    out["reduce_rows_ms"] = device_ms(fs, lambda: S.lib.sf_reduce(fs._h, S.SF_RED_SUM, S.FIELD_IDS["dens"], C.byref(red)),
+                                      1, trials=reps)
+    frame = np.zeros(fs.shape, fs.np_dtype)
+
+    def snapshot():
+        fs.snapshot(["dens"])
+        fs.snapshot_read(0, frame)
+
+    out["snapshot_ms"] = wall_ms(fs, snapshot, max(2, reps // 4))
+    out["render_read_ms"] = wall_ms(fs, lambda: fs.render("dens", None, 1, 0, SIGMA), reps)
+    loops = {0: [], 1: [], 10: []}
+    for _ in range(3):  # best of three passes per variant, the variants interleaved
+        for every in loops:
+            loops[every].append(loop_ms(fs, steps, every))
+    step, r1, r10 = (min(loops[e]) for e in (0, 1, 10))
+    out.update(step_ms=step, render1_step_ms=r1, render10_step_ms=r10, render1_share=(r1 - step) / step,
+               render10_share=(r10 - step) / step)
+    fs.close()
+    for k in [k for k in out if k.startswith(("render_", "light_")) and k.endswith("_ms") and k != "render_read_ms"]:
+        out[k[:-3] + "_over_reduce"] = out[k] / out["reduce_rows_ms"]
+    return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="+", default=["64:f32", "128:f32", "256:f32", "512:f32", "256:f64"])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20)
+    a = ap.parse_args()
+    for c in a.cases:
+        n, t = c.split(":")
+        print(json.dumps(time_case(int(n), t, a.reps, a.steps)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
