@@ -1,0 +1,44 @@
+"""Reads the kernel-resource remarks of one compile (hipcc -Rpass-analysis=kernel-resource-usage, stderr kept in a file),
+prints what is not a remark (warnings), and checks the instantiations of sfk::view_march_kernel against the limits of
+docs/SPEC.md §13: no scratch, no LDS, no AGPRs, at most 128 VGPRs (four waves per SIMD resident). Prints their table."""
+import re
+import sys
+
+LIMITS = {"VGPRs": 128, "AGPRs": 0, "ScratchSize [bytes/lane]": 0, "LDS Size [bytes/block]": 0, "VGPRs Spill": 0}
+
+
+def main(path):
+    kernels, cur, other, skip = {}, None, [], 0
+    for line in open(path, errors="replace"):
+        m = re.search(r"remark: (.*?) \[-Rpass-analysis=kernel-resource-usage\]", line)
+        if m:
+            skip = 2  # the source line and the caret that follow a remark
+            name = re.match(r"Function Name: (\S+)", m.group(1))
+            if name:
+                cur = kernels.setdefault(name.group(1), {})
+            elif cur is not None and ":" in m.group(1):
+                k, v = m.group(1).rsplit(":", 1)
+                cur[k.strip()] = v.strip()
+        elif skip and not re.match(r"\S+:\d+:\d+: ", line):
+            skip -= 1
+        else:
+            other.append(line)
+    other = [ln for ln in other if not ln.startswith("In file included from")]
+    sys.stderr.writelines(ln for ln in other if not re.match(r"\d+ (warning|remark)s? generated", ln.strip()) or "warning" in ln)
+    view = {k: v for k, v in kernels.items() if "view_march_kernel" in k}
+    if not view:
+        sys.exit(f"{path}: no view_march_kernel among {len(kernels)} kernels")
+    bad = 0
+    for name, r in sorted(view.items()):
+        print(f"  {name}: VGPRs {r.get('VGPRs')} AGPRs {r.get('AGPRs')} SGPRs {r.get('TotalSGPRs')} scratch "
+              f"{r.get('ScratchSize [bytes/lane]')} LDS {r.get('LDS Size [bytes/block]')} waves/SIMD "
+              f"{r.get('Occupancy [waves/SIMD]')}")
+        for key, cap in LIMITS.items():
+            if key not in r or int(r[key]) > cap:
+                print(f"    {key} = {r.get(key)} exceeds {cap}", file=sys.stderr)
+                bad += 1
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])

@@ -1,6 +1,7 @@
 // sf_api.hip — the C ABI of include/sfgpu.h over the type-erased solver (sf_base.hpp). No exception crosses it: every
 // entry point returns a status code and leaves the message in sf_last_error (the reference's convention is print +
 // exit(1), FluidGPU.cuh:34-41; the driver does that with the code it gets back).
+#include <cmath>
 #include "sf_base.hpp"
 
 using namespace sfi;
@@ -267,6 +268,53 @@ int sf_render_read(sf_ctx* ctx, void* colour, void* transmittance) {
 }
 int sf_light(sf_ctx* ctx, int dst, int dens, int axis, int from_high, double sigma) {
     return guarded(ctx, [&](SolverBase& s) { s.light(dst, dens, axis, from_high, sigma); });
+}
+int sf_render_view(sf_ctx* ctx, const sf_view_params* p) {
+    return guarded(ctx, [&](SolverBase& s) { s.render_view(p); });
+}
+int sf_render_view_read(sf_ctx* ctx, void* colour, void* transmittance) {
+    return guarded(ctx, [&](SolverBase& s) { s.render_view_read(colour, transmittance); });
+}
+// docs/SPEC.md §13: double arithmetic, + - * / sqrt only, bracketed as written (this file is compiled without contraction)
+int sf_view_frame(int N, const double dir[3], const double up[3], int width, int height, double step, double sigma,
+                  sf_view_params* out) {
+    if (!dir || !up || !out || N < 1) return SF_ERR_INVALID;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(dir[c]) || !std::isfinite(up[c])) return SF_ERR_INVALID;
+    if (!std::isfinite(step) || !(step > 0.0) || !std::isfinite(sigma) || sigma < 0.0) return SF_ERR_INVALID;
+    if (width < 1 || width > 16384 || height < 1 || height > 16384) return SF_ERR_INVALID;
+    auto len = [](const double* v) { return std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); };
+    auto cross = [](const double* a, const double* b, double* o) {
+        o[0] = a[1] * b[2] - a[2] * b[1], o[1] = a[2] * b[0] - a[0] * b[2], o[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double d[3], r[3], u[3];
+    const double ld = len(dir);
+    if (!(ld > 0.0) || !std::isfinite(ld)) return SF_ERR_INVALID;
+    for (int c = 0; c < 3; ++c) d[c] = dir[c] / ld;
+    cross(d, up, r);
+    const double lr = len(r);
+    if (!(lr > 0.0) || !std::isfinite(lr)) return SF_ERR_INVALID;
+    for (int c = 0; c < 3; ++c) r[c] = r[c] / lr;
+    cross(r, d, u);
+    const double L = std::sqrt(3.0) * N, pix = L / (width > height ? width : height), cen = (N + 1) / 2.0;
+    if (!(L / step < 65536.0)) return SF_ERR_INVALID;  // samples would leave 1 .. 65536
+    sf_view_params f{};
+    for (int c = 0; c < 3; ++c) {
+        f.du[c] = r[c] * pix;
+        f.dv[c] = u[c] * pix;
+        f.step[c] = d[c] * step;
+        f.origin[c] = ((cen - d[c] * (L / 2)) - f.du[c] * ((width - 1) / 2.0)) - f.dv[c] * ((height - 1) / 2.0);
+    }
+    f.width = width, f.height = height;
+    f.samples = (int)(L / step) + 1;
+    f.sigma = sigma * step;
+    f.dens = f.emit = -1;
+    for (const double* v : {f.origin, f.du, f.dv, f.step})
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(v[c])) return SF_ERR_INVALID;
+    if (!std::isfinite(f.sigma)) return SF_ERR_INVALID;
+    *out = f;
+    return SF_OK;
 }
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });

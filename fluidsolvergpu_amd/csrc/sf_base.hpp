@@ -99,6 +99,8 @@ public:
     virtual void render(const sf_render_params* p) = 0;
     virtual void render_read(void* colour, void* transmittance) = 0;
     virtual void light(int dst, int dens, int axis, int from_high, double sigma) = 0;
+    virtual void render_view(const sf_view_params* p) = 0;
+    virtual void render_view_read(void* colour, void* transmittance) = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

@@ -27,7 +27,7 @@
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
 //             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
-//             [--help]
+//             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -57,7 +57,13 @@
 // source, else SF_DENS0, which is scratch between steps while a density source is bound — and the view takes it as its
 // emission. The file is binary PGM (P5), maxval 65535, big-endian, q = (int)(min(max(C, 0), 1) * 65535 + 0.5) with
 // NaN -> 0, the row with the highest b first.
+// --render-view DX,DY,DZ:WxH:SIGMA[:STEP]: at every output step a W x H image of the density seen along the direction
+// (DX, DY, DZ) in (i, j, k) (docs/SPEC.md §13, the frame of sf_view_frame), "view_<frame, 4 digits>.pgm" in the same PGM
+// format, written by the process that holds the image (the last rank for DZ >= 0, else rank 0). up is (0,0,1), or (0,1,0)
+// when the direction is parallel to k. SIGMA >= 0 is the extinction per unit length, STEP > 0 the sample distance in
+// cells (default 1).
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -99,6 +105,9 @@ struct Options {
     double cg_tol = 1e-3;
     int render_axis = -1, render_high = 0, light_axis = -1, light_high = 0;  // --render (axis -1: off / no light)
     double render_sigma = 0.0;
+    bool view = false;  // --render-view
+    double view_dir[3] = {0, 0, 1}, view_sigma = 0.0, view_step = 1.0;
+    int view_w = 0, view_h = 0;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
     int rank = 0, world = 1, local_rank = 0;
@@ -173,6 +182,7 @@ static void usage(FILE* to) {
             "                 [--maccormack vel|dens|both] [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]]\n"
             "                 [--pressure-sync M] [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]]\n"
             "                 [--render VIEW:SIGMA[:LIGHT]]   VIEW, LIGHT: i+ i- j+ j- k+ k- (+ enters at the low index)\n"
+            "                 [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]]   an image along any direction, STEP in cells (default 1)\n"
             "                 [--loopback --rank R --world W] [--help]\n");
 }
 
@@ -181,6 +191,44 @@ static bool parse_view(const std::string& v, int& axis, int& high) {
     if (v.size() != 2 || (v[0] != 'i' && v[0] != 'j' && v[0] != 'k') || (v[1] != '+' && v[1] != '-')) return false;
     axis = v[0] - 'i';
     high = v[1] == '-' ? 1 : 0;
+    return true;
+}
+
+// a whole string as a finite double
+static bool parse_double(const std::string& v, double& out) {
+    if (v.empty() || std::isspace((unsigned char)v[0])) return false;
+    char* end = nullptr;
+    out = strtod(v.c_str(), &end);
+    return *end == 0 && std::isfinite(out);
+}
+// a whole string of 1 .. 5 digits as an int in 1 .. 16384
+static bool parse_extent(const std::string& v, int& out) {
+    if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos) return false;
+    out = (int)strtol(v.c_str(), nullptr, 10);
+    return out >= 1 && out <= 16384;
+}
+// DX,DY,DZ:WxH:SIGMA[:STEP] into the view members of o
+static bool parse_render_view(const std::string& spec, Options& o) {
+    std::vector<std::string> part;
+    for (size_t at = 0;;) {
+        const size_t c = spec.find(':', at);
+        part.push_back(spec.substr(at, c == std::string::npos ? c : c - at));
+        if (c == std::string::npos) break;
+        at = c + 1;
+    }
+    if (part.size() < 3 || part.size() > 4) return false;
+    const size_t c1 = part[0].find(','), c2 = c1 == std::string::npos ? c1 : part[0].find(',', c1 + 1);
+    if (c2 == std::string::npos || part[0].find(',', c2 + 1) != std::string::npos) return false;
+    if (!parse_double(part[0].substr(0, c1), o.view_dir[0]) || !parse_double(part[0].substr(c1 + 1, c2 - c1 - 1), o.view_dir[1]) ||
+        !parse_double(part[0].substr(c2 + 1), o.view_dir[2]))
+        return false;
+    if (o.view_dir[0] == 0.0 && o.view_dir[1] == 0.0 && o.view_dir[2] == 0.0) return false;
+    const size_t x = part[1].find('x');
+    if (x == std::string::npos || !parse_extent(part[1].substr(0, x), o.view_w) || !parse_extent(part[1].substr(x + 1), o.view_h))
+        return false;
+    if (!parse_double(part[2], o.view_sigma) || o.view_sigma < 0.0) return false;
+    o.view_step = 1.0;
+    if (part.size() == 4 && (!parse_double(part[3], o.view_step) || !(o.view_step > 0.0))) return false;
     return true;
 }
 
@@ -300,6 +348,21 @@ static Options parse(int argc, char** argv) {
             if (!ok) {
                 fprintf(stderr, "--render takes VIEW:SIGMA[:LIGHT] (VIEW, LIGHT one of i+ i- j+ j- k+ k-, SIGMA >= 0), not %s\n",
                         spec.c_str());
+                exit(2);
+            }
+        }
+        else if (s == "--render-view") {
+            const std::string spec = next();
+            sf_view_params probe;
+            o.view = parse_render_view(spec, o);
+            if (o.view) {  // (the frame depends on --n, which may follow: built when the run starts; here only what N cannot mend)
+                const double upv[3] = {0.0, (o.view_dir[0] == 0.0 && o.view_dir[1] == 0.0) ? 1.0 : 0.0,
+                                       (o.view_dir[0] == 0.0 && o.view_dir[1] == 0.0) ? 0.0 : 1.0};
+                o.view = sf_view_frame(1, o.view_dir, upv, o.view_w, o.view_h, 1.0, o.view_sigma, &probe) == SF_OK;
+            }
+            if (!o.view) {
+                fprintf(stderr, "--render-view takes DX,DY,DZ:WxH:SIGMA[:STEP] (a direction that is not zero, W and H in 1 .. 16384, "
+                                "SIGMA >= 0, STEP > 0), not %s\n", spec.c_str());
                 exit(2);
             }
         }
@@ -440,23 +503,17 @@ static void write_frame(const Options& o, int frame, int kb, int ke, const std::
 // The image of one output step (docs/SPEC.md §12): the pixel rows [row_b, row_e) of colour this rank holds as binary PGM,
 // 16 bits big-endian, the highest row first.
 template <class T>
-static void write_render(const Options& o, int frame, const std::vector<T>& colour, int row_b, int row_e) {
-    char name[64];
-    if (o.world == 1)
-        snprintf(name, sizeof name, "/render_%04d.pgm", frame);
-    else
-        snprintf(name, sizeof name, "/render_GPU%d_%04d.pgm", o.rank, frame);
-    const std::string path = o.out + name;
+static void write_pgm(const std::string& path, const std::vector<T>& colour, int width, int row_b, int row_e) {
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) {
         fprintf(stderr, "Error: cannot write %s\n", path.c_str());
         exit(1);
     }
-    fprintf(f, "P5\n%d %d\n65535\n", o.n, row_e - row_b);
-    std::vector<unsigned char> row(2 * (size_t)o.n);
+    fprintf(f, "P5\n%d %d\n65535\n", width, row_e - row_b);
+    std::vector<unsigned char> row(2 * (size_t)width);
     for (int b = row_e - 1; b >= row_b; --b) {
-        for (int a = 0; a < o.n; ++a) {
-            const double c = (double)colour[(size_t)a + (size_t)o.n * b];
+        for (int a = 0; a < width; ++a) {
+            const double c = (double)colour[(size_t)a + (size_t)width * b];
             const double cl = c > 0.0 ? (c < 1.0 ? c : 1.0) : 0.0;  // NaN -> 0
             const int q = (int)(cl * 65535.0 + 0.5);
             row[2 * a] = (unsigned char)(q >> 8);
@@ -465,6 +522,15 @@ static void write_render(const Options& o, int frame, const std::vector<T>& colo
         fwrite(row.data(), 1, row.size(), f);
     }
     fclose(f);
+}
+template <class T>
+static void write_render(const Options& o, int frame, const std::vector<T>& colour, int row_b, int row_e) {
+    char name[64];
+    if (o.world == 1)
+        snprintf(name, sizeof name, "/render_%04d.pgm", frame);
+    else
+        snprintf(name, sizeof name, "/render_GPU%d_%04d.pgm", o.rank, frame);
+    write_pgm<T>(o.out + name, colour, o.n, row_b, row_e);
 }
 
 template <class T>
@@ -535,6 +601,20 @@ static int run(const Options& o) {
         img_b = 0, img_e = mine ? o.n : 0;
     }
     std::vector<T> colour(o.render_axis >= 0 ? (size_t)o.n * o.n : 0);
+    // --render-view: the frame for this N; the image ends on the rank that owns the last slab visited
+    sf_view_params vp{};
+    bool view_mine = false;
+    if (o.view) {
+        const bool along_k = o.view_dir[0] == 0.0 && o.view_dir[1] == 0.0;
+        const double up[3] = {0.0, along_k ? 1.0 : 0.0, along_k ? 0.0 : 1.0};
+        if (sf_view_frame(o.n, o.view_dir, up, o.view_w, o.view_h, o.view_step, o.view_sigma, &vp) != SF_OK) {
+            fprintf(stderr, "--render-view: no frame for this direction, step and grid size\n");
+            exit(2);
+        }
+        vp.dens = SF_DENS;
+        view_mine = o.loopback || o.rank == ((sizeof(T) == 4 ? (double)(float)vp.step[2] : vp.step[2]) < 0.0 ? 0 : o.world - 1);
+    }
+    std::vector<T> view_colour(o.view ? (size_t)o.view_w * o.view_h : 0);
     // forces (SPEC §8): added by every vel_step to copies of the bound sources
     SF_CHECK_RETURN(sf_set_vorticity_confinement(g_ctx, o.vorticity));
     SF_CHECK_RETURN(sf_set_buoyancy(g_ctx, o.buoyancy, o.ambient, o.buoyancy_axis));
@@ -650,6 +730,15 @@ static int run(const Options& o) {
                 SF_CHECK_RETURN(sf_render(g_ctx, &rp));
                 SF_CHECK_RETURN(sf_render_read(g_ctx, colour.data(), nullptr));
                 if (img_e > img_b) write_render<T>(o, frame, colour, img_b, img_e);
+            }
+            if (o.view) {
+                SF_CHECK_RETURN(sf_render_view(g_ctx, &vp));
+                SF_CHECK_RETURN(sf_render_view_read(g_ctx, view_colour.data(), nullptr));
+                if (view_mine) {
+                    char name[64];
+                    snprintf(name, sizeof name, "/view_%04d.pgm", frame);
+                    write_pgm<T>(o.out + name, view_colour, o.view_w, 0, o.view_h);
+                }
             }
             if (ntr > 0) fetch_tracers();
             if (o.sync_output) {

@@ -2446,6 +2446,7 @@ struct TriSampleDev {
     // clamp_plane (decomposed tracers, SPEC §6.1): the local plane k0 - kg0 is clamped into [0, np - 2] so that the
     // two planes read are stored by this slab whatever the position (tracers owned elsewhere — loopback arrivals —
     // included). A tracer owned by the slab reads inside that range already, so its sample does not change.
+    TriSampleDev() = default;
     __device__ TriSampleDev(const Geom& g, T x, T y, T z, bool clamp_plane = false) {
         const int N = g.N;
         const T Nf = (T)N, lo = T(0.5), hi = Nf + T(0.5);
@@ -2471,6 +2472,17 @@ struct TriSampleDev {
         dj = g.px;
         dk = g.plane;
     }
+    // the eight cells of the sample, and the sample of them: apart, so that a caller can issue the loads of several
+    // samples before it combines the first (view_march_kernel)
+    __device__ void load(const T* __restrict__ d0, T (&c)[8]) const {
+        c[0] = d0[q], c[1] = d0[q + dk], c[2] = d0[q + dj], c[3] = d0[q + dj + dk];
+        c[4] = d0[q + 1], c[5] = d0[q + 1 + dk], c[6] = d0[q + 1 + dj], c[7] = d0[q + 1 + dj + dk];
+    }
+    __device__ T combine(const T (&c)[8]) const {
+        return s0 * (t0 * (r0 * c[0] + r1 * c[1]) + t1 * (r0 * c[2] + r1 * c[3])) +
+               s1 * (t0 * (r0 * c[4] + r1 * c[5]) + t1 * (r0 * c[6] + r1 * c[7]));
+    }
+    // (= combine of load, written out: the tracer kernels' code stays what it was)
     __device__ T operator()(const T* __restrict__ d0) const {
         return s0 * (t0 * (r0 * d0[q] + r1 * d0[q + dk]) + t1 * (r0 * d0[q + dj] + r1 * d0[q + dj + dk])) +
                s1 * (t0 * (r0 * d0[q + 1] + r1 * d0[q + 1 + dk]) +
@@ -3582,6 +3594,116 @@ __global__ void __launch_bounds__(64) ray_row_kernel(Geom g, RayArgs<T> A) {
         const long pix = (j - 1) + (long)g.N * (g.kg0 + g.G + p - 1);
         if (MODE != RAY_FIELD) A.img[pix] = C;
         A.img[NN + pix] = Tr;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Orthographic volume rendering from any direction (docs/SPEC.md §13). One lane owns one pixel of a W x H image and a
+// wave an 8 x 8 pixel tile, so the eight gathers of neighbouring lanes fall into neighbouring lines. The position of
+// sample n is computed from n afresh; a slab applies the samples it owns (§6.1) and hands the (C, Tr) pair on.
+// Each component of the position is monotone in n, so the samples a slab may own form one range of n per lane: it is
+// found by bisection on the closed bounds (a superset by at most a sample per end) and the predicate of §13 is then
+// applied to every sample of it, by a select on the state: the loads of a trip are unconditional (addresses clamped as
+// clamp_plane does) and all issued before the first sample is applied. Lanes past the image edge march a clamped pixel
+// and store nothing.
+template <class T>
+struct ViewArgs {
+    const T* dens;
+    const T* emit;  // RAY_IMAGE_EMIT only
+    const T* in;    // the (C, Tr) pair of the slab the rays come from; null: the rays start here
+    T* img;         // C at [0, W H), Tr at [W H, 2 W H): pixel (a, b) at a + W b
+    T o[3], du[3], dv[3], ds[3];
+    T s;            // T(sigma) * h
+    int width, height, samples;
+};
+template <class T>
+constexpr int VIEW_U = 16 / (int)sizeof(T);  // samples per trip: 32 (fp32) / 16 (fp64) gathers per field and lane
+
+// first n in [0, S] with pred(base + T(n) * d) true, for a pred that goes from false to true once (S: never)
+template <class T, class Pred>
+__device__ __forceinline__ int view_first(int S, T base, T d, Pred pred) {
+    int lo = 0, hi = S;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pred(base + (T)mid * d)) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+// the n in [n0, n1) whose component base + T(n) * d may lie in [L, H]: narrows [n0, n1)
+template <class T>
+__device__ __forceinline__ void view_range(int S, T base, T d, T L, T H, int& n0, int& n1) {
+    int b, e;
+    if (d >= T(0)) {
+        b = view_first(S, base, d, [L](T x) { return x >= L; });
+        e = view_first(S, base, d, [H](T x) { return !(x <= H); });
+    } else {
+        b = view_first(S, base, d, [H](T x) { return x <= H; });
+        e = view_first(S, base, d, [L](T x) { return !(x >= L); });
+    }
+    n0 = b > n0 ? b : n0;
+    n1 = e < n1 ? e : n1;
+}
+
+template <class T, int MODE>
+__global__ void __launch_bounds__(64) view_march_kernel(Geom g, ViewArgs<T> A) {
+    static_assert(MODE == RAY_IMAGE || MODE == RAY_IMAGE_EMIT, "the image forms");
+    constexpr int U = VIEW_U<T>;
+    const int tw = (A.width + 7) >> 3;
+    const int ty = (int)blockIdx.x / tw, tx = (int)blockIdx.x - ty * tw;
+    const int a = 8 * tx + ((int)threadIdx.x & 7), b = 8 * ty + ((int)threadIdx.x >> 3);
+    const bool live = a < A.width && b < A.height;
+    const int ac = a < A.width ? a : A.width - 1, bc = b < A.height ? b : A.height - 1;
+    const T lo = T(0.5), hi = (T)g.N + T(0.5);
+    // the heights this slab owns (§6.1): k0 in [kg0 + G, kg0 + G + nzl), and k0 = 0 on slab 0
+    const int klo = g.kg0 + g.G;
+    const T zlo = klo == 1 ? lo : (T)klo, zhx = (T)(klo + g.nzl);
+    const T px = (A.o[0] + (T)ac * A.du[0]) + (T)bc * A.dv[0];
+    const T py = (A.o[1] + (T)ac * A.du[1]) + (T)bc * A.dv[1];
+    const T pz = (A.o[2] + (T)ac * A.du[2]) + (T)bc * A.dv[2];
+    int n0 = 0, n1 = A.samples;
+    view_range(A.samples, px, A.ds[0], lo, hi, n0, n1);
+    view_range(A.samples, py, A.ds[1], lo, hi, n0, n1);
+    view_range(A.samples, pz, A.ds[2], zlo, zhx < hi ? zhx : hi, n0, n1);
+    const long WH = (long)A.width * A.height;
+    const long pix = ac + (long)A.width * bc;
+    T C = T(0), Tr = T(1);
+    if (A.in != nullptr) {
+        C = A.in[pix];
+        Tr = A.in[WH + pix];
+    }
+    for (int n = n0; n < n1; n += U) {
+        // positions and addresses of the trip, then all its gathers, then the samples in order
+        bool on[U];
+        TriSampleDev<T> S[U];
+        T cd[U][8], ce[MODE == RAY_IMAGE_EMIT ? U : 1][8];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T fn = (T)(n + u);
+            const T x = px + fn * A.ds[0], y = py + fn * A.ds[1], z = pz + fn * A.ds[2];
+            // (bitwise, not &&: a short-circuit is a join, and the loads of the trip would be waited for at each one)
+            on[u] = (n + u < n1) & (x >= lo) & (x <= hi) & (y >= lo) & (y <= hi) & (z >= lo) & (z <= hi) & (z >= zlo) & (z < zhx);
+            S[u] = TriSampleDev<T>(g, x, y, z, true);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            S[u].load(A.dens, cd[u]);
+            if constexpr (MODE == RAY_IMAGE_EMIT) S[u].load(A.emit, ce[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T d = S[u].combine(cd[u]);
+            T e = T(0);
+            if constexpr (MODE == RAY_IMAGE_EMIT) e = S[u].combine(ce[u]);
+            T Cn = C, Trn = Tr;
+            ray_step<T, MODE>(ray_opacity(A.s, d), e, Cn, Trn);
+            C = on[u] ? Cn : C;
+            Tr = on[u] ? Trn : Tr;
+        }
+    }
+    if (live) {
+        A.img[pix] = C;
+        A.img[WH + pix] = Tr;
     }
 }
 

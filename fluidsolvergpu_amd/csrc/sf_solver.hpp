@@ -78,9 +78,10 @@ class Solver final : public SolverBase {
         double* red_rows = nullptr;
         double* red_planes = nullptr;
         // rays (SPEC §12), allocated by the first sf_render [0] / sf_light [1]: the slab's (C, Tr) image pair, 2 N^2
-        // values, and, where the pair of the slab a k-ray comes from arrives as a message, the buffer it arrives in
-        T* ray_img[2] = {};
-        T* ray_in[2] = {};
+        // values, and, where the pair of the slab a k-ray comes from arrives as a message, the buffer it arrives in.
+        // [2]: the pair of sf_render_view (SPEC §13), 2 width height values, allocated afresh when the frame's size changes
+        T* ray_img[3] = {};
+        T* ray_in[3] = {};
     };
 
     // The first n internal slots of every slab alias its scratch buffers while this lives (invariant at WORK_SLOT). The
@@ -1278,6 +1279,36 @@ public:
             const size_t bytes = (pr.second - pr.first) * sizeof(T);
             if (colour) std::memcpy(static_cast<T*>(colour) + pr.first, ray_stage_ + pr.first, bytes);
             if (transmittance) std::memcpy(static_cast<T*>(transmittance) + pr.first, ray_stage_ + NN + pr.first, bytes);
+        }
+    }
+    // ---- orthographic volume rendering from any direction (SPEC §13) ----------------------------------------------
+    void render_view(const sf_view_params* p) override {
+        SF_REQUIRE(p != nullptr, "null view params");
+        for (const double* v : {p->origin, p->du, p->dv, p->step})
+            for (int c = 0; c < 3; ++c) SF_REQUIRE(std::isfinite(v[c]), "the frame's vectors must be finite");
+        SF_REQUIRE(std::isfinite(p->sigma) && p->sigma >= 0.0, "sigma must be finite and >= 0");
+        SF_REQUIRE(p->width >= 1 && p->width <= 16384 && p->height >= 1 && p->height <= 16384,
+                   "width and height must be in 1 .. 16384");
+        SF_REQUIRE(p->samples >= 1 && p->samples <= 65536, "samples must be in 1 .. 65536");
+        check_field(p->dens);
+        SF_REQUIRE(p->emit >= -1 && p->emit < SF_NUM_FIELDS, "emit must be a field id, or -1 for none");
+        SF_HIP(hipSetDevice(device_));
+        op_view(*p);
+    }
+    // The whole image is on the slab the rays leave the grid from (a loopback context: its own last slab); a context
+    // without it writes nothing.
+    void render_view_read(void* colour, void* transmittance) override {
+        SF_REQUIRE(view_w_ > 0, "render_view_read before any render_view");
+        SF_HIP(hipSetDevice(device_));
+        const size_t WH = (size_t)view_w_ * view_h_;
+        for (int s = 0; s < L_; ++s) {
+            Slab& sl = slabs_[s];
+            if (!ray_leaves_here(s, view_high_)) continue;
+            if (colour) SF_HIP(hipMemcpyAsync(colour, sl.ray_img[2], WH * sizeof(T), hipMemcpyDeviceToHost, sl.cs));
+            if (transmittance)
+                SF_HIP(hipMemcpyAsync(transmittance, sl.ray_img[2] + WH, WH * sizeof(T), hipMemcpyDeviceToHost, sl.cs));
+            tr_op("render_view_out", sl, sl.cs, {{sl.ray_img[2], false, 0, nplanes_}});
+            SF_HIP(hipStreamSynchronize(sl.cs));
         }
     }
     void light(int dst, int dens, int axis, int from_high, double sigma) override {
@@ -3301,19 +3332,11 @@ private:
         SF_HIP(hipGetLastError());
     }
 
-    // One march over the owned planes of every slab, on its compute stream. Rays along i and j stay inside a plane: the
-    // slabs run side by side and each writes the pixel rows of its planes. Rays along k cross the slabs in visit order:
-    // a slab starts from the image pair the one before it left — read in place when that slab is in this process, a
-    // message otherwise (to self through the communicator with SF_FLAG_RCCL_SELF) — so the chain has P stages. At the
-    // end every compute stream has waited for the last stage: the next march may overwrite any pair.
-    void op_rays(int mode, int axis, int high, double sigma, int dens, int emit, int dst) {
-        const int w = mode == sfk::RAY_FIELD ? 1 : 0;
-        const size_t cnt = 2 * (size_t)N_ * N_;
-        const bool chain = axis == 2 && P_ > 1;
+    // The image pair [w] of every slab (cnt values) and, where the pair of the slab before it arrives as a message, the
+    // buffer it arrives in: allocated on first use, as zeros.
+    void ray_buffers(int w, size_t cnt, bool chain, int high) {
         for (int s = 0; s < L_; ++s) {
             Slab& sl = slabs_[s];
-            for (int f : {dens, emit, dst})
-                if (f >= 0) ensure(sl, f);
             for (T** buf : {&sl.ray_img[w], (chain && ray_side(s, high ? 1 : 0) == TR_MSG) ? &sl.ray_in[w] : nullptr}) {
                 if (!buf || *buf) continue;
                 *buf = own_.dev<T>(cnt * sizeof(T));
@@ -3321,29 +3344,27 @@ private:
                 SF_HIP(hipDeviceSynchronize());  // (as alloc_field: the streams do not order against the null stream)
             }
         }
-        join();
-        const T h = T(1) / (T)N_;
+    }
+
+    // One march over every slab, on its compute stream: march(sl, in) launches it and traces it; `in` is the image pair
+    // the march starts from (null: the rays start here). Without a chain the slabs run side by side. With one the rays
+    // cross the slabs in visit order (downwards when `high`): a slab starts from the pair [w] (cnt values) the one before
+    // it left — read in place when that slab is in this process, a message otherwise (to self through the communicator
+    // with SF_FLAG_RCCL_SELF) — so the chain has P stages. At the end every compute stream has waited for the last
+    // stage: the next march may overwrite any pair.
+    template <class MarchF>
+    void ray_chain(int w, size_t cnt, bool chain, int high, MarchF march) {
         const ncclDataType_t dt = sizeof(T) == 4 ? ncclFloat : ncclDouble;
-        const int kb = G_, ke = G_ + nzl_;
-        const char* names[3][3] = {{"render_i", "render_j", "render_k"},
-                                   {"render_emit_i", "render_emit_j", "render_emit_k"},
-                                   {"light_i", "light_j", "light_k"}};
         for (int n = 0; n < L_; ++n) {
-            const int s = (chain && high) ? L_ - 1 - n : n;  // k-rays from the high side visit the slabs downwards
+            const int s = (chain && high) ? L_ - 1 - n : n;  // rays from the high side visit the slabs downwards
             Slab& sl = slabs_[s];
-            sfk::RayArgs<T> A{};
-            A.dens = sl.field[dens];
-            A.emit = emit >= 0 ? sl.field[emit] : nullptr;
-            A.dst = dst >= 0 ? sl.field[dst] : nullptr;
-            A.img = sl.ray_img[w];
-            A.s = (T)sigma * h;
-            A.from_high = high;
+            const T* in = nullptr;
             if (chain) {
                 const int from = high ? 1 : 0, side = ray_side(s, from);
                 Slab* prev = (high ? s < L_ - 1 : s > 0) ? &slabs_[s + (high ? 1 : -1)] : nullptr;
                 if (side != TR_NONE && prev) st_wait(sl, sl.cs, *prev, &Slab::cs_mark);
                 if (side == TR_LOCAL) {
-                    A.in = prev->ray_img[w];
+                    in = prev->ray_img[w];
                 } else if (side == TR_MSG) {
                     SF_NCCL(ncclGroupStart());
                     if (prev) {  // SF_FLAG_RCCL_SELF: the pair (send from the slab the rays left, receive here)
@@ -3359,21 +3380,10 @@ private:
                         if (prev) acc.push_back({prev->ray_img[w], false, 0, nplanes_});
                         tr_op(prev ? "rays_carry_rccl_self" : "rays_carry_recv", sl, sl.cs, acc);
                     }
-                    A.in = sl.ray_in[w];
+                    in = sl.ray_in[w];
                 }
             }
-            switch (mode) {
-                case sfk::RAY_IMAGE: launch_rays<sfk::RAY_IMAGE>(sl, axis, high, A); break;
-                case sfk::RAY_IMAGE_EMIT: launch_rays<sfk::RAY_IMAGE_EMIT>(sl, axis, high, A); break;
-                default: launch_rays<sfk::RAY_FIELD>(sl, axis, high, A); break;
-            }
-            if (trace_) {
-                std::vector<Acc> acc{{A.dens, false, kb, ke}, {A.img, true, 0, nplanes_}};
-                if (A.emit) acc.push_back({A.emit, false, kb, ke});
-                if (A.dst) acc.push_back({A.dst, true, kb, ke});
-                if (A.in) acc.push_back({A.in, false, 0, nplanes_});
-                tr_op(names[mode][axis], sl, sl.cs, acc);
-            }
+            march(sl, in);
             if (!chain) continue;
             if (L_ > 1) ev_record(sl, &Slab::cs_mark, sl.cs);
             if (nranks_ > 1 && !loopback_ && !ray_leaves_here(s, high) && tr_side(s, high ? 0 : 1) == TR_MSG) {
@@ -3389,6 +3399,95 @@ private:
             for (Slab& sl : slabs_)
                 if (&sl != &last) st_wait(sl, sl.cs, last, &Slab::cs_mark);
         }
+    }
+
+    // The marches of §12. Rays along i and j stay inside a plane: the slabs run side by side and each writes the pixel
+    // rows of its planes. Rays along k go through the chain.
+    void op_rays(int mode, int axis, int high, double sigma, int dens, int emit, int dst) {
+        const int w = mode == sfk::RAY_FIELD ? 1 : 0;
+        const size_t cnt = 2 * (size_t)N_ * N_;
+        const bool chain = axis == 2 && P_ > 1;
+        for (Slab& sl : slabs_)
+            for (int f : {dens, emit, dst})
+                if (f >= 0) ensure(sl, f);
+        ray_buffers(w, cnt, chain, high);
+        join();
+        const T h = T(1) / (T)N_;
+        const int kb = G_, ke = G_ + nzl_;
+        const char* names[3][3] = {{"render_i", "render_j", "render_k"},
+                                   {"render_emit_i", "render_emit_j", "render_emit_k"},
+                                   {"light_i", "light_j", "light_k"}};
+        ray_chain(w, cnt, chain, high, [&](Slab& sl, const T* in) {
+            sfk::RayArgs<T> A{};
+            A.dens = sl.field[dens];
+            A.emit = emit >= 0 ? sl.field[emit] : nullptr;
+            A.dst = dst >= 0 ? sl.field[dst] : nullptr;
+            A.img = sl.ray_img[w];
+            A.s = (T)sigma * h;
+            A.from_high = high;
+            A.in = in;
+            switch (mode) {
+                case sfk::RAY_IMAGE: launch_rays<sfk::RAY_IMAGE>(sl, axis, high, A); break;
+                case sfk::RAY_IMAGE_EMIT: launch_rays<sfk::RAY_IMAGE_EMIT>(sl, axis, high, A); break;
+                default: launch_rays<sfk::RAY_FIELD>(sl, axis, high, A); break;
+            }
+            if (trace_) {
+                std::vector<Acc> acc{{A.dens, false, kb, ke}, {A.img, true, 0, nplanes_}};
+                if (A.emit) acc.push_back({A.emit, false, kb, ke});
+                if (A.dst) acc.push_back({A.dst, true, kb, ke});
+                if (A.in) acc.push_back({A.in, false, 0, nplanes_});
+                tr_op(names[mode][axis], sl, sl.cs, acc);
+            }
+        });
+    }
+
+    // The march of §13: every slab applies the samples it owns of every ray, in the chain's order — upwards when
+    // T(step_z) >= 0, downwards otherwise. A sample reads the planes k0 and k0 + 1: the slab's interior planes, the
+    // ghost plane above them and, on slab 0, the shell plane below (all current after every operator, §10).
+    void op_view(const sf_view_params& p) {
+        const int mode = p.emit >= 0 ? sfk::RAY_IMAGE_EMIT : sfk::RAY_IMAGE;
+        const size_t cnt = 2 * (size_t)p.width * p.height;
+        const bool chain = P_ > 1;
+        const int high = (T)p.step[2] < T(0) ? 1 : 0;
+        for (Slab& sl : slabs_)
+            for (int f : {p.dens, p.emit})
+                if (f >= 0) ensure(sl, f);
+        if (cnt != view_cnt_) {  // another size: the device is done with the old pairs before they go
+            for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+            for (Slab& sl : slabs_) {
+                own_.release(sl.ray_img[2]);
+                own_.release(sl.ray_in[2]);
+            }
+            view_cnt_ = cnt;
+            view_w_ = view_h_ = 0;  // no image to read until this render has been issued
+        }
+        ray_buffers(2, cnt, chain, high);
+        join();
+        const int kb = G_, ke = G_ + nzl_;
+        const unsigned tiles = (unsigned)(ceil_div(p.width, 8) * ceil_div(p.height, 8));
+        ray_chain(2, cnt, chain, high, [&](Slab& sl, const T* in) {
+            sfk::ViewArgs<T> A{};
+            A.dens = sl.field[p.dens];
+            A.emit = p.emit >= 0 ? sl.field[p.emit] : nullptr;
+            A.in = in;
+            A.img = sl.ray_img[2];
+            for (int c = 0; c < 3; ++c) A.o[c] = (T)p.origin[c], A.du[c] = (T)p.du[c], A.dv[c] = (T)p.dv[c], A.ds[c] = (T)p.step[c];
+            A.s = (T)p.sigma * (T(1) / (T)N_);
+            A.width = p.width, A.height = p.height, A.samples = p.samples;
+            if (mode == sfk::RAY_IMAGE_EMIT)
+                hipLaunchKernelGGL((sfk::view_march_kernel<T, sfk::RAY_IMAGE_EMIT>), dim3(tiles), dim3(64), 0, sl.cs, sl.geom, A);
+            else
+                hipLaunchKernelGGL((sfk::view_march_kernel<T, sfk::RAY_IMAGE>), dim3(tiles), dim3(64), 0, sl.cs, sl.geom, A);
+            SF_HIP(hipGetLastError());
+            if (trace_) {
+                const int lo = sl.geom.wall_lo ? kb - 1 : kb;
+                std::vector<Acc> acc{{A.dens, false, lo, ke + 1}, {A.img, true, 0, nplanes_}};
+                if (A.emit) acc.push_back({A.emit, false, lo, ke + 1});
+                if (A.in) acc.push_back({A.in, false, 0, nplanes_});
+                tr_op(A.emit ? "render_view_emit" : "render_view", sl, sl.cs, acc);
+            }
+        });
+        view_w_ = p.width, view_h_ = p.height, view_high_ = high;
     }
 
     // Communicator guard: destroyed before own_ (declared after it), so before the streams its calls were issued on.
@@ -3455,6 +3554,8 @@ private:
                                     // cg_scalars_kernel folds (any context with check_every_ >= 1)
     T* ray_stage_ = nullptr;         // pinned: the image pair on its way to the caller (sf_render_read)
     int ray_axis_ = -1, ray_high_ = 0;  // view of the last sf_render (-1: none yet)
+    size_t view_cnt_ = 0;                     // values of the image pair of sf_render_view now allocated
+    int view_w_ = 0, view_h_ = 0, view_high_ = 0;  // frame of the last sf_render_view (width 0: none yet)
     sfk::CgState<T>* cg_state_ = nullptr;       // device: the scalars of a CG solve (check_every_ >= 1)
     sfk::CgState<T>* cg_state_host_ = nullptr;  // pinned: its mirror, filled by cg_state_read()
 };

@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "sf_set_pressure_preconditioner", "sf_pressure_preconditioner_get",
     "sf_set_pressure_multigrid", "sf_pressure_multigrid_get", "sf_precondition",
     "sf_render", "sf_render_read", "sf_light",
+    "sf_render_view", "sf_render_view_read", "sf_view_frame",
 )
 
 
@@ -91,6 +92,13 @@ class SfPressureMultigrid(C.Structure):
 class SfRenderParams(C.Structure):
     """sf_render_params of include/sfgpu.h (docs/SPEC.md §12)."""
     _fields_ = [("axis", C.c_int), ("from_high", C.c_int), ("sigma", C.c_double), ("dens", C.c_int), ("emit", C.c_int)]
+
+
+class SfViewParams(C.Structure):
+    """sf_view_params of include/sfgpu.h (docs/SPEC.md §13)."""
+    _fields_ = [("origin", C.c_double * 3), ("du", C.c_double * 3), ("dv", C.c_double * 3), ("step", C.c_double * 3),
+                ("width", C.c_int), ("height", C.c_int), ("samples", C.c_int), ("sigma", C.c_double),
+                ("dens", C.c_int), ("emit", C.c_int)]
 
 
 _ctx = C.c_void_p
@@ -141,6 +149,10 @@ lib.sf_precondition.argtypes = [_ctx, C.c_int, C.c_int]
 lib.sf_render.argtypes = [_ctx, C.POINTER(SfRenderParams)]
 lib.sf_render_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
 lib.sf_light.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
+lib.sf_render_view.argtypes = [_ctx, C.POINTER(SfViewParams)]
+lib.sf_render_view_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
+lib.sf_view_frame.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double,
+                              C.c_double, C.POINTER(SfViewParams)]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -427,6 +439,32 @@ class FluidSolver:
         """dst = the transmittance of the ray along axis in front of every cell (1 on the first cell visited), then
         set_bnd(0, dst): what render takes as `emit` for self-shadowed smoke. dst must not be dens."""
         self._ck(lib.sf_light(self._h, _fid(dst), _fid(dens), int(axis), int(from_high), float(sigma)))
+
+    # -- orthographic volume rendering from any direction (docs/SPEC.md §13) ----------------------
+    def view_frame(self, dir, up=(0.0, 0.0, 1.0), width=256, height=256, step=1.0, sigma=1.0):
+        """The SfViewParams of sf_view_frame for this grid: a width x height image looking along `dir` ((x, y, z) =
+        (i, j, k)) with `up` as the vertical, samples `step` cells apart, extinction `sigma` per unit length."""
+        f = SfViewParams()
+        st = lib.sf_view_frame(self.N, (C.c_double * 3)(*map(float, dir)), (C.c_double * 3)(*map(float, up)), int(width),
+                               int(height), float(step), float(sigma), C.byref(f))
+        if st != SF_OK:
+            raise SfError(st, "sf_view_frame: a zero or non-finite dir, up parallel to dir, step not > 0 or too small, "
+                              "sigma < 0, or width / height outside 1 .. 16384")
+        return f
+
+    def render_view(self, frame, dens="dens", emit=None):
+        """One ray per pixel of the frame (an SfViewParams: view_frame, or filled by hand) through the density slot
+        `dens` and the emission slot `emit` (None: none), trilinear samples composited front to back. Returns (colour,
+        transmittance), each shaped (height, width); zeros where this context does not hold the image. Collective on
+        several ranks; waits for the image."""
+        p = SfViewParams.from_buffer_copy(frame)
+        p.dens = _fid(dens)
+        p.emit = -1 if emit is None else _fid(emit)
+        self._ck(lib.sf_render_view(self._h, C.byref(p)))
+        colour = np.zeros((p.height, p.width), self.np_dtype)
+        trans = np.zeros((p.height, p.width), self.np_dtype)
+        self._ck(lib.sf_render_view_read(self._h, colour.ctypes.data_as(C.c_void_p), trans.ctypes.data_as(C.c_void_p)))
+        return colour, trans
 
     def set_iters(self, iters):
         self._ck(lib.sf_set_iters(self._h, int(iters)))

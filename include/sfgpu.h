@@ -362,6 +362,38 @@ int sf_render(sf_ctx* ctx, const sf_render_params* p);
 int sf_render_read(sf_ctx* ctx, void* colour, void* transmittance);
 int sf_light(sf_ctx* ctx, int dst, int dens, int axis, int from_high, double sigma);
 
+/* Orthographic volume rendering from any direction (docs/SPEC.md §13): a width x height image of parallel rays. The
+ * frame is in grid-index coordinates (the centre of cell i is at x = i), vectors ordered (x, y, z) = (i, j, k); every
+ * double is converted to the context's dtype T once. Sample n (0 <= n < samples) of pixel (a, b) is at
+ *     x = ((origin + T(a) * du) + T(b) * dv) + T(n) * step        per component, from n afresh,
+ * and is visited iff 0.5 <= x <= N + 0.5 holds for all three components (a NaN component: not visited). The visited
+ * samples of a pixel are composited front to back, in increasing n, with the recurrence of sf_render on the trilinear
+ * sample of dens (and of emit) at the position and s = T(sigma) * h; a sample that is not visited leaves (C, Tr) alone,
+ * so a ray that misses the box ends at exactly (+0, 1). The bits are the same for every decomposition, transport and
+ * launch geometry and equal the numpy reference tests/render_view_ref.py.
+ *   sf_render_view: asynchronous; writes no field and changes no later step by a bit; issues no halo exchange (ghost
+ *       planes are current after every operator and upload). Collective on several ranks: each slab applies the samples
+ *       whose lower plane k0 it owns and hands the (C, Tr) pair on, upwards if T(step[2]) >= 0 and downwards otherwise.
+ *       The view has an image pair of its own: a view render does not touch the image of sf_render.
+ *   sf_render_view_read: waits for the last sf_render_view, then writes C (colour) and Tr (transmittance) into dense
+ *       width * height arrays of T, pixel (a, b) at a + width * b; either pointer may be NULL. The whole image is on the
+ *       context that owns the last slab visited; other contexts write nothing. A loopback context renders its own planes
+ *       only.
+ *   sf_view_frame: host only. The frame that looks along dir with up as the vertical, on an image plane that spans the
+ *       box's bounding sphere: pixel pitch sqrt(3) N / max(width, height), samples `step` apart from the sphere's near
+ *       side to its far side, sigma scaled by step (so sigma stays the extinction per cell length). dens and emit are
+ *       left at -1 for the caller. All double arithmetic, bracketed as SPEC §13 writes it.
+ * SF_ERR_INVALID: a NULL pointer, a double that is not finite, sigma < 0, width or height outside 1 .. 16384, samples
+ * outside 1 .. 65536, a slot out of range, sf_render_view_read before any sf_render_view; in sf_view_frame also N < 1,
+ * a zero dir, up parallel to dir, step not > 0, or a step that gives more than 65536 samples. An SF_USER slot not yet
+ * used is allocated (zeros) first, as elsewhere. */
+typedef struct sf_view_params { double origin[3], du[3], dv[3], step[3]; int width, height, samples;
+                                double sigma; int dens, emit; } sf_view_params;   /* emit = -1: none */
+int sf_render_view(sf_ctx* ctx, const sf_view_params* p);
+int sf_render_view_read(sf_ctx* ctx, void* colour, void* transmittance);
+int sf_view_frame(int N, const double dir[3], const double up[3], int width, int height, double step,
+                  double sigma, sf_view_params* out);
+
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);
 int sf_set_coefficients(sf_ctx* ctx, double dt, double diff, double visc);

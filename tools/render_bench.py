@@ -15,7 +15,13 @@ process:
   step_ms               vel_step + dens_step per step, host wall time of --steps steps after a sync
   render1 / render10    the same loop with light + render + read after every step / every 10th step, and its share
 
+--view times sf_render_view of docs/SPEC.md §13 instead: a 512 x 512 sf_view_frame image per case, for the directions
+(0,0,1) (up (0,1,0)), (1,2,3) and (1,1,0), steps 1 and 0.5, without and with an emission field: ms per call and ns per
+visited sample (counted exactly in numpy at N <= 256, else N^3 / (pix^2 step)). Yardsticks in the same process: sf_advect
+of the density (the eight-gather kernel) and sf_render along k, both in ns per cell.
+
   python tools/render_bench.py                          # 64^3, 128^3, 256^3, 512^3 fp32 and 256^3 fp64
+  python tools/render_bench.py --view                   # 256^3, 512^3 fp32 and 256^3 fp64
   python tools/render_bench.py --cases 256:f32 --reps 5 # one case (e.g. under rocprofv3 --kernel-trace --stats)
 """
 import argparse
@@ -124,15 +130,64 @@ def time_case(N, dtype, reps, steps):
     return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in out.items()}
 
 
+VIEW_DIRS = [((0, 0, 1), (0, 1, 0)), ((1, 2, 3), (0, 0, 1)), ((1, 1, 0), (0, 0, 1))]
+
+
+def visited_samples(N, T, f):
+    """The number of visited samples of frame f (an SfViewParams) in the arithmetic of §13."""
+    a = np.arange(f.width).astype(T)[None, :]
+    b = np.arange(f.height).astype(T)[:, None]
+    base = [((T(f.origin[c]) + a * T(f.du[c])) + b * T(f.dv[c])).astype(T) for c in range(3)]
+    lo, hi, total = T(0.5), T(N) + T(0.5), 0
+    for n in range(f.samples):
+        vis = np.ones(base[0].shape, bool)
+        for c in range(3):
+            x = base[c] + T(n) * T(f.step[c])
+            vis &= (x >= lo) & (x <= hi)
+        total += int(np.count_nonzero(vis))
+    return total
+
+
+def time_view_case(N, dtype, reps, size=512):
+    S, fs = make(N, dtype)
+    T = fs.np_dtype
+    out = {"grid": N, "dtype": dtype, "image": size, "reps": reps}
+    cells = float(N) ** 3
+    adv = device_ms(fs, lambda: fs.advect(0, "dens0", "dens", "u", "v", "w"), reps)
+    rp = S.SfRenderParams(axis=2, from_high=0, sigma=SIGMA, dens=S.FIELD_IDS["dens"], emit=-1)
+    rk = device_ms(fs, lambda: S.lib.sf_render(fs._h, C.byref(rp)), reps)
+    out.update(advect_ms=adv, advect_ns_per_cell=adv * 1e6 / cells, render_k_ms=rk, render_k_ns_per_cell=rk * 1e6 / cells)
+    for d, up in VIEW_DIRS:
+        for step in (1.0, 0.5):
+            f = fs.view_frame(d, up, size, size, step, SIGMA)
+            pix = 3.0 ** 0.5 * N / size
+            n = visited_samples(N, T, f) if N <= 256 else cells / (pix * pix * step)
+            for emit, tag in ((-1, "view"), (S.FIELD_IDS["dens0"], "view_emit")):
+                f.dens, f.emit = S.FIELD_IDS["dens"], emit
+                ms = device_ms(fs, lambda: S.lib.sf_render_view(fs._h, C.byref(f)), reps)
+                key = f"{tag}_{''.join(map(str, d))}_s{step}"
+                out[key + "_ms"] = ms
+                out[key + "_ns_per_sample"] = ms * 1e6 / n
+                if emit < 0:
+                    out[key + "_over_advect"] = (ms * 1e6 / n) / (adv * 1e6 / cells)
+            out[f"samples_{''.join(map(str, d))}_s{step}"] = int(n)
+    fs.close()
+    return {k: (round(v, 5) if isinstance(v, float) else v) for k, v in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", nargs="+", default=["64:f32", "128:f32", "256:f32", "512:f32", "256:f64"])
+    ap.add_argument("--view", action="store_true", help="time sf_render_view (SPEC §13) instead")
+    ap.add_argument("--cases", nargs="+", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--steps", type=int, default=20)
     a = ap.parse_args()
+    if a.cases is None:
+        a.cases = ["256:f32", "512:f32", "256:f64"] if a.view else ["64:f32", "128:f32", "256:f32", "512:f32", "256:f64"]
     for c in a.cases:
         n, t = c.split(":")
-        print(json.dumps(time_case(int(n), t, a.reps, a.steps)), flush=True)
+        out = time_view_case(int(n), t, a.reps) if a.view else time_case(int(n), t, a.reps, a.steps)
+        print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":
