@@ -1,8 +1,11 @@
 """Reads the kernel-resource remarks of one compile (hipcc -Rpass-analysis=kernel-resource-usage, stderr kept in a file),
-prints what is not a remark (warnings), and checks the instantiations of sfk::view_march_kernel against the limits of
-docs/SPEC.md §13: no scratch, no LDS, no AGPRs, at most 128 VGPRs (four waves per SIMD resident). Prints their table."""
+prints what is not a remark (warnings), and checks the instantiations of sfk::view_march_kernel (docs/SPEC.md §13) and
+sfk::camera_march_kernel (§14) against the limits of §13: no scratch, no LDS, no AGPRs, at most 128 VGPRs (four waves
+per SIMD resident). Prints their table."""
 import re
 import sys
+
+GATHER_KERNELS = ("view_march_kernel", "camera_march_kernel")
 
 LIMITS = {"VGPRs": 128, "AGPRs": 0, "ScratchSize [bytes/lane]": 0, "LDS Size [bytes/block]": 0, "VGPRs Spill": 0}
 
@@ -25,9 +28,10 @@ def main(path):
             other.append(line)
     other = [ln for ln in other if not ln.startswith("In file included from")]
     sys.stderr.writelines(ln for ln in other if not re.match(r"\d+ (warning|remark)s? generated", ln.strip()) or "warning" in ln)
-    view = {k: v for k, v in kernels.items() if "view_march_kernel" in k}
-    if not view:
-        sys.exit(f"{path}: no view_march_kernel among {len(kernels)} kernels")
+    view = {k: v for k, v in kernels.items() if any(name in k for name in GATHER_KERNELS)}
+    for name in GATHER_KERNELS:
+        if not any(name in k for k in view):
+            sys.exit(f"{path}: no {name} among {len(kernels)} kernels")
     bad = 0
     for name, r in sorted(view.items()):
         print(f"  {name}: VGPRs {r.get('VGPRs')} AGPRs {r.get('AGPRs')} SGPRs {r.get('TotalSGPRs')} scratch "

@@ -316,6 +316,73 @@ int sf_view_frame(int N, const double dir[3], const double up[3], int width, int
     *out = f;
     return SF_OK;
 }
+int sf_render_camera(sf_ctx* ctx, const sf_camera_params* p) {
+    return guarded(ctx, [&](SolverBase& s) { s.render_camera(p); });
+}
+int sf_camera_passes_get(const sf_camera_params* p, int dtype, int* passes) {
+    if (!p || !passes || (dtype != SF_F32 && dtype != SF_F64)) return SF_ERR_INVALID;
+    if (p->view.width < 1 || p->view.width > 16384 || p->view.height < 1 || p->view.height > 16384) return SF_ERR_INVALID;
+    for (const double* v : {p->view.origin, p->view.du, p->view.dv, p->view.step, p->step_du, p->step_dv})
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(v[c])) return SF_ERR_INVALID;
+    int out = 0;
+    const bool ok = dtype == SF_F32 ? camera_corner_rule<float>(*p, &out) : camera_corner_rule<double>(*p, &out);
+    if (!ok) return SF_ERR_INVALID;
+    *passes = out;
+    return SF_OK;
+}
+// docs/SPEC.md §14: double arithmetic, + - * / sqrt only, bracketed as written
+int sf_camera_frame(int N, const double eye[3], const double target[3], const double up[3], double tan_half_fov,
+                    int width, int height, double step, double sigma, sf_camera_params* out) {
+    if (!eye || !target || !up || !out || N < 1) return SF_ERR_INVALID;
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(eye[c]) || !std::isfinite(target[c]) || !std::isfinite(up[c])) return SF_ERR_INVALID;
+    if (!std::isfinite(step) || !(step > 0.0) || !std::isfinite(sigma) || sigma < 0.0) return SF_ERR_INVALID;
+    if (!std::isfinite(tan_half_fov) || !(tan_half_fov > 0.0)) return SF_ERR_INVALID;
+    if (width < 1 || width > 16384 || height < 1 || height > 16384) return SF_ERR_INVALID;
+    auto len = [](const double* v) { return std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); };
+    auto cross = [](const double* a, const double* b, double* o) {
+        o[0] = a[1] * b[2] - a[2] * b[1], o[1] = a[2] * b[0] - a[0] * b[2], o[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double f[3], d[3], r[3], u[3], e[3], q0[3];
+    for (int c = 0; c < 3; ++c) f[c] = target[c] - eye[c];
+    const double lf = len(f);
+    if (!(lf > 0.0) || !std::isfinite(lf)) return SF_ERR_INVALID;
+    for (int c = 0; c < 3; ++c) d[c] = f[c] / lf;
+    cross(d, up, r);
+    const double lr = len(r);
+    if (!(lr > 0.0) || !std::isfinite(lr)) return SF_ERR_INVALID;
+    for (int c = 0; c < 3; ++c) r[c] = r[c] / lr;
+    cross(r, d, u);
+    const double R = std::sqrt(3.0) * N / 2.0, cen = (N + 1) / 2.0;
+    for (int c = 0; c < 3; ++c) e[c] = cen - eye[c];
+    const double dc = (e[0] * d[0] + e[1] * d[1]) + e[2] * d[2];
+    double t0 = dc - R;
+    if (!(t0 > 0.0)) t0 = 0.0;
+    const double t1 = dc + R;
+    if (!(t1 > t0)) return SF_ERR_INVALID;  // the box lies behind the camera
+    if (!((t1 - t0) / step < 65536.0)) return SF_ERR_INVALID;  // samples would leave 1 .. 65536
+    const double pp = (2.0 * tan_half_fov) / height;
+    sf_camera_params k{};
+    for (int c = 0; c < 3; ++c) {
+        q0[c] = (d[c] - r[c] * (pp * ((width - 1) / 2.0))) - u[c] * (pp * ((height - 1) / 2.0));
+        k.view.origin[c] = eye[c] + q0[c] * t0;
+        k.view.du[c] = r[c] * (pp * t0);
+        k.view.dv[c] = u[c] * (pp * t0);
+        k.view.step[c] = q0[c] * step;
+        k.step_du[c] = r[c] * (pp * step);
+        k.step_dv[c] = u[c] * (pp * step);
+    }
+    k.view.width = width, k.view.height = height;
+    k.view.samples = (int)((t1 - t0) / step) + 1;
+    k.view.sigma = sigma;
+    k.view.dens = k.view.emit = -1;
+    for (const double* v : {k.view.origin, k.view.du, k.view.dv, k.view.step, k.step_du, k.step_dv})
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(v[c])) return SF_ERR_INVALID;
+    *out = k;
+    return SF_OK;
+}
 int sf_set_iters(sf_ctx* ctx, int iters) {
     return guarded(ctx, [&](SolverBase& s) { s.set_iters(iters); });
 }

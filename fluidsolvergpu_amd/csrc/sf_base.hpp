@@ -38,6 +38,28 @@ inline int env_int(const char* name, int dflt) {
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
+// The corner rule of docs/SPEC.md §14 in T (host arithmetic, compiled without contraction: the device's r_z in bits).
+// r_z = (step_z + T(a) step_du_z) + T(b) step_dv_z is monotone in a and in b, so its extremes over the image lie at the
+// four corner pixels: all >= 0 is one upward chain, all < 0 one downward chain, else both. False where a corner's step
+// vector or origin is not finite in T (then *passes is not written).
+template <class T>
+inline bool camera_corner_rule(const sf_camera_params& p, int* passes) {
+    int ups = 0;
+    for (int corner = 0; corner < 4; ++corner) {
+        const T a = (T)((corner & 1) ? p.view.width - 1 : 0), b = (T)((corner & 2) ? p.view.height - 1 : 0);
+        T rz = T(0);
+        for (int c = 0; c < 3; ++c) {
+            const T r = ((T)p.view.step[c] + a * (T)p.step_du[c]) + b * (T)p.step_dv[c];
+            const T o = ((T)p.view.origin[c] + a * (T)p.view.du[c]) + b * (T)p.view.dv[c];
+            if (!std::isfinite(r) || !std::isfinite(o)) return false;
+            rz = r;
+        }
+        ups += rz < T(0) ? 0 : 1;
+    }
+    *passes = ups == 4 ? SF_CAMERA_UP : ups == 0 ? SF_CAMERA_DOWN : SF_CAMERA_BOTH;
+    return true;
+}
+
 class SolverBase {
 public:
     virtual ~SolverBase() {}
@@ -101,6 +123,7 @@ public:
     virtual void light(int dst, int dens, int axis, int from_high, double sigma) = 0;
     virtual void render_view(const sf_view_params* p) = 0;
     virtual void render_view_read(void* colour, void* transmittance) = 0;
+    virtual void render_camera(const sf_camera_params* p) = 0;
 };
 
 SolverBase* make_solver_f32(const sf_params& p);

@@ -27,7 +27,7 @@
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
 //             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
-//             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--help]
+//             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]] [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -62,6 +62,11 @@
 // format, written by the process that holds the image (the last rank for DZ >= 0, else rank 0). up is (0,0,1), or (0,1,0)
 // when the direction is parallel to k. SIGMA >= 0 is the extinction per unit length, STEP > 0 the sample distance in
 // cells (default 1).
+// --render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]: at every output step a W x H pinhole image of the density
+// from the eye E towards the target T, both in (i, j, k) with the centre of cell i at i (docs/SPEC.md §14, the frame of
+// sf_camera_frame), "camera_<frame, 4 digits>.pgm" in the same PGM format, written by the process that holds the image
+// (the last rank if every ray climbs, sf_camera_passes_get; else rank 0). up is (0,0,1), or (0,1,0) for a camera that looks
+// along k. FOV_DEG is the vertical field of view (default 40), STEP > 0 the sample distance in depth (default 1).
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -108,6 +113,9 @@ struct Options {
     bool view = false;  // --render-view
     double view_dir[3] = {0, 0, 1}, view_sigma = 0.0, view_step = 1.0;
     int view_w = 0, view_h = 0;
+    bool camera = false;  // --render-camera
+    double cam_eye[3] = {0, 0, 0}, cam_target[3] = {0, 0, 1}, cam_sigma = 0.0, cam_fov = 40.0, cam_step = 1.0;
+    int cam_w = 0, cam_h = 0;
     bool f64 = false, binary = false, plumbing = false, quiet = false, sync_output = false, loopback = false;
     std::string out = ".";
     int rank = 0, world = 1, local_rank = 0;
@@ -183,6 +191,7 @@ static void usage(FILE* to) {
             "                 [--pressure-sync M] [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]]\n"
             "                 [--render VIEW:SIGMA[:LIGHT]]   VIEW, LIGHT: i+ i- j+ j- k+ k- (+ enters at the low index)\n"
             "                 [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]]   an image along any direction, STEP in cells (default 1)\n"
+            "                 [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]   a pinhole camera at E looking at T\n"
             "                 [--loopback --rank R --world W] [--help]\n");
 }
 
@@ -229,6 +238,40 @@ static bool parse_render_view(const std::string& spec, Options& o) {
     if (!parse_double(part[2], o.view_sigma) || o.view_sigma < 0.0) return false;
     o.view_step = 1.0;
     if (part.size() == 4 && (!parse_double(part[3], o.view_step) || !(o.view_step > 0.0))) return false;
+    return true;
+}
+
+// X,Y,Z as three finite doubles
+static bool parse_triple(const std::string& v, double out[3]) {
+    const size_t c1 = v.find(','), c2 = c1 == std::string::npos ? c1 : v.find(',', c1 + 1);
+    if (c2 == std::string::npos || v.find(',', c2 + 1) != std::string::npos) return false;
+    return parse_double(v.substr(0, c1), out[0]) && parse_double(v.substr(c1 + 1, c2 - c1 - 1), out[1]) &&
+           parse_double(v.substr(c2 + 1), out[2]);
+}
+// the vertical of --render-camera: k, or j for a camera that looks along k
+static void camera_up(const Options& o, double up[3]) {
+    const bool along_k = o.cam_eye[0] == o.cam_target[0] && o.cam_eye[1] == o.cam_target[1];
+    up[0] = 0.0, up[1] = along_k ? 1.0 : 0.0, up[2] = along_k ? 0.0 : 1.0;
+}
+// EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]] into the camera members of o
+static bool parse_render_camera(const std::string& spec, Options& o) {
+    std::vector<std::string> part;
+    for (size_t at = 0;;) {
+        const size_t c = spec.find(':', at);
+        part.push_back(spec.substr(at, c == std::string::npos ? c : c - at));
+        if (c == std::string::npos) break;
+        at = c + 1;
+    }
+    if (part.size() < 4 || part.size() > 6) return false;
+    if (!parse_triple(part[0], o.cam_eye) || !parse_triple(part[1], o.cam_target)) return false;
+    if (o.cam_eye[0] == o.cam_target[0] && o.cam_eye[1] == o.cam_target[1] && o.cam_eye[2] == o.cam_target[2]) return false;
+    const size_t x = part[2].find('x');
+    if (x == std::string::npos || !parse_extent(part[2].substr(0, x), o.cam_w) || !parse_extent(part[2].substr(x + 1), o.cam_h))
+        return false;
+    if (!parse_double(part[3], o.cam_sigma) || o.cam_sigma < 0.0) return false;
+    o.cam_fov = 40.0, o.cam_step = 1.0;
+    if (part.size() >= 5 && (!parse_double(part[4], o.cam_fov) || !(o.cam_fov > 0.0) || !(o.cam_fov < 180.0))) return false;
+    if (part.size() == 6 && (!parse_double(part[5], o.cam_step) || !(o.cam_step > 0.0))) return false;
     return true;
 }
 
@@ -363,6 +406,15 @@ static Options parse(int argc, char** argv) {
             if (!o.view) {
                 fprintf(stderr, "--render-view takes DX,DY,DZ:WxH:SIGMA[:STEP] (a direction that is not zero, W and H in 1 .. 16384, "
                                 "SIGMA >= 0, STEP > 0), not %s\n", spec.c_str());
+                exit(2);
+            }
+        }
+        else if (s == "--render-camera") {
+            const std::string spec = next();
+            o.camera = parse_render_camera(spec, o);  // (whether the box is in front of the camera depends on --n: when the run starts)
+            if (!o.camera) {
+                fprintf(stderr, "--render-camera takes EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]] (an eye and a target that differ, W "
+                                "and H in 1 .. 16384, SIGMA >= 0, 0 < FOV_DEG < 180, STEP > 0), not %s\n", spec.c_str());
                 exit(2);
             }
         }
@@ -615,6 +667,23 @@ static int run(const Options& o) {
         view_mine = o.loopback || o.rank == ((sizeof(T) == 4 ? (double)(float)vp.step[2] : vp.step[2]) < 0.0 ? 0 : o.world - 1);
     }
     std::vector<T> view_colour(o.view ? (size_t)o.view_w * o.view_h : 0);
+    // --render-camera: the frame for this N; the image ends on the rank sf_camera_passes_get names (up: the last, else 0)
+    sf_camera_params cp{};
+    bool camera_mine = false;
+    if (o.camera) {
+        double up[3];
+        camera_up(o, up);
+        int passes = SF_CAMERA_UP;
+        if (sf_camera_frame(o.n, o.cam_eye, o.cam_target, up, std::tan(o.cam_fov * (M_PI / 360.0)), o.cam_w, o.cam_h, o.cam_step,
+                            o.cam_sigma, &cp) != SF_OK ||
+            sf_camera_passes_get(&cp, sizeof(T) == 4 ? SF_F32 : SF_F64, &passes) != SF_OK) {
+            fprintf(stderr, "--render-camera: no frame for this camera, step and grid size (is the box behind the camera?)\n");
+            exit(2);
+        }
+        cp.view.dens = SF_DENS;
+        camera_mine = o.loopback || o.rank == (passes == SF_CAMERA_UP ? o.world - 1 : 0);
+    }
+    std::vector<T> camera_colour(o.camera ? (size_t)o.cam_w * o.cam_h : 0);
     // forces (SPEC §8): added by every vel_step to copies of the bound sources
     SF_CHECK_RETURN(sf_set_vorticity_confinement(g_ctx, o.vorticity));
     SF_CHECK_RETURN(sf_set_buoyancy(g_ctx, o.buoyancy, o.ambient, o.buoyancy_axis));
@@ -738,6 +807,15 @@ static int run(const Options& o) {
                     char name[64];
                     snprintf(name, sizeof name, "/view_%04d.pgm", frame);
                     write_pgm<T>(o.out + name, view_colour, o.view_w, 0, o.view_h);
+                }
+            }
+            if (o.camera) {
+                SF_CHECK_RETURN(sf_render_camera(g_ctx, &cp));
+                SF_CHECK_RETURN(sf_render_view_read(g_ctx, camera_colour.data(), nullptr));
+                if (camera_mine) {
+                    char name[64];
+                    snprintf(name, sizeof name, "/camera_%04d.pgm", frame);
+                    write_pgm<T>(o.out + name, camera_colour, o.cam_w, 0, o.cam_h);
                 }
             }
             if (ntr > 0) fetch_tracers();

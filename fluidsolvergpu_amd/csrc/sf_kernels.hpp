@@ -3707,4 +3707,92 @@ __global__ void __launch_bounds__(64) view_march_kernel(Geom g, ViewArgs<T> A) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Perspective volume rendering (docs/SPEC.md §14): the march of §13 with a step vector per pixel,
+// r = (ds + T(a) dsu) + T(b) dsv, so that the rays of a pinhole camera fan out. What §13's kernel holds in scalar
+// registers — the step, the opacity scalar and the sign each bisection takes — is per lane here; the position is still
+// base + T(n) r from n afresh, so view_range, the predicate and the trip are §13's. The rays of one image may cross the
+// slabs in both directions: `pass` names the pixels this launch applies (SF_CAMERA_UP: r_z >= 0, SF_CAMERA_DOWN:
+// r_z < 0, SF_CAMERA_BOTH: all); the others get an empty range of n and carry their pair from `in` to `img` untouched.
+// `in` may be `img` (the first slab of a downward pass that follows an upward one): a lane reads and writes its own
+// pixel only, and a lane past the image edge, which reads a clamped pixel, stores nothing.
+enum { CAMERA_UP = 0, CAMERA_DOWN = 1, CAMERA_BOTH = 2 };  // = sf_camera_passes of sfgpu.h
+template <class T>
+struct CameraArgs {
+    const T* dens;
+    const T* emit;  // RAY_IMAGE_EMIT only
+    const T* in;    // the (C, Tr) pair the march starts from; null: the rays start here
+    T* img;         // as ViewArgs::img
+    T o[3], du[3], dv[3], ds[3], dsu[3], dsv[3];
+    T sh;           // T(sigma) * h: the extinction per cell length, to be scaled by |r| per pixel
+    int width, height, samples, pass;
+};
+
+// (the trip is §13's VIEW_U in all four instantiations: they stay within 128 VGPRs, see check_resources.py)
+template <class T, int MODE>
+__global__ void __launch_bounds__(64) camera_march_kernel(Geom g, CameraArgs<T> A) {
+    static_assert(MODE == RAY_IMAGE || MODE == RAY_IMAGE_EMIT, "the image forms");
+    constexpr int U = VIEW_U<T>;
+    const int tw = (A.width + 7) >> 3;
+    const int ty = (int)blockIdx.x / tw, tx = (int)blockIdx.x - ty * tw;
+    const int a = 8 * tx + ((int)threadIdx.x & 7), b = 8 * ty + ((int)threadIdx.x >> 3);
+    const bool live = a < A.width && b < A.height;
+    const int ac = a < A.width ? a : A.width - 1, bc = b < A.height ? b : A.height - 1;
+    const T lo = T(0.5), hi = (T)g.N + T(0.5);
+    const int klo = g.kg0 + g.G;
+    const T zlo = klo == 1 ? lo : (T)klo, zhx = (T)(klo + g.nzl);
+    const T fa = (T)ac, fb = (T)bc;
+    const T px = (A.o[0] + fa * A.du[0]) + fb * A.dv[0];
+    const T py = (A.o[1] + fa * A.du[1]) + fb * A.dv[1];
+    const T pz = (A.o[2] + fa * A.du[2]) + fb * A.dv[2];
+    const T rx = (A.ds[0] + fa * A.dsu[0]) + fb * A.dsv[0];
+    const T ry = (A.ds[1] + fa * A.dsu[1]) + fb * A.dsv[1];
+    const T rz = (A.ds[2] + fa * A.dsu[2]) + fb * A.dsv[2];
+    const T s = A.sh * sqrt((rx * rx + ry * ry) + rz * rz);  // correctly rounded (no fast-math, no rsqrt)
+    int n0 = 0, n1 = A.samples;
+    view_range(A.samples, px, rx, lo, hi, n0, n1);
+    view_range(A.samples, py, ry, lo, hi, n0, n1);
+    view_range(A.samples, pz, rz, zlo, zhx < hi ? zhx : hi, n0, n1);
+    const bool down = rz < T(0);
+    if (A.pass != CAMERA_BOTH && down != (A.pass == CAMERA_DOWN)) n1 = n0;
+    const long WH = (long)A.width * A.height;
+    const long pix = ac + (long)A.width * bc;
+    T C = T(0), Tr = T(1);
+    if (A.in != nullptr) {
+        C = A.in[pix];
+        Tr = A.in[WH + pix];
+    }
+    for (int n = n0; n < n1; n += U) {
+        bool on[U];
+        TriSampleDev<T> S[U];
+        T cd[U][8], ce[MODE == RAY_IMAGE_EMIT ? U : 1][8];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T fn = (T)(n + u);
+            const T x = px + fn * rx, y = py + fn * ry, z = pz + fn * rz;
+            on[u] = (n + u < n1) & (x >= lo) & (x <= hi) & (y >= lo) & (y <= hi) & (z >= lo) & (z <= hi) & (z >= zlo) & (z < zhx);
+            S[u] = TriSampleDev<T>(g, x, y, z, true);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            S[u].load(A.dens, cd[u]);
+            if constexpr (MODE == RAY_IMAGE_EMIT) S[u].load(A.emit, ce[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const T d = S[u].combine(cd[u]);
+            T e = T(0);
+            if constexpr (MODE == RAY_IMAGE_EMIT) e = S[u].combine(ce[u]);
+            T Cn = C, Trn = Tr;
+            ray_step<T, MODE>(ray_opacity(s, d), e, Cn, Trn);
+            C = on[u] ? Cn : C;
+            Tr = on[u] ? Trn : Tr;
+        }
+    }
+    if (live) {
+        A.img[pix] = C;
+        A.img[WH + pix] = Tr;
+    }
+}
+
 }  // namespace sfk

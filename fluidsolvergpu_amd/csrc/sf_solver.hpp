@@ -1282,7 +1282,7 @@ public:
         }
     }
     // ---- orthographic volume rendering from any direction (SPEC §13) ----------------------------------------------
-    void render_view(const sf_view_params* p) override {
+    void check_view(const sf_view_params* p) {
         SF_REQUIRE(p != nullptr, "null view params");
         for (const double* v : {p->origin, p->du, p->dv, p->step})
             for (int c = 0; c < 3; ++c) SF_REQUIRE(std::isfinite(v[c]), "the frame's vectors must be finite");
@@ -1292,8 +1292,22 @@ public:
         SF_REQUIRE(p->samples >= 1 && p->samples <= 65536, "samples must be in 1 .. 65536");
         check_field(p->dens);
         SF_REQUIRE(p->emit >= -1 && p->emit < SF_NUM_FIELDS, "emit must be a field id, or -1 for none");
+    }
+    void render_view(const sf_view_params* p) override {
+        check_view(p);
         SF_HIP(hipSetDevice(device_));
         op_view(*p);
+    }
+    // ---- perspective volume rendering (SPEC §14): into the image pair of §13, read by render_view_read --------------
+    void render_camera(const sf_camera_params* p) override {
+        SF_REQUIRE(p != nullptr, "null camera params");
+        check_view(&p->view);
+        for (const double* v : {p->step_du, p->step_dv})
+            for (int c = 0; c < 3; ++c) SF_REQUIRE(std::isfinite(v[c]), "the frame's vectors must be finite");
+        int passes = 0;
+        SF_REQUIRE(camera_corner_rule<T>(*p, &passes), "a corner pixel's step vector or origin is not finite in the context's dtype");
+        SF_HIP(hipSetDevice(device_));
+        op_camera(*p, passes);
     }
     // The whole image is on the slab the rays leave the grid from (a loopback context: its own last slab); a context
     // without it writes nothing.
@@ -3351,9 +3365,11 @@ private:
     // cross the slabs in visit order (downwards when `high`): a slab starts from the pair [w] (cnt values) the one before
     // it left — read in place when that slab is in this process, a message otherwise (to self through the communicator
     // with SF_FLAG_RCCL_SELF) — so the chain has P stages. At the end every compute stream has waited for the last
-    // stage: the next march may overwrite any pair.
+    // stage: the next march may overwrite any pair. With `resume` a slab that has nobody to receive from starts from
+    // the pair [w] it holds itself (the second pass of §14, after a chain the other way ended there) and march() reads
+    // and writes that one buffer.
     template <class MarchF>
-    void ray_chain(int w, size_t cnt, bool chain, int high, MarchF march) {
+    void ray_chain(int w, size_t cnt, bool chain, int high, MarchF march, bool resume = false) {
         const ncclDataType_t dt = sizeof(T) == 4 ? ncclFloat : ncclDouble;
         for (int n = 0; n < L_; ++n) {
             const int s = (chain && high) ? L_ - 1 - n : n;  // rays from the high side visit the slabs downwards
@@ -3381,6 +3397,8 @@ private:
                         tr_op(prev ? "rays_carry_rccl_self" : "rays_carry_recv", sl, sl.cs, acc);
                     }
                     in = sl.ray_in[w];
+                } else if (resume) {
+                    in = sl.ray_img[w];
                 }
             }
             march(sl, in);
@@ -3441,6 +3459,18 @@ private:
         });
     }
 
+    // The image pair [2] holds cnt values from here on: a pair of another size goes, once the device is done with it.
+    void view_resize(size_t cnt) {
+        if (cnt == view_cnt_) return;
+        for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
+        for (Slab& sl : slabs_) {
+            own_.release(sl.ray_img[2]);
+            own_.release(sl.ray_in[2]);
+        }
+        view_cnt_ = cnt;
+        view_w_ = view_h_ = 0;  // no image to read until this render has been issued
+    }
+
     // The march of §13: every slab applies the samples it owns of every ray, in the chain's order — upwards when
     // T(step_z) >= 0, downwards otherwise. A sample reads the planes k0 and k0 + 1: the slab's interior planes, the
     // ghost plane above them and, on slab 0, the shell plane below (all current after every operator, §10).
@@ -3452,15 +3482,7 @@ private:
         for (Slab& sl : slabs_)
             for (int f : {p.dens, p.emit})
                 if (f >= 0) ensure(sl, f);
-        if (cnt != view_cnt_) {  // another size: the device is done with the old pairs before they go
-            for (Slab& sl : slabs_) SF_HIP(hipStreamSynchronize(sl.cs));
-            for (Slab& sl : slabs_) {
-                own_.release(sl.ray_img[2]);
-                own_.release(sl.ray_in[2]);
-            }
-            view_cnt_ = cnt;
-            view_w_ = view_h_ = 0;  // no image to read until this render has been issued
-        }
+        view_resize(cnt);
         ray_buffers(2, cnt, chain, high);
         join();
         const int kb = G_, ke = G_ + nzl_;
@@ -3488,6 +3510,59 @@ private:
             }
         });
         view_w_ = p.width, view_h_ = p.height, view_high_ = high;
+    }
+
+    // The march of §14 into the pair of §13. The corner rule names the chains: one, as §13's, when every pixel's rays
+    // climb or every pixel's descend; else an upward chain that applies the up pixels and a downward one, resumed from
+    // the pair the upward chain left on the last slab, that applies the down pixels. Either hands the whole pair on.
+    // Without a chain (one slab) a single launch applies every pixel.
+    void op_camera(const sf_camera_params& c, int passes) {
+        const sf_view_params& p = c.view;
+        const int mode = p.emit >= 0 ? sfk::RAY_IMAGE_EMIT : sfk::RAY_IMAGE;
+        const size_t cnt = 2 * (size_t)p.width * p.height;
+        const bool chain = P_ > 1;
+        for (Slab& sl : slabs_)
+            for (int f : {p.dens, p.emit})
+                if (f >= 0) ensure(sl, f);
+        view_resize(cnt);
+        for (int high = 0; high < 2; ++high)
+            if (passes == SF_CAMERA_BOTH || passes == high) ray_buffers(2, cnt, chain, high);
+        join();
+        const int kb = G_, ke = G_ + nzl_;
+        const unsigned tiles = (unsigned)(ceil_div(p.width, 8) * ceil_div(p.height, 8));
+        static const char* names[2][3] = {{"render_camera_up", "render_camera_down", "render_camera_both"},
+                                          {"render_camera_emit_up", "render_camera_emit_down", "render_camera_emit_both"}};
+        for (int high = 0; high < 2; ++high) {
+            if (passes != SF_CAMERA_BOTH && passes != high) continue;
+            const int pass = !chain ? (int)sfk::CAMERA_BOTH : passes == SF_CAMERA_BOTH ? high : (int)sfk::CAMERA_BOTH;
+            ray_chain(2, cnt, chain, high, [&](Slab& sl, const T* in) {
+                sfk::CameraArgs<T> A{};
+                A.dens = sl.field[p.dens];
+                A.emit = p.emit >= 0 ? sl.field[p.emit] : nullptr;
+                A.in = in;
+                A.img = sl.ray_img[2];
+                for (int x = 0; x < 3; ++x) {
+                    A.o[x] = (T)p.origin[x], A.du[x] = (T)p.du[x], A.dv[x] = (T)p.dv[x], A.ds[x] = (T)p.step[x];
+                    A.dsu[x] = (T)c.step_du[x], A.dsv[x] = (T)c.step_dv[x];
+                }
+                A.sh = (T)p.sigma * (T(1) / (T)N_);
+                A.width = p.width, A.height = p.height, A.samples = p.samples, A.pass = pass;
+                if (mode == sfk::RAY_IMAGE_EMIT)
+                    hipLaunchKernelGGL((sfk::camera_march_kernel<T, sfk::RAY_IMAGE_EMIT>), dim3(tiles), dim3(64), 0, sl.cs, sl.geom, A);
+                else
+                    hipLaunchKernelGGL((sfk::camera_march_kernel<T, sfk::RAY_IMAGE>), dim3(tiles), dim3(64), 0, sl.cs, sl.geom, A);
+                SF_HIP(hipGetLastError());
+                if (trace_) {
+                    const int lo = sl.geom.wall_lo ? kb - 1 : kb;
+                    std::vector<Acc> acc{{A.dens, false, lo, ke + 1}, {A.img, true, 0, nplanes_}};
+                    if (A.emit) acc.push_back({A.emit, false, lo, ke + 1});
+                    if (A.in) acc.push_back({A.in, false, 0, nplanes_});  // (the resumed stage: the buffer just named)
+                    tr_op(names[A.emit ? 1 : 0][pass], sl, sl.cs, acc);
+                }
+            }, chain && passes == SF_CAMERA_BOTH && high == 1);
+            if (!chain) break;  // one slab: the single launch has applied every pixel
+        }
+        view_w_ = p.width, view_h_ = p.height, view_high_ = passes == SF_CAMERA_UP ? 0 : 1;
     }
 
     // Communicator guard: destroyed before own_ (declared after it), so before the streams its calls were issued on.

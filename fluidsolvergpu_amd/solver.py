@@ -6,6 +6,7 @@ module has no fallback: if the library is missing the import fails, and if no MI
 `FluidSolver(...)` raises SfError(SF_ERR_NO_DEVICE).
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -53,6 +54,7 @@ ABI_SYMBOLS = (
     "sf_set_pressure_multigrid", "sf_pressure_multigrid_get", "sf_precondition",
     "sf_render", "sf_render_read", "sf_light",
     "sf_render_view", "sf_render_view_read", "sf_view_frame",
+    "sf_render_camera", "sf_camera_passes_get", "sf_camera_frame",
 )
 
 
@@ -100,6 +102,14 @@ class SfViewParams(C.Structure):
                 ("width", C.c_int), ("height", C.c_int), ("samples", C.c_int), ("sigma", C.c_double),
                 ("dens", C.c_int), ("emit", C.c_int)]
 
+
+class SfCameraParams(C.Structure):
+    """sf_camera_params of include/sfgpu.h (docs/SPEC.md §14)."""
+    _fields_ = [("view", SfViewParams), ("step_du", C.c_double * 3), ("step_dv", C.c_double * 3)]
+
+
+SF_CAMERA_UP, SF_CAMERA_DOWN, SF_CAMERA_BOTH = 0, 1, 2
+CAMERA_PASSES = ("up", "down", "both")
 
 _ctx = C.c_void_p
 lib.sf_version.restype = C.c_char_p
@@ -153,6 +163,10 @@ lib.sf_render_view.argtypes = [_ctx, C.POINTER(SfViewParams)]
 lib.sf_render_view_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
 lib.sf_view_frame.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double,
                               C.c_double, C.POINTER(SfViewParams)]
+lib.sf_render_camera.argtypes = [_ctx, C.POINTER(SfCameraParams)]
+lib.sf_camera_passes_get.argtypes = [C.POINTER(SfCameraParams), C.c_int, C.POINTER(C.c_int)]
+lib.sf_camera_frame.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(SfCameraParams)]
 lib.sf_set_iters.argtypes = [_ctx, C.c_int]
 lib.sf_set_coefficients.argtypes = [_ctx, C.c_double, C.c_double, C.c_double]
 lib.sf_sync.argtypes = [_ctx]
@@ -463,6 +477,43 @@ class FluidSolver:
         self._ck(lib.sf_render_view(self._h, C.byref(p)))
         colour = np.zeros((p.height, p.width), self.np_dtype)
         trans = np.zeros((p.height, p.width), self.np_dtype)
+        self._ck(lib.sf_render_view_read(self._h, colour.ctypes.data_as(C.c_void_p), trans.ctypes.data_as(C.c_void_p)))
+        return colour, trans
+
+    # -- perspective volume rendering (docs/SPEC.md §14) ------------------------------------------
+    def camera_frame(self, eye, target, up=(0.0, 0.0, 1.0), fov_y_deg=40.0, width=256, height=256, step=1.0, sigma=1.0):
+        """The SfCameraParams of sf_camera_frame for this grid: a pinhole camera at `eye` looking at `target` ((x, y, z)
+        = (i, j, k), the centre of cell i at x = i) with `up` as the vertical and a vertical field of view of fov_y_deg
+        degrees, samples `step` cells apart in depth, extinction `sigma` per cell length."""
+        f = SfCameraParams()
+        vec = lambda v: (C.c_double * 3)(*map(float, v))
+        st = lib.sf_camera_frame(self.N, vec(eye), vec(target), vec(up), math.tan(math.radians(float(fov_y_deg)) / 2.0),
+                                 int(width), int(height), float(step), float(sigma), C.byref(f))
+        if st != SF_OK:
+            raise SfError(st, "sf_camera_frame: eye == target, up parallel to the direction, a field of view or step not "
+                              "> 0, the box behind the camera, too many samples, sigma < 0, or width / height outside "
+                              "1 .. 16384")
+        return f
+
+    def camera_passes(self, frame):
+        """Which chains render_camera runs for the frame in this context's dtype: "up", "down" or "both"."""
+        out = C.c_int()
+        p = SfCameraParams.from_buffer_copy(frame)
+        st = lib.sf_camera_passes_get(C.byref(p), SF_F32 if self.np_dtype == np.float32 else SF_F64, C.byref(out))
+        if st != SF_OK:
+            raise SfError(st, "sf_camera_passes_get: a corner pixel's step vector or origin is not finite")
+        return CAMERA_PASSES[out.value]
+
+    def render_camera(self, frame, dens="dens", emit=None):
+        """One ray per pixel of the frame (an SfCameraParams: camera_frame, or filled by hand), as render_view with a
+        step vector per pixel. Returns (colour, transmittance), each shaped (height, width); zeros where this context
+        does not hold the image. Collective on several ranks; waits for the image."""
+        p = SfCameraParams.from_buffer_copy(frame)
+        p.view.dens = _fid(dens)
+        p.view.emit = -1 if emit is None else _fid(emit)
+        self._ck(lib.sf_render_camera(self._h, C.byref(p)))
+        colour = np.zeros((p.view.height, p.view.width), self.np_dtype)
+        trans = np.zeros((p.view.height, p.view.width), self.np_dtype)
         self._ck(lib.sf_render_view_read(self._h, colour.ctypes.data_as(C.c_void_p), trans.ctypes.data_as(C.c_void_p)))
         return colour, trans
 

@@ -375,7 +375,8 @@ int sf_light(sf_ctx* ctx, int dst, int dens, int axis, int from_high, double sig
  *       planes are current after every operator and upload). Collective on several ranks: each slab applies the samples
  *       whose lower plane k0 it owns and hands the (C, Tr) pair on, upwards if T(step[2]) >= 0 and downwards otherwise.
  *       The view has an image pair of its own: a view render does not touch the image of sf_render.
- *   sf_render_view_read: waits for the last sf_render_view, then writes C (colour) and Tr (transmittance) into dense
+ *   sf_render_view_read: waits for the last sf_render_view or sf_render_camera (below; they share the image pair and the
+ *       read returns the last image of either), then writes C (colour) and Tr (transmittance) into dense
  *       width * height arrays of T, pixel (a, b) at a + width * b; either pointer may be NULL. The whole image is on the
  *       context that owns the last slab visited; other contexts write nothing. A loopback context renders its own planes
  *       only.
@@ -393,6 +394,38 @@ int sf_render_view(sf_ctx* ctx, const sf_view_params* p);
 int sf_render_view_read(sf_ctx* ctx, void* colour, void* transmittance);
 int sf_view_frame(int N, const double dir[3], const double up[3], int width, int height, double step,
                   double sigma, sf_view_params* out);
+
+/* Perspective volume rendering (docs/SPEC.md §14): the frame of sf_render_view plus two vectors that make the step a
+ * function of the pixel, so that the rays of a pinhole camera fan out. Per component, in T,
+ *     r = (view.step + T(a) * step_du) + T(b) * step_dv          the step vector of pixel (a, b)
+ *     x = ((origin + T(a) * du) + T(b) * dv) + T(n) * r          sample n, from n afresh
+ * with the visited predicate, the trilinear sample, the recurrence and the untouched unvisited sample of §13. view.sigma
+ * is the extinction per cell length: the opacity scalar of a pixel is s = (T(sigma) * h) * sqrt((r_x r_x + r_y r_y) +
+ * r_z r_z), so samples spaced differently along different rays absorb alike. With step_du = step_dv = 0 the positions
+ * are sf_render_view's. The bits are the same for every decomposition, transport and launch geometry and equal the numpy
+ * reference tests/render_camera_ref.py.
+ *   sf_render_camera: asynchronous and collective, as sf_render_view; issues no halo exchange. A pixel is `down` iff
+ *       T(r_z) < 0 and `up` otherwise. r_z is monotone along the rows and columns of the image, so the four corner pixels
+ *       decide: all up or all down is one chain in that direction, as §13's; a mixed image takes an upward chain over all
+ *       slabs that applies the up pixels and then a downward chain, starting from the pair the upward one left on the last
+ *       slab, that applies the down pixels. It writes into the image pair of sf_render_view: sf_render_view_read returns
+ *       the last image of either call, on the context that owns the last slab visited (mixed: slab 0). Nothing of it
+ *       reaches the graph cache.
+ *   sf_camera_passes_get: host only. The corner rule for dtype (SF_F32 / SF_F64): which chains sf_render_camera runs.
+ *   sf_camera_frame: host only. A pinhole camera at eye looking at target, up as the vertical, tan_half_fov the tangent
+ *       of half the vertical field of view. Sample n of every pixel lies at depth t0 + n * step along the viewing
+ *       direction, from where the bounding sphere of the box begins (or the eye, inside it) to where it ends. All double
+ *       arithmetic with + - * / sqrt only, bracketed as SPEC §14 writes it; sigma is passed through; dens and emit are
+ *       left at -1.
+ * SF_ERR_INVALID: what sf_render_view refuses; a corner pixel whose r or origin is not finite in T; a dtype that is
+ * neither SF_F32 nor SF_F64; in sf_camera_frame N < 1, eye == target, up parallel to the direction, tan_half_fov or step
+ * not > 0 (or not finite), a box behind the camera, more than 65536 samples. */
+typedef struct sf_camera_params { sf_view_params view; double step_du[3], step_dv[3]; } sf_camera_params;
+enum sf_camera_passes { SF_CAMERA_UP = 0, SF_CAMERA_DOWN = 1, SF_CAMERA_BOTH = 2 };
+int sf_render_camera(sf_ctx* ctx, const sf_camera_params* p);
+int sf_camera_passes_get(const sf_camera_params* p, int dtype, int* passes);
+int sf_camera_frame(int N, const double eye[3], const double target[3], const double up[3], double tan_half_fov,
+                    int width, int height, double step, double sigma, sf_camera_params* out);
 
 /* Run-time parameters (the reference only has compile-time #defines, FluidGPU.cuh:1-31). */
 int sf_set_iters(sf_ctx* ctx, int iters);

@@ -20,8 +20,16 @@ process:
 visited sample (counted exactly in numpy at N <= 256, else N^3 / (pix^2 step)). Yardsticks in the same process: sf_advect
 of the density (the eight-gather kernel) and sf_render along k, both in ns per cell.
 
+--camera times sf_render_camera of docs/SPEC.md §14 instead: a 512 x 512 sf_camera_frame image per case for three
+cameras that look along (1,2,3) — far (20 N from the centre, the field of view that just holds the bounding sphere:
+nearly parallel rays), near (1.5 N from the centre, 40 degrees) and inside (the eye in the box, 40 degrees) — steps 1 and
+0.5, without and with an emission field, each next to sf_render_view along the same direction in the same process: ms per
+call, ps per visited sample (counted in numpy in the arithmetic of §14 on every pixel at N <= 256 and on every fourth
+pixel each way, times 16, above), and the ratio of the camera's ps per visited sample to the view's.
+
   python tools/render_bench.py                          # 64^3, 128^3, 256^3, 512^3 fp32 and 256^3 fp64
   python tools/render_bench.py --view                   # 256^3, 512^3 fp32 and 256^3 fp64
+  python tools/render_bench.py --camera                 # 256^3, 512^3 fp32 and 256^3 fp64
   python tools/render_bench.py --cases 256:f32 --reps 5 # one case (e.g. under rocprofv3 --kernel-trace --stats)
 """
 import argparse
@@ -175,18 +183,78 @@ def time_view_case(N, dtype, reps, size=512):
     return {k: (round(v, 5) if isinstance(v, float) else v) for k, v in out.items()}
 
 
+CAMERA_DIR = (1.0, 2.0, 3.0)
+
+
+def camera_visited(N, T, v, step_du, step_dv, stride=1):
+    """The number of visited samples of a frame (v: its SfViewParams) in the arithmetic of §14, on every stride-th pixel
+    each way, times stride^2."""
+    a = np.arange(0, v.width, stride).astype(T)[None, :]
+    b = np.arange(0, v.height, stride).astype(T)[:, None]
+    base = [((T(v.origin[c]) + a * T(v.du[c])) + b * T(v.dv[c])).astype(T) for c in range(3)]
+    r = [((T(v.step[c]) + a * T(step_du[c])) + b * T(step_dv[c])).astype(T) for c in range(3)]
+    lo, hi, total = T(0.5), T(N) + T(0.5), 0
+    for n in range(v.samples):
+        vis = np.ones(base[0].shape, bool)
+        for c in range(3):
+            x = base[c] + T(n) * r[c]
+            vis &= (x >= lo) & (x <= hi)
+        total += int(np.count_nonzero(vis))
+    return total * stride * stride
+
+
+def time_camera_case(N, dtype, reps, size=512):
+    S, fs = make(N, dtype)
+    T = fs.np_dtype
+    out = {"grid": N, "dtype": dtype, "image": size, "reps": reps}
+    stride = 1 if N <= 256 else 4
+    d = np.array(CAMERA_DIR) / np.linalg.norm(CAMERA_DIR)
+    c = (N + 1) / 2.0
+    half = float(np.degrees(np.arctan((3.0 ** 0.5 * N / 2.0) / (20.0 * N))))
+    cameras = {"far": (c - 20.0 * N * d, 2.0 * half), "near": (c - 1.5 * N * d, 40.0), "inside": (c - 0.2 * N * d, 40.0)}
+    zero = (0.0, 0.0, 0.0)
+    for step in (1.0, 0.5):
+        v = fs.view_frame(CAMERA_DIR, (0, 0, 1), size, size, step, SIGMA)
+        nv = camera_visited(N, T, v, zero, zero, stride)
+        ortho = {}
+        for emit, tag in ((-1, "plain"), (S.FIELD_IDS["dens0"], "emit")):
+            v.dens, v.emit = S.FIELD_IDS["dens"], emit
+            ortho[tag] = device_ms(fs, lambda: S.lib.sf_render_view(fs._h, C.byref(v)), reps)
+            out[f"view_{tag}_s{step}_ms"] = ortho[tag]
+            out[f"view_{tag}_s{step}_ps_per_sample"] = ortho[tag] * 1e9 / nv
+        out[f"view_samples_s{step}"] = nv
+        for name, (eye, fov) in cameras.items():
+            f = fs.camera_frame(eye, (c, c, c), (0, 0, 1), fov, size, size, step, SIGMA)
+            n = camera_visited(N, T, f.view, f.step_du, f.step_dv, stride)
+            out[f"{name}_samples_s{step}"] = n
+            out[f"{name}_passes_s{step}"] = fs.camera_passes(f)
+            for emit, tag in ((-1, "plain"), (S.FIELD_IDS["dens0"], "emit")):
+                f.view.dens, f.view.emit = S.FIELD_IDS["dens"], emit
+                ms = device_ms(fs, lambda: S.lib.sf_render_camera(fs._h, C.byref(f)), reps)
+                key = f"{name}_{tag}_s{step}"
+                out[key + "_ms"] = ms
+                out[key + "_ps_per_sample"] = ms * 1e9 / n
+                out[key + "_over_view"] = (ms / n) / (ortho[tag] / nv)
+    fs.close()
+    return {k: (round(v, 5) if isinstance(v, float) else v) for k, v in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--view", action="store_true", help="time sf_render_view (SPEC §13) instead")
+    ap.add_argument("--camera", action="store_true", help="time sf_render_camera (SPEC §14) next to sf_render_view instead")
     ap.add_argument("--cases", nargs="+", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--steps", type=int, default=20)
     a = ap.parse_args()
     if a.cases is None:
-        a.cases = ["256:f32", "512:f32", "256:f64"] if a.view else ["64:f32", "128:f32", "256:f32", "512:f32", "256:f64"]
+        a.cases = ["256:f32", "512:f32", "256:f64"] if (a.view or a.camera) else ["64:f32", "128:f32", "256:f32", "512:f32", "256:f64"]
     for c in a.cases:
         n, t = c.split(":")
-        out = time_view_case(int(n), t, a.reps) if a.view else time_case(int(n), t, a.reps, a.steps)
+        if a.camera:
+            out = time_camera_case(int(n), t, a.reps)
+        else:
+            out = time_view_case(int(n), t, a.reps) if a.view else time_case(int(n), t, a.reps, a.steps)
         print(json.dumps(out), flush=True)
 
 
