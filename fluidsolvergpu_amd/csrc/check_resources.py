@@ -1,13 +1,18 @@
 """Reads the kernel-resource remarks of one compile (hipcc -Rpass-analysis=kernel-resource-usage, stderr kept in a file),
 prints what is not a remark (warnings), and checks the instantiations of sfk::view_march_kernel (docs/SPEC.md §13) and
 sfk::camera_march_kernel (§14) against the limits of §13: no scratch, no LDS, no AGPRs, at most 128 VGPRs (four waves
-per SIMD resident). Prints their table."""
+per SIMD resident), and the masked kernels of §15 against theirs: no scratch, no LDS, no AGPRs. Prints their table."""
 import re
 import sys
 
 GATHER_KERNELS = ("view_march_kernel", "camera_march_kernel")
 
 LIMITS = {"VGPRs": 128, "AGPRs": 0, "ScratchSize [bytes/lane]": 0, "LDS Size [bytes/block]": 0, "VGPRs Spill": 0}
+# the kernels of solid obstacles (docs/SPEC.md §15): row kernels next to unmasked siblings, held to the same absence of
+# scratch, AGPRs and LDS (their VGPRs are printed, not capped)
+MASKED_KERNELS = ("face_code_kernel", "cg_init_masked_kernel", "cg_apply_dot_masked_kernel", "project_div_masked_kernel",
+                  "project_sub_masked_kernel", "zero_solid_kernel")
+MASKED_LIMITS = {k: v for k, v in LIMITS.items() if k != "VGPRs"}
 
 
 def main(path):
@@ -28,19 +33,20 @@ def main(path):
             other.append(line)
     other = [ln for ln in other if not ln.startswith("In file included from")]
     sys.stderr.writelines(ln for ln in other if not re.match(r"\d+ (warning|remark)s? generated", ln.strip()) or "warning" in ln)
-    view = {k: v for k, v in kernels.items() if any(name in k for name in GATHER_KERNELS)}
-    for name in GATHER_KERNELS:
-        if not any(name in k for k in view):
-            sys.exit(f"{path}: no {name} among {len(kernels)} kernels")
     bad = 0
-    for name, r in sorted(view.items()):
-        print(f"  {name}: VGPRs {r.get('VGPRs')} AGPRs {r.get('AGPRs')} SGPRs {r.get('TotalSGPRs')} scratch "
-              f"{r.get('ScratchSize [bytes/lane]')} LDS {r.get('LDS Size [bytes/block]')} waves/SIMD "
-              f"{r.get('Occupancy [waves/SIMD]')}")
-        for key, cap in LIMITS.items():
-            if key not in r or int(r[key]) > cap:
-                print(f"    {key} = {r.get(key)} exceeds {cap}", file=sys.stderr)
-                bad += 1
+    for names, limits in ((GATHER_KERNELS, LIMITS), (MASKED_KERNELS, MASKED_LIMITS)):
+        view = {k: v for k, v in kernels.items() if any(name in k for name in names)}
+        for name in names:
+            if not any(name in k for k in view):
+                sys.exit(f"{path}: no {name} among {len(kernels)} kernels")
+        for name, r in sorted(view.items()):
+            print(f"  {name}: VGPRs {r.get('VGPRs')} AGPRs {r.get('AGPRs')} SGPRs {r.get('TotalSGPRs')} scratch "
+                  f"{r.get('ScratchSize [bytes/lane]')} LDS {r.get('LDS Size [bytes/block]')} waves/SIMD "
+                  f"{r.get('Occupancy [waves/SIMD]')}")
+            for key, cap in limits.items():
+                if key not in r or int(r[key]) > cap:
+                    print(f"    {key} = {r.get(key)} exceeds {cap}", file=sys.stderr)
+                    bad += 1
     sys.exit(1 if bad else 0)
 
 

@@ -260,6 +260,14 @@ int sf_pressure_multigrid_get(const sf_ctx* ctx, sf_pressure_multigrid* out) {
 int sf_precondition(sf_ctx* ctx, int z, int r) {
     return guarded(ctx, [&](SolverBase& s) { s.precondition(z, r); });
 }
+int sf_set_obstacles(sf_ctx* ctx, int mask_slot) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_obstacles(mask_slot); });
+}
+int sf_obstacles_get(const sf_ctx* ctx, sf_obstacles* out) {
+    if (!ctx || !ctx->impl || !out) return SF_ERR_INVALID;
+    ctx->impl->obstacles(out);
+    return SF_OK;
+}
 int sf_render(sf_ctx* ctx, const sf_render_params* p) {
     return guarded(ctx, [&](SolverBase& s) { s.render(p); });
 }

@@ -118,6 +118,8 @@ public:
     virtual void set_pressure_multigrid(int sweeps, int max_levels, int coarse_sweeps) = 0;
     virtual void pressure_multigrid(sf_pressure_multigrid* out) const = 0;
     virtual void precondition(int z, int r) = 0;
+    virtual void set_obstacles(int mask_slot) = 0;
+    virtual void obstacles(sf_obstacles* out) const = 0;
     virtual void render(const sf_render_params* p) = 0;
     virtual void render_read(void* colour, void* transmittance) = 0;
     virtual void light(int dst, int dens, int axis, int from_high, double sigma) = 0;

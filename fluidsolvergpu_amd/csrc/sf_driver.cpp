@@ -27,7 +27,8 @@
 //             [--vorticity EPS] [--buoyancy BETA] [--ambient A] [--buoyancy-axis 1] [--maccormack vel|dens|both]
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
 //             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
-//             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]] [--help]
+//             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]
+//             [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]... [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -49,6 +50,9 @@
 // --pressure-mg NU[:LEVELS[:COARSE]] (with --pressure cg): the multigrid V-cycle preconditioner of docs/SPEC.md §11.3 with
 // NU >= 1 sweeps per level, at most LEVELS levels (0, the default: as many as the grid allows) and COARSE >= 1 sweeps on
 // the coarsest (default 8). In force it takes the place of --pressure-precond.
+// --obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R (with --pressure cg, not with --pressure-mg; up to 16 times): solid
+// cells of docs/SPEC.md §15, in cell indices: the cells of the inclusive index box, or those whose centre index lies
+// within R of (CX, CY, CZ) — squared distance, in double, <= R^2. The union of all of them is the mask of sf_set_obstacles.
 // --render VIEW:SIGMA[:LIGHT]: at every output step an image of the density (docs/SPEC.md §12) next to the frame,
 // "render_<frame, 4 digits>.pgm" (several processes: "render_GPU<rank>_<frame>.pgm", each rank the pixel rows it holds).
 // VIEW and LIGHT are one of i+ i- j+ j- k+ k-: the axis of the rays and the side they enter from (+: at index 1). SIGMA
@@ -107,6 +111,11 @@ struct Options {
     int pressure = SF_PRESSURE_JACOBI, cg_max_iters = 100, cg_check_every = 0;
     int cg_precond = SF_PRECOND_NONE, cg_precond_sweeps = 0;
     int mg_sweeps = 0, mg_levels = 0, mg_coarse = 8;
+    struct Obstacle {
+        bool sphere;
+        double a[6];  // box: i0, j0, k0, i1, j1, k1; sphere: cx, cy, cz, r
+    };
+    std::vector<Obstacle> obstacles;  // --obstacle (docs/SPEC.md §15)
     double cg_tol = 1e-3;
     int render_axis = -1, render_high = 0, light_axis = -1, light_high = 0;  // --render (axis -1: off / no light)
     double render_sigma = 0.0;
@@ -192,7 +201,44 @@ static void usage(FILE* to) {
             "                 [--render VIEW:SIGMA[:LIGHT]]   VIEW, LIGHT: i+ i- j+ j- k+ k- (+ enters at the low index)\n"
             "                 [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]]   an image along any direction, STEP in cells (default 1)\n"
             "                 [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]   a pinhole camera at E looking at T\n"
+            "                 [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]...   solid cells (with --pressure cg), up to 16\n"
             "                 [--loopback --rank R --world W] [--help]\n");
+}
+
+// "a,b,c" -> three finite numbers (integers only if `whole`)
+static bool parse_triple(const std::string& s, bool whole, double* out) {
+    size_t at = 0;
+    for (int q = 0; q < 3; ++q) {
+        const size_t c = q < 2 ? s.find(',', at) : std::string::npos;
+        if (q < 2 && c == std::string::npos) return false;
+        const std::string part = s.substr(at, c == std::string::npos ? c : c - at);
+        char* end = nullptr;
+        out[q] = strtod(part.c_str(), &end);
+        if (part.empty() || *end != 0 || !std::isfinite(out[q])) return false;
+        if (whole && (out[q] != std::floor(out[q]) || std::fabs(out[q]) > 1e6)) return false;
+        at = c + 1;
+    }
+    return true;
+}
+
+// box:I0,J0,K0:I1,J1,K1 (whole indices, I0 <= I1 ...) | sphere:CX,CY,CZ:R (R >= 0)
+static bool parse_obstacle(const std::string& spec, Options::Obstacle& ob) {
+    const size_t c1 = spec.find(':'), c2 = c1 == std::string::npos ? c1 : spec.find(':', c1 + 1);
+    if (c2 == std::string::npos || spec.find(':', c2 + 1) != std::string::npos) return false;
+    const std::string kind = spec.substr(0, c1), first = spec.substr(c1 + 1, c2 - c1 - 1), second = spec.substr(c2 + 1);
+    if (kind == "box") {
+        ob.sphere = false;
+        if (!parse_triple(first, true, ob.a) || !parse_triple(second, true, ob.a + 3)) return false;
+        return ob.a[0] <= ob.a[3] && ob.a[1] <= ob.a[4] && ob.a[2] <= ob.a[5];
+    }
+    if (kind == "sphere") {
+        ob.sphere = true;
+        if (!parse_triple(first, false, ob.a)) return false;
+        char* end = nullptr;
+        ob.a[3] = strtod(second.c_str(), &end);
+        return !second.empty() && *end == 0 && std::isfinite(ob.a[3]) && ob.a[3] >= 0.0;
+    }
+    return false;
 }
 
 // "i+" .. "k-" -> axis 0..2 and from_high (+ enters at the low index)
@@ -375,6 +421,20 @@ static Options parse(int argc, char** argv) {
             o.mg_levels = (int)val[1];
             o.mg_coarse = (int)val[2];
         }
+        else if (s == "--obstacle") {
+            const std::string spec = next();
+            Options::Obstacle ob{};
+            if (!parse_obstacle(spec, ob)) {
+                fprintf(stderr, "--obstacle takes box:I0,J0,K0:I1,J1,K1 (whole cell indices, low <= high) or sphere:CX,CY,CZ:R "
+                                "(R >= 0), not %s\n", spec.c_str());
+                exit(2);
+            }
+            if (o.obstacles.size() >= 16) {
+                fprintf(stderr, "--obstacle may be given 16 times at most\n");
+                exit(2);
+            }
+            o.obstacles.push_back(ob);
+        }
         else if (s == "--render") {
             // VIEW:SIGMA[:LIGHT]
             const std::string spec = next();
@@ -473,6 +533,10 @@ static Options parse(int argc, char** argv) {
         fprintf(stderr, "--rank / --world need --loopback (ranks of a real run come from RANK / WORLD_SIZE)\n");
         exit(2);
     }
+    if (!o.obstacles.empty() && (o.pressure != SF_PRESSURE_CG || o.mg_sweeps > 0)) {
+        fprintf(stderr, "--obstacle needs --pressure cg and does not go with --pressure-mg (docs/SPEC.md §15)\n");
+        exit(2);
+    }
     // frames go to <out>/: create it (the reference writes into the working directory, which always exists)
     if (o.every > 0) {
         std::error_code ec;
@@ -510,6 +574,28 @@ static std::vector<T> make_input(int which, int N, int kb, int ke, double dt, bo
         if (which == 7) at(c, c, c) = T(100);
         if (which == 5) at(c, c, c) = plumbing ? T(5) : (T)A;
     }
+    return f;
+}
+
+// The mask of --obstacle on the global planes [kb, ke): 1 in the cells of any obstacle, 0 elsewhere (docs/SPEC.md §15).
+template <class T>
+static std::vector<T> make_mask(const Options& o, int kb, int ke) {
+    const int N = o.n;
+    const size_t S = (size_t)N + 2;
+    std::vector<T> f(S * S * (size_t)(ke - kb), T(0));
+    for (const Options::Obstacle& ob : o.obstacles)
+        for (int k = std::max(kb, 1); k < std::min(ke, N + 1); ++k)
+            for (int j = 1; j <= N; ++j)
+                for (int i = 1; i <= N; ++i) {
+                    bool in;
+                    if (ob.sphere) {
+                        const double dx = i - ob.a[0], dy = j - ob.a[1], dz = k - ob.a[2];
+                        in = (dx * dx + dy * dy) + dz * dz <= ob.a[3] * ob.a[3];
+                    } else {
+                        in = i >= ob.a[0] && i <= ob.a[3] && j >= ob.a[1] && j <= ob.a[4] && k >= ob.a[2] && k <= ob.a[5];
+                    }
+                    if (in) f[(size_t)i + S * ((size_t)j + S * (size_t)(k - kb))] = T(1);
+                }
     return f;
 }
 
@@ -632,6 +718,16 @@ static int run(const Options& o) {
     }
     for (int f : {SF_U, SF_V, SF_W}) SF_CHECK_RETURN(sf_set_bnd(g_ctx, f + 1, f));
     SF_CHECK_RETURN(sf_set_bnd(g_ctx, 0, SF_DENS));
+    // --obstacle: the mask goes through a slot that is scratch before the first step (every SF_USER slot is bound below)
+    // and is read there once
+    if (!o.obstacles.empty()) {
+        SF_CHECK_RETURN(sf_upload_planes(g_ctx, SF_DENS0, st_kb, st_ke, make_mask<T>(o, st_kb, st_ke).data()));
+        SF_CHECK_RETURN(sf_set_obstacles(g_ctx, SF_DENS0));
+        SF_CHECK_RETURN(sf_fill(g_ctx, SF_DENS0, 0.0));
+        sf_obstacles ob{};
+        SF_CHECK_RETURN(sf_obstacles_get(g_ctx, &ob));
+        if (o.rank == 0) std::cout << "obstacles: " << o.obstacles.size() << ", fluid cells " << ob.fluid_cells << "\n";
+    }
     // sources stay resident in HBM (SF_USER0..3) and are re-injected every step
     const int bound[4] = {SF_USER0, SF_USER1, SF_USER2, SF_USER3};
     SF_CHECK_RETURN(sf_bind_sources(g_ctx, bound[0], bound[1], bound[2], bound[3]));

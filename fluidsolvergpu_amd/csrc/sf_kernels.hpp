@@ -3243,6 +3243,317 @@ __global__ void __launch_bounds__(256) cg_direction_z_kernel(Geom g, CgArgs<T> A
     }
 }
 
+// ---- Solid obstacles (SPEC §15) ----
+// One rule: a closed neighbour reads as the cell itself. The mask is turned once into a per-cell face code (a small
+// integer stored as T: one bit per closed face of a fluid cell, FC_SOLID for a solid cell), so a masked kernel loads
+// one more vector per cell instead of seven mask values. Every masked kernel is a sibling of the unmasked one, with
+// its row shape and its sums; the unmasked kernels are untouched. Loads stay unconditional: the face rule is a select
+// on loaded values, so what a solid cell stores (a NaN included) is never an operand of a fluid cell.
+enum { FC_ILO = 1, FC_IHI = 2, FC_JLO = 4, FC_JHI = 8, FC_KLO = 16, FC_KHI = 32, FC_SOLID = 64 };
+
+// solid(c): mask[c] > 0 as T (NaN, -0 and negatives are fluid)
+template <class T>
+__device__ __forceinline__ bool fc_solid(T m) {
+    return m > T(0);
+}
+
+// The face codes of the slab's own planes from the mask, read at the seven points (ghost planes of the mask included;
+// shell cells are never solid, whatever the mask holds there). Row records: the fluid cells of the row, so that
+// n_fluid is a §10 sum (of integers: exact).
+template <class T>
+struct FaceCodeArgs {
+    const T* mask;
+    T* code;
+};
+template <class T>
+__global__ void __launch_bounds__(256) face_code_kernel(Geom g, FaceCodeArgs<T> A, double* __restrict__ rows, int npad) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    const T* __restrict__ mask = A.mask;
+    T* __restrict__ code = A.code;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const int kg = g.kg0 + kl;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    const bool jlo_in = j > 1, jhi_in = j < g.N, klo_in = kg > 1, khi_in = kg < g.N;
+    double cs = 0.0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V mc = ldv(mask + q);
+        const T mm = mask[q - 1], mp = mask[q + W];
+        const V jm = ldv(mask + q - g.px), jp = ldv(mask + q + g.px);
+        const V km = ldv(mask + q - g.plane), kp = ldv(mask + q + g.plane);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const int i = i0c + e;
+            const T left = (e == 0) ? mm : mc[e - 1];
+            const T right = (e == W - 1) ? mp : mc[e + 1];
+            int c = 0;
+            c |= (i > 1 && fc_solid(left)) ? FC_ILO : 0;
+            c |= (i < g.N && fc_solid(right)) ? FC_IHI : 0;
+            c |= (jlo_in && fc_solid(jm[e])) ? FC_JLO : 0;
+            c |= (jhi_in && fc_solid(jp[e])) ? FC_JHI : 0;
+            c |= (klo_in && fc_solid(km[e])) ? FC_KLO : 0;
+            c |= (khi_in && fc_solid(kp[e])) ? FC_KHI : 0;
+            const bool solid = fc_solid(mc[e]);
+            out[e] = (T)(solid ? (int)FC_SOLID : c);
+            cs = cs + ((e < nv && !solid) ? 1.0 : 0.0);
+        }
+        if (nv > 0) store_cells<T, W>(code, r, i0, out, nv);
+    }
+    const double rec = wave_fold(cs, FoldSum());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = rec;
+}
+
+// The argument of a masked CG row kernel: that of its sibling, and the face codes.
+template <class T>
+struct CgMaskArgs {
+    CgArgs<T> a;
+    const T* code;
+};
+
+// cg_init_kernel under a mask: r = div - mu on fluid cells, +0 on solid ones.
+template <class T, bool DEV = false>
+__global__ void __launch_bounds__(256) cg_init_masked_kernel(Geom g, CgMaskArgs<T> M, double* __restrict__ rows, int npad) {
+    constexpr int W = VecT<T>::W;
+    const CgArgs<T>& A = M.a;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const T mu = cg_scalar<DEV, CG_USE_MU>(A);
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    double cs = 0.0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type dv = ldv(A.div + r + i0c), cv = ldv(M.code + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const T v = dv[e] - mu;
+            out[e] = ((int)cv[e] & FC_SOLID) ? T(0) : v;
+            cs = cs + (e < nv ? (double)out[e] * (double)out[e] : 0.0);
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.r, r, i0, out, nv);
+            store_cells<T, W>(A.d, r, i0, out, nv);
+            emit_shells<T, W>(A.d, g, 0, i0, j, kl, out, nv);
+        }
+    }
+    const double rec = wave_fold(cs, FoldSum());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = rec;
+}
+
+// cg_stencil under a mask: the loads, the lane exchange and the wave-uniform seam cells of cg_stencil, then eff() as
+// selects on what was loaded; +0 on solid cells.
+template <class T, int W>
+__device__ __forceinline__ void cg_stencil_masked(const Geom& g, const T* __restrict__ x, const T* __restrict__ code, long r,
+                                                  int m, int i0, int i0c, typename VecT<T>::type& xc, T (&ax)[W]) {
+    typedef typename VecT<T>::type V;
+    const long q = r + i0c;
+    xc = ldv(x + q);
+    const V jm = ldv(x + q - g.px), jp = ldv(x + q + g.px);
+    const V km = ldv(x + q - g.plane), kp = ldv(x + q + g.plane);
+    const V cv = ldv(code + q);
+    const int first = 1 + 64 * W * m;
+    const int next = first + 64 * W;
+    const int end = next < g.N + 1 ? next : g.N + 1;
+    const T lo = x[r + first - 1], hi = x[r + end];
+    const int lane = (int)threadIdx.x & 63;
+    T left = lane_up(xc[W - 1]), right = lane_dn(xc[0]);
+    if (lane == 0) left = lo;
+    if (i0 + W == end) right = hi;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+        const int c = (int)cv[e];
+        const T self = xc[e];
+        T l = (e == 0) ? left : xc[e - 1];
+        T rt = (e == W - 1) ? right : xc[e + 1];
+        l = (c & FC_ILO) ? self : l;
+        rt = (c & FC_IHI) ? self : rt;
+        const T a = (c & FC_JLO) ? self : jm[e], b = (c & FC_JHI) ? self : jp[e];
+        const T d = (c & FC_KLO) ? self : km[e], f = (c & FC_KHI) ? self : kp[e];
+        const T v = T(6) * self - (((l + rt) + (a + b)) + (d + f));
+        ax[e] = (c & FC_SOLID) ? T(0) : v;
+    }
+}
+
+// cg_apply_dot_kernel under a mask. RES: e = div - A p on fluid cells, +0 on solid ones; div.div as stored.
+template <class T, bool RES, bool DEV = false>
+__global__ void __launch_bounds__(256) cg_apply_dot_masked_kernel(Geom g, CgMaskArgs<T> M, double* __restrict__ rows,
+                                                                  int npad) {
+    constexpr int W = VecT<T>::W;
+    const CgArgs<T>& A = M.a;
+    int j, p;
+    if (!cg_live<DEV>(A)) return;
+    if (!reduce_row(g, j, p)) return;
+    const long r = row0(g, j, g.G + p);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    const T* __restrict__ x = RES ? A.p : A.d;
+    double c0 = 0.0, c1 = 0.0;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        typename VecT<T>::type xc;
+        T ax[W];
+        cg_stencil_masked<T, W>(g, x, M.code, r, m, i0, i0c, xc, ax);
+        const int nv = cg_valid<W>(g, i0);
+        if constexpr (RES) {
+            const typename VecT<T>::type dv = ldv(A.div + r + i0c), cv = ldv(M.code + r + i0c);
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const T err = ((int)cv[e] & FC_SOLID) ? T(0) : dv[e] - ax[e];
+                c0 = c0 + (e < nv ? (double)err * (double)err : 0.0);
+                c1 = c1 + (e < nv ? (double)dv[e] * (double)dv[e] : 0.0);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < W; ++e) c0 = c0 + (e < nv ? (double)xc[e] * (double)ax[e] : 0.0);
+            if (nv > 0) store_cells<T, W>(A.q, r, i0, ax, nv);
+        }
+    }
+    const double rec0 = wave_fold(c0, FoldSum());
+    if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 0, p, j)] = rec0;
+    if constexpr (RES) {
+        const double rec1 = wave_fold(c1, FoldSum());
+        if (((int)threadIdx.x & 63) == 0) rows[rec_at(g, npad, 1, p, j)] = rec1;
+    }
+}
+
+// The two halves of project and the end of dens_step under a mask, in the row shape (no row records).
+template <class T>
+struct ProjectMaskArgs {
+    T* u;
+    T* v;
+    T* w;
+    T* p;       // sub: read; zero: the density, in place
+    T* div;     // div: written
+    const T* code;
+    T c_div, c_grad;
+};
+
+// div = c_div*(((effn(u,i+1) - effn(u,i-1)) + ...) + ...) on fluid cells, +0 on solid ones; set_bnd(0, div)
+template <class T>
+__global__ void __launch_bounds__(256) project_div_masked_kernel(Geom g, ProjectMaskArgs<T> A) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V uc = ldv(A.u + q), vc = ldv(A.v + q), wc = ldv(A.w + q), cv = ldv(A.code + q);
+        const T um = A.u[q - 1], up = A.u[q + W];
+        const V vm = ldv(A.v + q - g.px), vp = ldv(A.v + q + g.px);
+        const V wm = ldv(A.w + q - g.plane), wp = ldv(A.w + q + g.plane);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const int c = (int)cv[e];
+            T left = (e == 0) ? um : uc[e - 1];
+            T right = (e == W - 1) ? up : uc[e + 1];
+            left = (c & FC_ILO) ? -uc[e] : left;
+            right = (c & FC_IHI) ? -uc[e] : right;
+            const T a = (c & FC_JLO) ? -vc[e] : vm[e], b = (c & FC_JHI) ? -vc[e] : vp[e];
+            const T d = (c & FC_KLO) ? -wc[e] : wm[e], f = (c & FC_KHI) ? -wc[e] : wp[e];
+            const T val = A.c_div * (((right - left) + (b - a)) + (f - d));
+            out[e] = (c & FC_SOLID) ? T(0) : val;
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.div, r, i0, out, nv);
+            emit_shells<T, W>(A.div, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
+// u -= c_grad*(eff(p,i+1) - eff(p,i-1)) etc. on fluid cells, u = v = w = +0 on solid ones; the three set_bnd
+template <class T>
+__global__ void __launch_bounds__(256) project_sub_masked_kernel(Geom g, ProjectMaskArgs<T> A) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    const T* __restrict__ pr = A.p;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V pc = ldv(pr + q), cv = ldv(A.code + q);
+        const T pm = pr[q - 1], pp = pr[q + W];
+        const V pjm = ldv(pr + q - g.px), pjp = ldv(pr + q + g.px);
+        const V pkm = ldv(pr + q - g.plane), pkp = ldv(pr + q + g.plane);
+        const V uc = ldv(A.u + q), vc = ldv(A.v + q), wc = ldv(A.w + q);
+        const int nv = cg_valid<W>(g, i0);
+        T ou[W], ov[W], ow[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const int c = (int)cv[e];
+            const T self = pc[e];
+            T left = (e == 0) ? pm : pc[e - 1];
+            T right = (e == W - 1) ? pp : pc[e + 1];
+            left = (c & FC_ILO) ? self : left;
+            right = (c & FC_IHI) ? self : right;
+            const T a = (c & FC_JLO) ? self : pjm[e], b = (c & FC_JHI) ? self : pjp[e];
+            const T d = (c & FC_KLO) ? self : pkm[e], f = (c & FC_KHI) ? self : pkp[e];
+            const T nu = uc[e] - A.c_grad * (right - left);
+            const T nvv = vc[e] - A.c_grad * (b - a);
+            const T nw = wc[e] - A.c_grad * (f - d);
+            const bool solid = (c & FC_SOLID) != 0;
+            ou[e] = solid ? T(0) : nu;
+            ov[e] = solid ? T(0) : nvv;
+            ow[e] = solid ? T(0) : nw;
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.u, r, i0, ou, nv);
+            store_cells<T, W>(A.v, r, i0, ov, nv);
+            store_cells<T, W>(A.w, r, i0, ow, nv);
+            emit_shells<T, W>(A.u, g, 1, i0, j, kl, ou, nv);
+            emit_shells<T, W>(A.v, g, 2, i0, j, kl, ov, nv);
+            emit_shells<T, W>(A.w, g, 3, i0, j, kl, ow, nv);
+        }
+    }
+}
+
+// The end of dens_step under a mask: dens = +0 on solid cells, set_bnd(0, dens); in place, every lane its own cells.
+template <class T>
+__global__ void __launch_bounds__(256) zero_solid_kernel(Geom g, ProjectMaskArgs<T> A) {
+    constexpr int W = VecT<T>::W;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type xv = ldv(A.p + r + i0c), cv = ldv(A.code + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) out[e] = ((int)cv[e] & FC_SOLID) ? T(0) : xv[e];
+        if (nv > 0) {
+            store_cells<T, W>(A.p, r, i0, out, nv);
+            emit_shells<T, W>(A.p, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
 // ---- Multigrid V-cycle preconditioner (SPEC §11.3) ----
 // Three row kernels on the fields of one level (a Geom of its own: n_l cells per axis, one ghost plane per side on the
 // coarse levels) with the row shape, the clamped unconditional loads and the stencil of the CG kernels above. They know

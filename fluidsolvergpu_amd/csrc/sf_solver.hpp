@@ -42,6 +42,9 @@ class Solver final : public SolverBase {
     static constexpr int mg_z(int l) { return MG_SLOT + 3 * (l - 1); }
     static constexpr int mg_zp(int l) { return mg_z(l) + 1; }
     static constexpr int mg_r(int l) { return mg_z(l) + 2; }
+    // The face codes of the obstacles in force (SPEC §15): one slot with a buffer of its own from the first
+    // sf_set_obstacles on, written by that call only.
+    static constexpr int OBST_SLOT = MG_SLOT + 3 * (MG_MAXL - 1);
 
     // The geometry of the fields an operator runs on: the solver-wide one (lv0_, the default everywhere) or a coarse
     // level of the multigrid hierarchy, whose fields have n cells per axis, n / P planes per slab and one ghost plane.
@@ -53,7 +56,7 @@ class Solver final : public SolverBase {
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
         sfk::Geom geom{};
-        T* field[SF_NUM_FIELDS + NSCRATCH + 2 + 3 * (MG_MAXL - 1)] = {};
+        T* field[SF_NUM_FIELDS + NSCRATCH + 2 + 3 * (MG_MAXL - 1) + 1] = {};
         T* scratch[NSCRATCH] = {};
         T* snap[4] = {};               // snapshot buffers for asynchronous output
         hipStream_t os = nullptr;      // output (copy) stream
@@ -672,7 +675,12 @@ public:
         // FIRST projection: its slot is overwritten by advect before anything else looks at it. Their solves therefore
         // leave the i-shell unwritten (no partial writes to HBM: a 512^3 last pass takes 441 instead of 520 us). K_ = 0
         // runs no sweep: the fields keep their caller-written shells and are read from memory as before.
-        const bool dead = ishell_skip_ && K_ >= 1 && dead_ishell_opt_;
+        // (obstacles, SPEC §15: the masked project halves read every shell as stored, so nothing is left unwritten)
+        SF_REQUIRE(!obst_on_ || pressure_ == SF_PRESSURE_CG,
+                   "vel_step: obstacles need the CG pressure solver (SF_PRESSURE_CG)");
+        SF_REQUIRE(!(obst_on_ && mg_nu_ > 0),
+                   "vel_step: obstacles with the multigrid preconditioner in force are not supported");
+        const bool dead = ishell_skip_ && K_ >= 1 && dead_ishell_opt_ && !obst_on_;
         // SPEC §8: with a force on, the sources (bound slots, or the x0 slots themselves) plus the forces go into the
         // x0 slots first, and the step continues as with unbound sources
         const bool forces = eps_ != T(0) || beta_ != T(0);
@@ -729,6 +737,7 @@ public:
             op_advect_mc<1>(x, x0, b0, SF_U, SF_V, SF_W, false);
         else
             op_advect<1>(x, x0, b0, SF_U, SF_V, SF_W, false);
+        if (obst_on_) op_zero_solid(SF_DENS);
     }
 
     void set_iters(int iters) override {
@@ -1173,17 +1182,56 @@ public:
         join();
         SF_HIP(hipSetDevice(device_));
         records_alloc();
-        launch_rows("poisson_residual", sfk::cg_apply_dot_kernel<T, true>, [&](Slab& sl) {
+        auto args = [&](Slab& sl) {
             sfk::CgArgs<T> A{};
             A.p = ensure(sl, p);
             A.div = ensure(sl, div);
             return A;
-        }, [&](Slab& sl) {
-            return std::vector<Acc>{{sl.field[p], false, G_ - 1, G_ + nzl_ + 1}, {sl.field[div], false, G_, G_ + nzl_}};
-        });
+        };
+        auto acc = [&](Slab& sl) {
+            std::vector<Acc> a{{sl.field[p], false, G_ - 1, G_ + nzl_ + 1}, {sl.field[div], false, G_, G_ + nzl_}};
+            if (obst_on_) a.push_back({sl.field[OBST_SLOT], false, G_, G_ + nzl_});
+            return a;
+        };
+        if (obst_on_)
+            launch_rows("poisson_residual_masked", sfk::cg_apply_dot_masked_kernel<T, true>,
+                        [&](Slab& sl) { return sfk::CgMaskArgs<T>{args(sl), sl.field[OBST_SLOT]}; }, acc);
+        else
+            launch_rows("poisson_residual", sfk::cg_apply_dot_kernel<T, true>, args, acc);
         double r[2];
         finish_records(2, 2, 0, r);
         *rel = r[1] == 0.0 ? 0.0 : std::sqrt(r[0] / r[1]);
+    }
+    // SPEC §15: the mask of slot `mask_slot` becomes the face codes every masked kernel reads; -1: off
+    void set_obstacles(int mask_slot) override {
+        SF_REQUIRE(mask_slot >= -1 && mask_slot < SF_NUM_FIELDS, "set_obstacles: slot out of range (-1: off)");
+        SF_HIP(hipSetDevice(device_));
+        sync();
+        for (GraphEntry& e : graph_cache_) (void)hipGraphExecDestroy(e.exec);  // a dens_step of the other form
+        graph_cache_.clear();
+        if (mask_slot < 0) {
+            obst_on_ = false;
+            return;
+        }
+        records_alloc();
+        for (Slab& sl : slabs_) {
+            ensure(sl, mask_slot);
+            if (!sl.field[OBST_SLOT]) sl.field[OBST_SLOT] = alloc_field();
+        }
+        launch_rows("face_code", sfk::face_code_kernel<T>,
+                    [&](Slab& sl) { return sfk::FaceCodeArgs<T>{sl.field[mask_slot], sl.field[OBST_SLOT]}; },
+                    [&](Slab& sl) {
+                        return std::vector<Acc>{{sl.field[mask_slot], false, G_ - 1, G_ + nzl_ + 1},
+                                                {sl.field[OBST_SLOT], true, G_, G_ + nzl_}};
+                    });
+        double n[1];
+        finish_records(1, 1, 0, n);
+        n_fluid_ = (long long)n[0];
+        obst_on_ = true;
+    }
+    void obstacles(sf_obstacles* out) const override {
+        out->enabled = obst_on_ ? 1 : 0;
+        out->fluid_cells = obst_on_ ? n_fluid_ : (long long)N_ * N_ * N_;
     }
     void pressure_info(sf_pressure_info* out) const override { *out = info_; }
     void set_pressure_sync(int check_every) override {
@@ -2825,6 +2873,75 @@ private:
         exchange<3>(uvw);
     }
 
+    // ---- the two halves under obstacles (SPEC §15): one row launch per slab on its compute stream ----
+    sfk::ProjectMaskArgs<T> project_mask_args(Slab& sl, int u, int v, int w, int p, int div) {
+        const T Nf = (T)N_;
+        sfk::ProjectMaskArgs<T> A{};
+        A.u = u >= 0 ? ensure(sl, u) : nullptr;
+        A.v = v >= 0 ? ensure(sl, v) : nullptr;
+        A.w = w >= 0 ? ensure(sl, w) : nullptr;
+        A.p = ensure(sl, p);
+        A.div = div >= 0 ? ensure(sl, div) : nullptr;
+        A.code = sl.field[OBST_SLOT];
+        A.c_div = T(-0.5) * (T(1) / Nf);
+        A.c_grad = T(0.5) * Nf;
+        return A;
+    }
+    // a field as a row launch over the slab's own planes writes it: the shell plane of a wall slab included
+    Acc rows_written(const Slab& sl, const T* buf) const {
+        int lo, hi;
+        wr_range(sl, G_, G_ + nzl_, lo, hi);
+        return Acc{buf, true, lo, hi};
+    }
+    void project_first_half_masked(int u, int v, int w, int p, int div) {
+        join();
+        for (Slab& sl : slabs_) {
+            for (int f : {u, v, w, p, div}) ensure(sl, f);
+            SF_HIP(hipMemsetAsync(sl.field[p], 0, (size_t)field_elems_ * sizeof(T), sl.cs));
+            tr_whole("zero_p", sl, {}, {sl.field[p]});
+        }
+        launch_rows<false>("project_div_masked", sfk::project_div_masked_kernel<T>,
+                           [&](Slab& sl) { return project_mask_args(sl, u, v, w, p, div); },
+                           [&](Slab& sl) {
+                               return std::vector<Acc>{{sl.field[u], false, G_, G_ + nzl_},
+                                                       {sl.field[v], false, G_, G_ + nzl_},
+                                                       {sl.field[w], false, G_ - 1, G_ + nzl_ + 1},
+                                                       {sl.field[OBST_SLOT], false, G_, G_ + nzl_},
+                                                       rows_written(sl, sl.field[div])};
+                           });
+        publish_from_cs(div);
+    }
+    void project_second_half_masked(int u, int v, int w, int p, int div) {
+        join();  // p's ghost planes
+        launch_rows<false>("project_sub_masked", sfk::project_sub_masked_kernel<T>,
+                           [&](Slab& sl) { return project_mask_args(sl, u, v, w, p, div); },
+                           [&](Slab& sl) {
+                               std::vector<Acc> a{{sl.field[p], false, G_ - 1, G_ + nzl_ + 1},
+                                                  {sl.field[OBST_SLOT], false, G_, G_ + nzl_}};
+                               for (int q : {u, v, w}) {
+                                   a.push_back({sl.field[q], false, G_, G_ + nzl_});
+                                   a.push_back(rows_written(sl, sl.field[q]));
+                               }
+                               return a;
+                           });
+        if (P_ == 1) return;
+        for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
+        const int uvw[3] = {u, v, w};
+        exchange<3>(uvw);
+    }
+    // the end of dens_step under obstacles: x = +0 on solid cells, set_bnd(0, x), its ghost planes
+    void op_zero_solid(int x) {
+        join();
+        launch_rows<false>("zero_solid", sfk::zero_solid_kernel<T>,
+                           [&](Slab& sl) { return project_mask_args(sl, -1, -1, -1, x, -1); },
+                           [&](Slab& sl) {
+                               return std::vector<Acc>{{sl.field[x], false, G_, G_ + nzl_},
+                                                       {sl.field[OBST_SLOT], false, G_, G_ + nzl_},
+                                                       rows_written(sl, sl.field[x])};
+                           });
+        publish_from_cs(x);
+    }
+
     void note_solve(int solver, int status, int iterations, double rel) {
         info_.solver = solver;
         info_.status = status;
@@ -3116,6 +3233,7 @@ private:
     sfk::CgState<T> cg_iterate(int p, int div, double tol, int max_iters, int pm) {
         const int kb = G_, ke = G_ + nzl_;
         const bool pc = pm > 0;
+        const bool masked = obst_on_;  // SPEC §15: the masked siblings of init and apply, n_fluid as mu's divisor
         // d as a kernel writes it: the shell plane of a wall slab included
         auto d_written = [&](Slab& sl) {
             int lo, hi;
@@ -3124,10 +3242,14 @@ private:
         };
         // the fields each row kernel touches (z is whichever buffer the last pass of M(r) left in its slot)
         auto init_acc = [&](Slab& sl) {
-            return std::vector<Acc>{{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke}, d_written(sl)};
+            std::vector<Acc> a{{sl.field[div], false, kb, ke}, {sl.field[CG_R], true, kb, ke}, d_written(sl)};
+            if (masked) a.push_back({sl.field[OBST_SLOT], false, kb, ke});
+            return a;
         };
         auto apply_acc = [&](Slab& sl) {
-            return std::vector<Acc>{{sl.field[CG_D], false, kb - 1, ke + 1}, {sl.field[CG_Q], true, kb, ke}};
+            std::vector<Acc> a{{sl.field[CG_D], false, kb - 1, ke + 1}, {sl.field[CG_Q], true, kb, ke}};
+            if (masked) a.push_back({sl.field[OBST_SLOT], false, kb, ke});
+            return a;
         };
         auto update_acc = [&](Slab& sl) {
             return std::vector<Acc>{{sl.field[CG_D], false, kb, ke}, {sl.field[CG_Q], false, kb, ke},
@@ -3153,6 +3275,11 @@ private:
         };
         // rhs: the field at div's place; s: the scalar of the by-value forms
         auto args = [&](int rhs, T s) { return [this, p, rhs, s](Slab& sl) { return cg_args<DEV>(sl, p, rhs, s); }; };
+        auto margs = [&](int rhs, T s) {
+            return [this, p, rhs, s](Slab& sl) {
+                return sfk::CgMaskArgs<T>{cg_args<DEV>(sl, p, rhs, s), sl.field[OBST_SLOT]};
+            };
+        };
 
         sfk::CgState<T> st{};
         // z = M(r), gamma = r.z, then the direction from z: d = z (the first one) or z + beta * d
@@ -3168,7 +3295,11 @@ private:
         };
         auto iteration = [&] {
             join();  // d's ghost planes
-            launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false, DEV>, args(div, T(0)), acc(apply_acc));
+            if (masked)
+                launch_rows("cg_apply_dot_masked", sfk::cg_apply_dot_masked_kernel<T, false, DEV>, margs(div, T(0)),
+                            acc(apply_acc));
+            else
+                launch_rows("cg_apply_dot", sfk::cg_apply_dot_kernel<T, false, DEV>, args(div, T(0)), acc(apply_acc));
             if (!(pc ? cg_sum<DEV, sfk::STAGE_DELTA_PC>(st, 0.0) : cg_sum<DEV, sfk::STAGE_DELTA>(st, 0.0))) return false;
             launch_rows("cg_update", sfk::cg_update_kernel<T, DEV>, args(div, st.aT), acc(update_acc));
             if (!(pc ? cg_sum<DEV, sfk::STAGE_RHO_PC>(st, tol * tol) : cg_sum<DEV, sfk::STAGE_RHO>(st, tol * tol)))
@@ -3183,8 +3314,13 @@ private:
         launch_rows("cg_sum_div", sfk::reduce_rows_kernel<T, sfk::RED_SUM>,
                     [&](Slab& sl) { return (const T*)sl.field[div]; },
                     [&](Slab& sl) { return std::vector<Acc>{{sl.field[div], false, kb, ke}}; });
-        cg_sum<DEV, sfk::STAGE_MU>(st, (double)N_ * (double)N_ * (double)N_);
-        launch_rows("cg_init", sfk::cg_init_kernel<T, DEV>, args(div, st.mu), acc(init_acc));
+        // (with no fluid cell the sum is +0 and there is nothing to divide: mu = 0)
+        const double cells = masked ? (n_fluid_ > 0 ? (double)n_fluid_ : 1.0) : (double)N_ * (double)N_ * (double)N_;
+        cg_sum<DEV, sfk::STAGE_MU>(st, cells);
+        if (masked)
+            launch_rows("cg_init_masked", sfk::cg_init_masked_kernel<T, DEV>, margs(div, st.mu), acc(init_acc));
+        else
+            launch_rows("cg_init", sfk::cg_init_kernel<T, DEV>, args(div, st.mu), acc(init_acc));
         if (!pc) publish_from_cs(CG_D);  // (a preconditioned solve replaces d before anything reads its ghost planes)
         bool go = cg_sum<DEV, sfk::STAGE_RHO0>(st, 0.0);
         if (go && pc) go = direction_pc(std::true_type{});
@@ -3202,6 +3338,9 @@ private:
 
     void op_project_cg(int u, int v, int w, int p, int div, double tol, int max_iters, bool mirror_u = false) {
         mirror_u = mirror_u && ishell_skip_;
+        SF_REQUIRE(!(obst_on_ && mg_nu_ > 0),
+                   "project_cg: obstacles with the multigrid preconditioner in force are not supported (its coarse "
+                   "operators do not know the mask); switch one of them off");
         records_alloc();
         static_assert(sfk::CG_ST_CONVERGED == SF_CG_CONVERGED && sfk::CG_ST_MAX_ITERS == SF_CG_MAX_ITERS &&
                           sfk::CG_ST_BREAKDOWN == SF_CG_BREAKDOWN, "CgState::status holds sf_cg_status values");
@@ -3211,14 +3350,20 @@ private:
         if (pm > 0) pcg_alloc();
         host_waits_ = 0;
         ScratchAlias work_slots(slabs_, 3);
-        project_first_half(u, v, w, p, div, mirror_u, false, true);
+        if (obst_on_)
+            project_first_half_masked(u, v, w, p, div);
+        else
+            project_first_half(u, v, w, p, div, mirror_u, false, true);
         join();
         // (a solve that max_iters ends is still active, with the status its rho0 stage left: SF_CG_MAX_ITERS)
         const sfk::CgState<T> st =
             dev ? cg_iterate<true>(p, div, tol, max_iters, pm) : cg_iterate<false>(p, div, tol, max_iters, pm);
         host_waits_total_ += host_waits_;
         op_set_bnd(0, p, "cg_set_bnd_p");
-        project_second_half(u, v, w, p, div, false);
+        if (obst_on_)
+            project_second_half_masked(u, v, w, p, div);
+        else
+            project_second_half(u, v, w, p, div, false);
         note_solve(SF_PRESSURE_CG, st.status, st.iterations, st.rho0 == 0.0 ? 0.0 : std::sqrt(st.last / st.rho0));
     }
 
@@ -3596,6 +3741,8 @@ private:
     int check_every_ = 0, host_waits_ = 0;  // sf_set_pressure_sync; host waits of the last CG projection
     int precond_ = SF_PRECOND_NONE, precond_sweeps_ = 0;  // sf_set_pressure_preconditioner (SPEC §11.2)
     int mg_nu_ = 0, mg_maxl_ = 0, mg_nuc_ = 8;            // sf_set_pressure_multigrid (SPEC §11.3); nu = 0: off
+    bool obst_on_ = false;    // sf_set_obstacles (SPEC §15): the face codes of OBST_SLOT are in force
+    long long n_fluid_ = 0;   // fluid interior cells under them
     long long host_waits_total_ = 0;
     sf_pressure_info info_{SF_PRESSURE_JACOBI, SF_CG_MAX_ITERS, 0, -1.0, 0, 0};  // the last projection
     int num_cu_ = 256;

@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "sf_set_pressure_sync", "sf_pressure_sync_get",
     "sf_set_pressure_preconditioner", "sf_pressure_preconditioner_get",
     "sf_set_pressure_multigrid", "sf_pressure_multigrid_get", "sf_precondition",
+    "sf_set_obstacles", "sf_obstacles_get",
     "sf_render", "sf_render_read", "sf_light",
     "sf_render_view", "sf_render_view_read", "sf_view_frame",
     "sf_render_camera", "sf_camera_passes_get", "sf_camera_frame",
@@ -89,6 +90,11 @@ class SfPressurePreconditioner(C.Structure):
 class SfPressureMultigrid(C.Structure):
     """sf_pressure_multigrid of include/sfgpu.h (docs/SPEC.md §11.3)."""
     _fields_ = [("sweeps", C.c_int), ("max_levels", C.c_int), ("coarse_sweeps", C.c_int), ("levels", C.c_int)]
+
+
+class SfObstacles(C.Structure):
+    """sf_obstacles of include/sfgpu.h (docs/SPEC.md §15)."""
+    _fields_ = [("enabled", C.c_int), ("fluid_cells", C.c_longlong)]
 
 
 class SfRenderParams(C.Structure):
@@ -156,6 +162,8 @@ lib.sf_pressure_preconditioner_get.argtypes = [_ctx, C.POINTER(SfPressurePrecond
 lib.sf_set_pressure_multigrid.argtypes = [_ctx, C.c_int, C.c_int, C.c_int]
 lib.sf_pressure_multigrid_get.argtypes = [_ctx, C.POINTER(SfPressureMultigrid)]
 lib.sf_precondition.argtypes = [_ctx, C.c_int, C.c_int]
+lib.sf_set_obstacles.argtypes = [_ctx, C.c_int]
+lib.sf_obstacles_get.argtypes = [_ctx, C.POINTER(SfObstacles)]
 lib.sf_render.argtypes = [_ctx, C.POINTER(SfRenderParams)]
 lib.sf_render_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
 lib.sf_light.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
@@ -434,6 +442,28 @@ class FluidSolver:
         """z = M(r) with the preconditioner in force (the V-cycle of §11.3, else the Jacobi sweeps of §11.2): r is read
         on interior cells, z is written whole."""
         self._ck(lib.sf_precondition(self._h, _fid(z), _fid(r)))
+
+    # -- solid obstacles (docs/SPEC.md §15) --------------------------------------------------------
+    def set_obstacles(self, mask, slot="user3"):
+        """Solid cells for the CG projection, vel_step and dens_step: an interior cell is solid iff its mask value is
+        > 0. mask: None switches obstacles off; a field name or id takes the mask that slot holds; an (N+2)^3 array is
+        uploaded into `slot` first, over what the slot holds (the slot is free again afterwards: the mask is read once,
+        by this call; name a slot that is scratch at that moment where user3 is a bound source).
+        Collective on several ranks; synchronises."""
+        if mask is None:
+            self._ck(lib.sf_set_obstacles(self._h, -1))
+            return
+        if isinstance(mask, (str, int)):
+            slot = mask
+        else:
+            self.upload(slot, mask)
+        self._ck(lib.sf_set_obstacles(self._h, _fid(slot)))
+
+    def obstacles(self):
+        """enabled (0 / 1) and fluid_cells, the fluid interior cells of the whole grid (sf_obstacles_get)."""
+        d = SfObstacles()
+        self._ck(lib.sf_obstacles_get(self._h, C.byref(d)))
+        return {n: getattr(d, n) for n, _ in SfObstacles._fields_}
 
     # -- volume rendering and light marching (docs/SPEC.md §12) ---------------------------------
     def render(self, dens="dens", emit=None, axis=2, from_high=0, sigma=1.0):

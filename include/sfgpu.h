@@ -335,6 +335,27 @@ int sf_set_pressure_multigrid(sf_ctx* ctx, int sweeps, int max_levels, int coars
 int sf_pressure_multigrid_get(const sf_ctx* ctx, sf_pressure_multigrid* out);
 int sf_precondition(sf_ctx* ctx, int z, int r);
 
+/* Solid obstacles (docs/SPEC.md §15): a cell mask that the CG projection honours. An interior cell is solid iff its
+ * mask value is > 0 (NaN, -0 and negatives are fluid; shell entries are ignored, shell cells are never solid). One rule
+ * defines the divergence, the operator and the gradient: across a face that an interior solid cell closes, a fluid
+ * cell reads itself (negated for the normal velocity) instead of the neighbour, as selects on loaded values, so nothing
+ * stored in a solid cell (a NaN included) reaches a fluid cell. Solid cells end a projection with u = v = w = +0 and a
+ * dens_step with dens = +0.
+ *   sf_set_obstacles(mask_slot): reads the mask from field mask_slot once and turns it into per-cell face codes in a
+ *       work field of the context (allocated by the first call); later writes to the slot change nothing until it is
+ *       called again. From then on sf_project_cg, sf_poisson_residual and both projections of sf_vel_step are the masked
+ *       forms of §15 and sf_dens_step zeroes the density of solid cells; sf_vel_step then needs SF_PRESSURE_CG
+ *       (SF_ERR_INVALID otherwise), and a masked solve while the multigrid V-cycle is in force is SF_ERR_INVALID with
+ *       a message. sf_project and sf_precondition are never masked. mask_slot = -1 switches obstacles off and restores
+ *       the launches of a context that never set any. With a mask without a solid cell every result has the bits of
+ *       the unmasked call. Same bits for every decomposition, transport and check_every. Collective, the same on
+ *       every rank; it synchronises (the fluid cells are counted as a §10 sum) and drops the graphs SF_GRAPH has
+ *       cached. A slot outside -1 .. SF_NUM_FIELDS-1: SF_ERR_INVALID, and the setting is unchanged.
+ *   sf_obstacles_get: enabled (0 / 1) and fluid_cells, the fluid interior cells of the whole grid (N^3 while off). */
+typedef struct sf_obstacles { int enabled; long long fluid_cells; } sf_obstacles;
+int sf_set_obstacles(sf_ctx* ctx, int mask_slot);
+int sf_obstacles_get(const sf_ctx* ctx, sf_obstacles* out);
+
 /* Axis-aligned volume rendering and light marching of docs/SPEC.md §12: an N x N image of the smoke from data that
  * already sits in device memory, instead of a (N+2)^3 frame over the bus. One ray per pixel runs along axis (0: i,
  * 1: j, 2: k) through the N interior cells of a line, entering at index 1 (from_high = 0) or N (from_high = 1). A cell

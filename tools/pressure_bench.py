@@ -143,8 +143,32 @@ def precond_label(sweeps):
     return {"sweeps": None, "mg": "%d:%d:%d" % sweeps} if isinstance(sweeps, tuple) else {"sweeps": sweeps}
 
 
-def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters):
-    """One row per sweep count: an iteration's time, and the projection to tol = 1e-3 from the same state."""
+def obstacle_mask(N, dtype, specs):
+    """The mask of the driver's --obstacle values (docs/SPEC.md §15), and `centred`: the box of the cells i with
+    0.3 N < i <= 0.6 N per axis. (N+2)^3, [k, j, i], 1 in solid cells."""
+    import numpy as np
+
+    k, j, i = np.meshgrid(*(np.arange(N + 2, dtype=np.float64),) * 3, indexing="ij", sparse=True)
+    solid = np.zeros((N + 2,) * 3, bool)
+    for spec in specs:
+        if spec == "centred":
+            spec = "box:%d,%d,%d:%d,%d,%d" % ((int(0.3 * N) + 1,) * 3 + (int(0.6 * N),) * 3)
+        kind, a, b = spec.split(":")
+        a = [float(x) for x in a.split(",")]
+        if kind == "box":
+            b = [float(x) for x in b.split(",")]
+            solid |= (i >= a[0]) & (i <= b[0]) & (j >= a[1]) & (j <= b[1]) & (k >= a[2]) & (k <= b[2])
+        elif kind == "sphere":
+            solid |= ((i - a[0]) ** 2 + (j - a[1]) ** 2) + (k - a[2]) ** 2 <= float(b) ** 2
+        else:
+            raise SystemExit(f"--obstacle takes centred, box:I0,J0,K0:I1,J1,K1 or sphere:CX,CY,CZ:R, not {spec}")
+    solid[0], solid[-1], solid[:, 0], solid[:, -1], solid[:, :, 0], solid[:, :, -1] = (False,) * 6
+    return solid.astype(np.float32 if dtype == "f32" else np.float64)
+
+
+def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters, obstacle=None):
+    """One row per sweep count: an iteration's time, and the projection to tol = 1e-3 from the same state. obstacle: the
+    --obstacle values; the solves then run under that mask (sf_set_obstacles) and the rows say how many cells are fluid."""
     fs = context(N, dtype)
     for _ in range(2):
         fs.vel_step()
@@ -152,6 +176,8 @@ def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters):
     fs.sync()
     state = {n: fs.download(n) for n in ("u", "v", "w")}
     fs.set_pressure_sync(check_every)
+    if obstacle:
+        fs.set_obstacles(obstacle_mask(N, dtype, obstacle), slot="dens0")
 
     def solve(tol, limit):
         for n, a in state.items():
@@ -170,6 +196,7 @@ def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters):
         tm, info = min((solve(1e-30, iters) for _ in range(reps)), key=lambda r: r[0])
         tp, done = min((solve(1e-3, max_iters) for _ in range(reps)), key=lambda r: r[0])
         rows.append({"case": "precond", "grid": N, "dtype": dtype, **precond_label(m), "check_every": check_every,
+                     "obstacle": obstacle, "fluid_cells": fs.obstacles()["fluid_cells"],
                      "iteration_ms": round((tm - t0) / max(info["iterations"], 1), 5),
                      "iterations_1e-3": done["iterations"], "status_1e-3": done["status"],
                      "rel_residual": done["rel_residual"], "poisson_residual": fs.poisson_residual("u0", "v0"),
@@ -242,6 +269,9 @@ def main():
     ap.add_argument("--precond", default=None, help="comma-separated sweep counts, e.g. 0,2,4,8: only the precond cases")
     ap.add_argument("--mg", default=None, help="comma-separated V-cycle settings NU[:LEVELS[:COARSE]] (SPEC §11.3), e.g. "
                     "2,2:0:16,1,2:4: added to the precond cases (alone: --precond 0)")
+    ap.add_argument("--obstacle", action="append", default=None,
+                    help="with --precond: solve under this mask too (centred, box:I0,J0,K0:I1,J1,K1, sphere:CX,CY,CZ:R; may "
+                         "be repeated): every case runs without and with it")
     ap.add_argument("--check-every", nargs="+", default=["0", "1", "8", "max"])
     ap.add_argument("--sync-slabs", type=int, default=4)
     a = ap.parse_args()
@@ -251,8 +281,9 @@ def main():
         every = 0 if a.sync in (False, True) else int(a.sync)
         for c in a.cases:
             n, t = c.split(":")
-            for row in limited(a.limit, lambda: precond_case(int(n), t, a.iters, a.reps, sweeps, every, a.max_iters)):
-                print(json.dumps(row), flush=True)
+            for ob in ([None, a.obstacle] if a.obstacle else [None]):
+                for row in limited(a.limit, lambda: precond_case(int(n), t, a.iters, a.reps, sweeps, every, a.max_iters, ob)):
+                    print(json.dumps(row), flush=True)
         if not a.no_step:
             n, t = a.step_case.split(":")
             for m in sweeps:
