@@ -268,6 +268,17 @@ int sf_obstacles_get(const sf_ctx* ctx, sf_obstacles* out) {
     ctx->impl->obstacles(out);
     return SF_OK;
 }
+int sf_set_obstacle_multigrid(sf_ctx* ctx, int on) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_obstacle_multigrid(on); });
+}
+int sf_obstacle_multigrid_get(const sf_ctx* ctx, int* on) {
+    if (!ctx || !ctx->impl || !on) return SF_ERR_INVALID;
+    ctx->impl->obstacle_multigrid(on);
+    return SF_OK;
+}
+int sf_precondition_masked(sf_ctx* ctx, int z, int r) {
+    return guarded(ctx, [&](SolverBase& s) { s.precondition_masked(z, r); });
+}
 int sf_render(sf_ctx* ctx, const sf_render_params* p) {
     return guarded(ctx, [&](SolverBase& s) { s.render(p); });
 }

@@ -120,6 +120,9 @@ public:
     virtual void precondition(int z, int r) = 0;
     virtual void set_obstacles(int mask_slot) = 0;
     virtual void obstacles(sf_obstacles* out) const = 0;
+    virtual void set_obstacle_multigrid(int on) = 0;
+    virtual void obstacle_multigrid(int* on) const = 0;
+    virtual void precondition_masked(int z, int r) = 0;
     virtual void render(const sf_render_params* p) = 0;
     virtual void render_read(void* colour, void* transmittance) = 0;
     virtual void light(int dst, int dens, int axis, int from_high, double sigma) = 0;

@@ -28,7 +28,7 @@
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
 //             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
 //             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]
-//             [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]... [--help]
+//             [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]... [--obstacle-mg] [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -53,6 +53,7 @@
 // --obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R (with --pressure cg, not with --pressure-mg; up to 16 times): solid
 // cells of docs/SPEC.md §15, in cell indices: the cells of the inclusive index box, or those whose centre index lies
 // within R of (CX, CY, CZ) — squared distance, in double, <= R^2. The union of all of them is the mask of sf_set_obstacles.
+// --obstacle-mg: lets --obstacle go with --pressure-mg: the masked V-cycle of docs/SPEC.md §16 (sf_set_obstacle_multigrid).
 // --render VIEW:SIGMA[:LIGHT]: at every output step an image of the density (docs/SPEC.md §12) next to the frame,
 // "render_<frame, 4 digits>.pgm" (several processes: "render_GPU<rank>_<frame>.pgm", each rank the pixel rows it holds).
 // VIEW and LIGHT are one of i+ i- j+ j- k+ k-: the axis of the rays and the side they enter from (+: at index 1). SIGMA
@@ -116,6 +117,7 @@ struct Options {
         double a[6];  // box: i0, j0, k0, i1, j1, k1; sphere: cx, cy, cz, r
     };
     std::vector<Obstacle> obstacles;  // --obstacle (docs/SPEC.md §15)
+    bool obstacle_mg = false;         // --obstacle-mg (docs/SPEC.md §16)
     double cg_tol = 1e-3;
     int render_axis = -1, render_high = 0, light_axis = -1, light_high = 0;  // --render (axis -1: off / no light)
     double render_sigma = 0.0;
@@ -202,6 +204,7 @@ static void usage(FILE* to) {
             "                 [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]]   an image along any direction, STEP in cells (default 1)\n"
             "                 [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]   a pinhole camera at E looking at T\n"
             "                 [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]...   solid cells (with --pressure cg), up to 16\n"
+            "                 [--obstacle-mg]   --obstacle together with --pressure-mg: the masked V-cycle\n"
             "                 [--loopback --rank R --world W] [--help]\n");
 }
 
@@ -435,6 +438,7 @@ static Options parse(int argc, char** argv) {
             }
             o.obstacles.push_back(ob);
         }
+        else if (s == "--obstacle-mg") o.obstacle_mg = true;
         else if (s == "--render") {
             // VIEW:SIGMA[:LIGHT]
             const std::string spec = next();
@@ -533,7 +537,7 @@ static Options parse(int argc, char** argv) {
         fprintf(stderr, "--rank / --world need --loopback (ranks of a real run come from RANK / WORLD_SIZE)\n");
         exit(2);
     }
-    if (!o.obstacles.empty() && (o.pressure != SF_PRESSURE_CG || o.mg_sweeps > 0)) {
+    if (!o.obstacles.empty() && (o.pressure != SF_PRESSURE_CG || (o.mg_sweeps > 0 && !o.obstacle_mg))) {
         fprintf(stderr, "--obstacle needs --pressure cg and does not go with --pressure-mg (docs/SPEC.md §15)\n");
         exit(2);
     }
@@ -789,6 +793,7 @@ static int run(const Options& o) {
     if (o.cg_precond != SF_PRECOND_NONE)
         SF_CHECK_RETURN(sf_set_pressure_preconditioner(g_ctx, o.cg_precond, o.cg_precond_sweeps));
     if (o.mg_sweeps > 0) SF_CHECK_RETURN(sf_set_pressure_multigrid(g_ctx, o.mg_sweeps, o.mg_levels, o.mg_coarse));
+    if (o.obstacle_mg) SF_CHECK_RETURN(sf_set_obstacle_multigrid(g_ctx, 1));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

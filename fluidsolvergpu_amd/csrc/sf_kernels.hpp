@@ -3669,6 +3669,155 @@ __global__ void __launch_bounds__(256) mg_prolong_kernel(Geom g, MgArgs<T> A) {
     }
 }
 
+// ---- The V-cycle under a mask (SPEC §16) ----
+// Siblings of the three kernels above with cg_stencil_masked in place of cg_stencil and one face-code vector per cell:
+// the row mapping, the clamped unconditional loads and the stores are theirs, every face and solid rule is a select on
+// loaded values. A level without a solid cell (all codes 0) gives the bits of the unmasked kernel.
+template <class T>
+struct MgMaskArgs {
+    MgArgs<T> a;
+    const T* code;  // smooth: the level's face codes; restrict, prolong, coarsen: the fine level's
+};
+
+// The mask of the next level (as a field of T, for face_code_kernel on that level): 1 where all eight children carry
+// FC_SOLID, else 0. Row mapping of mg_restrict_kernel; a.out: the coarse mask, a.other: the fine level.
+template <class T>
+__global__ void __launch_bounds__(256) mg_coarsen_mask_kernel(Geom gc, MgMaskArgs<T> M) {
+    constexpr int W = VecT<T>::W, H = W / 2;
+    const MgArgs<T>& A = M.a;
+    const Geom& gf = A.other;
+    int J, P;
+    if (!reduce_row(gc, J, P)) return;
+    const long rc = row0(gc, J, gc.G + P);
+    const int nm = (gf.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(gf, m, i0, i0c);
+        int all[H];
+#pragma unroll
+        for (int h = 0; h < H; ++h) all[h] = FC_SOLID;
+#pragma unroll
+        for (int dk = 0; dk < 2; ++dk)
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const long rf = row0(gf, 2 * J - 1 + dj, gf.G + 2 * P + dk);
+                const typename VecT<T>::type cv = ldv(M.code + rf + i0c);
+#pragma unroll
+                for (int h = 0; h < H; ++h) all[h] &= (int)cv[2 * h] & (int)cv[2 * h + 1];
+            }
+        const int I0 = (i0 + 1) / 2;
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+            if (I0 + h <= gc.N) A.out[rc + I0 + h] = all[h] ? T(1) : T(0);
+    }
+}
+
+// mg_smooth_kernel under a mask: z' = z + c_s * (r - A_m z) on fluid cells, +0 on solid ones, set_bnd(0, z'). FIRST:
+// T(0) + c_s * r on fluid cells. What r and z store in a solid cell is loaded and never an operand of a result.
+template <class T, bool FIRST>
+__global__ void __launch_bounds__(256) mg_smooth_masked_kernel(Geom g, MgMaskArgs<T> M) {
+    constexpr int W = VecT<T>::W;
+    const MgArgs<T>& A = M.a;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const T cs = (T)(1.0 / 7.0);
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type rv = ldv(A.r + r + i0c), cv = ldv(M.code + r + i0c);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+        if constexpr (FIRST) {
+#pragma unroll
+            for (int e = 0; e < W; ++e) out[e] = ((int)cv[e] & FC_SOLID) ? T(0) : T(0) + cs * rv[e];
+        } else {
+            typename VecT<T>::type zc;
+            T az[W];
+            cg_stencil_masked<T, W>(g, A.z, M.code, r, m, i0, i0c, zc, az);
+#pragma unroll
+            for (int e = 0; e < W; ++e) out[e] = ((int)cv[e] & FC_SOLID) ? T(0) : zc[e] + cs * (rv[e] - az[e]);
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.out, r, i0, out, nv);
+            emit_shells<T, W>(A.out, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
+// mg_restrict_kernel under a mask: e = r - A_m z on fluid cells, +0 on solid ones, then the same bracketed sum. A coarse
+// cell that is solid has eight solid children and sums eight +0: no select on the coarse side.
+template <class T>
+__global__ void __launch_bounds__(256) mg_restrict_masked_kernel(Geom gc, MgMaskArgs<T> M) {
+    constexpr int W = VecT<T>::W, H = W / 2;
+    const MgArgs<T>& A = M.a;
+    const Geom& gf = A.other;
+    int J, P;
+    if (!reduce_row(gc, J, P)) return;
+    const T half = T(0.5);
+    const long rc = row0(gc, J, gc.G + P);
+    const int nm = (gf.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(gf, m, i0, i0c);
+        T s[2][2][H];
+#pragma unroll
+        for (int dk = 0; dk < 2; ++dk)
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const long rf = row0(gf, 2 * J - 1 + dj, gf.G + 2 * P + dk);
+                typename VecT<T>::type zc;
+                T az[W];
+                cg_stencil_masked<T, W>(gf, A.z, M.code, rf, m, i0, i0c, zc, az);
+                const typename VecT<T>::type rv = ldv(A.r + rf + i0c), cv = ldv(M.code + rf + i0c);
+                T e[W];
+#pragma unroll
+                for (int c = 0; c < W; ++c) e[c] = ((int)cv[c] & FC_SOLID) ? T(0) : rv[c] - az[c];
+#pragma unroll
+                for (int h = 0; h < H; ++h) s[dk][dj][h] = e[2 * h] + e[2 * h + 1];
+            }
+        const int I0 = (i0 + 1) / 2;
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+            const T v = half * ((s[0][0][h] + s[0][1][h]) + (s[1][0][h] + s[1][1][h]));
+            if (I0 + h <= gc.N) A.out[rc + I0 + h] = v;
+        }
+    }
+}
+
+// mg_prolong_kernel under a mask: z += zc[parent] on fluid cells, z = +0 on solid ones, set_bnd(0, z).
+template <class T>
+__global__ void __launch_bounds__(256) mg_prolong_masked_kernel(Geom g, MgMaskArgs<T> M) {
+    constexpr int W = VecT<T>::W, H = W / 2;
+    const MgArgs<T>& A = M.a;
+    const Geom& gc = A.other;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const long rc = row0(gc, (j + 1) / 2, gc.G + p / 2);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const typename VecT<T>::type zv = ldv(A.out + r + i0c), cv = ldv(M.code + r + i0c);
+        const int I0c = (i0c + 1) / 2;
+        T c[H];
+#pragma unroll
+        for (int h = 0; h < H; ++h) c[h] = A.z[rc + I0c + h];
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) out[e] = ((int)cv[e] & FC_SOLID) ? T(0) : zv[e] + c[e / 2];
+        if (nv > 0) {
+            store_cells<T, W>(A.out, r, i0, out, nv);
+            emit_shells<T, W>(A.out, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
 // What a solve does with the sum s of one stage (SPEC §11, §11.2): the stop tests and their status, and alpha and beta
 // as T. The one statement of those rules: cg_scalars_kernel applies it where the scalars live on the device, the
 // host (Solver::cg_sum) where they do not. c: N^3 (STAGE_MU) or tol * tol (STAGE_RHO, STAGE_RHO_PC).

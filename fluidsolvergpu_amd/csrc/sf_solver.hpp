@@ -45,6 +45,9 @@ class Solver final : public SolverBase {
     // The face codes of the obstacles in force (SPEC §15): one slot with a buffer of its own from the first
     // sf_set_obstacles on, written by that call only.
     static constexpr int OBST_SLOT = MG_SLOT + 3 * (MG_MAXL - 1);
+    // The face codes of the coarse levels l >= 1 under obstacles (SPEC §16): one owning slot per level, written when the
+    // first masked V-cycle after sf_set_obstacles / sf_set_pressure_multigrid builds them. Level 0 is OBST_SLOT.
+    static constexpr int mg_code(int l) { return OBST_SLOT + l; }
 
     // The geometry of the fields an operator runs on: the solver-wide one (lv0_, the default everywhere) or a coarse
     // level of the multigrid hierarchy, whose fields have n cells per axis, n / P planes per slab and one ghost plane.
@@ -56,7 +59,7 @@ class Solver final : public SolverBase {
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
         sfk::Geom geom{};
-        T* field[SF_NUM_FIELDS + NSCRATCH + 2 + 3 * (MG_MAXL - 1) + 1] = {};
+        T* field[SF_NUM_FIELDS + NSCRATCH + 2 + 3 * (MG_MAXL - 1) + 1 + (MG_MAXL - 1)] = {};
         T* scratch[NSCRATCH] = {};
         T* snap[4] = {};               // snapshot buffers for asynchronous output
         hipStream_t os = nullptr;      // output (copy) stream
@@ -678,7 +681,7 @@ public:
         // (obstacles, SPEC §15: the masked project halves read every shell as stored, so nothing is left unwritten)
         SF_REQUIRE(!obst_on_ || pressure_ == SF_PRESSURE_CG,
                    "vel_step: obstacles need the CG pressure solver (SF_PRESSURE_CG)");
-        SF_REQUIRE(!(obst_on_ && mg_nu_ > 0),
+        SF_REQUIRE(!(obst_on_ && mg_nu_ > 0) || obst_mg_,
                    "vel_step: obstacles with the multigrid preconditioner in force are not supported");
         const bool dead = ishell_skip_ && K_ >= 1 && dead_ishell_opt_ && !obst_on_;
         // SPEC §8: with a force on, the sources (bound slots, or the x0 slots themselves) plus the forces go into the
@@ -1209,6 +1212,7 @@ public:
         sync();
         for (GraphEntry& e : graph_cache_) (void)hipGraphExecDestroy(e.exec);  // a dens_step of the other form
         graph_cache_.clear();
+        mg_codes_ok_ = false;
         if (mask_slot < 0) {
             obst_on_ = false;
             return;
@@ -1232,6 +1236,29 @@ public:
     void obstacles(sf_obstacles* out) const override {
         out->enabled = obst_on_ ? 1 : 0;
         out->fluid_cells = obst_on_ ? n_fluid_ : (long long)N_ * N_ * N_;
+    }
+    // SPEC §16: with obstacles on and the V-cycle in force, the masked V-cycle instead of the refusal
+    void set_obstacle_multigrid(int on) override {
+        SF_REQUIRE(on == 0 || on == 1, "obstacle multigrid: on must be 0 or 1");
+        SF_HIP(hipSetDevice(device_));
+        sync();
+        for (GraphEntry& e : graph_cache_) (void)hipGraphExecDestroy(e.exec);
+        graph_cache_.clear();
+        obst_mg_ = on != 0;
+    }
+    void obstacle_multigrid(int* on) const override { *on = obst_mg_ ? 1 : 0; }
+    void precondition_masked(int z, int r) override {
+        check_distinct("precondition_masked: z and r must be different fields", {z, r});
+        SF_REQUIRE(obst_on_ && mg_nu_ > 0 && obst_mg_,
+                   "precondition_masked: needs obstacles (sf_set_obstacles), the multigrid preconditioner "
+                   "(sf_set_pressure_multigrid) and sf_set_obstacle_multigrid(1)");
+        SF_HIP(hipSetDevice(device_));
+        pcg_alloc();
+        records_alloc();
+        for (Slab& sl : slabs_)
+            for (int f : {z, r}) ensure(sl, f);
+        join();
+        op_precondition(mg_nu_, z, r, true);
     }
     void pressure_info(sf_pressure_info* out) const override { *out = info_; }
     void set_pressure_sync(int check_every) override {
@@ -1267,6 +1294,7 @@ public:
         mg_nu_ = sweeps;
         mg_maxl_ = max_levels;
         mg_nuc_ = coarse_sweeps;
+        mg_codes_ok_ = false;
     }
     void pressure_multigrid(sf_pressure_multigrid* out) const override {
         out->sweeps = mg_nu_;
@@ -1813,13 +1841,15 @@ private:
     // One row kernel (one wave per row, the nzl planes of a slab in one launch: SPEC §10, §11) on every slab's compute
     // stream, with its trace. args(sl): the kernel's argument after the geometry; acc(sl): its field accesses. RECORDS:
     // the kernel also takes, and writes, the slab's row records.
-    // lv: the level whose rows the launch runs over (the multigrid kernels; no row records there).
+    // lv: the level whose rows the launch runs over (the multigrid kernels; row records only from the face codes of a
+    // coarse level, which nothing reads).
     template <bool RECORDS = true, class K, class ArgsF, class AccF>
     void launch_rows(const char* name, K kernel, ArgsF args, AccF acc, const Level* lv = nullptr) {
         const Level& h = lv ? *lv : lv0_;
         for (Slab& sl : slabs_) {
             if constexpr (RECORDS)
-                hipLaunchKernelGGL(kernel, dim3(row_blocks(h)), dim3(256), 0, sl.cs, sl.geom, args(sl), sl.red_rows, rows_pad());
+                hipLaunchKernelGGL(kernel, dim3(row_blocks(h)), dim3(256), 0, sl.cs, lv ? level_geom(sl, h) : sl.geom, args(sl),
+                                   sl.red_rows, rows_pad());
             else
                 hipLaunchKernelGGL(kernel, dim3(row_blocks(h)), dim3(256), 0, sl.cs, lv ? level_geom(sl, h) : sl.geom, args(sl));
             SF_HIP(hipGetLastError());
@@ -3085,9 +3115,10 @@ private:
     // compute streams joined for the row kernel that follows.
     // The one place that chooses M: the V-cycle of §11.3 while sf_set_pressure_multigrid has it in force, else the sweeps.
     // z, r: the slots of the solve, or the two fields of sf_precondition.
-    void op_precondition(int sweeps, int z = CG_Z, int r = CG_R) {
+    // masked: the V-cycle of §16 (the Jacobi sweeps never know the mask: SPEC §15).
+    void op_precondition(int sweeps, int z = CG_Z, int r = CG_R, bool masked = false) {
         if (mg_nu_ > 0) {
-            op_vcycle(z, r);
+            op_vcycle(z, r, masked);
             return;
         }
         publish_from_cs(r);
@@ -3137,18 +3168,53 @@ private:
         }
         return lv;
     }
+    // The face codes of the coarse levels (SPEC §16): level l + 1 is solid where all eight children are solid on level
+    // l. The coarse mask is built in the level's right-hand side (free between cycles), its one ghost plane travels,
+    // and face_code_kernel turns it into the level's codes exactly as sf_set_obstacles does on level 0 (the row records
+    // it writes are not used). Same codes for every decomposition.
+    void mg_codes_build(const std::vector<Level>& lv) {
+        const int nl = (int)lv.size();
+        for (Slab& sl : slabs_)
+            for (int l = 1; l < nl; ++l)
+                if (!sl.field[mg_code(l)]) sl.field[mg_code(l)] = alloc_field(&lv[l]);
+        for (int l = 0; l + 1 < nl; ++l) {
+            const Level &hf = lv[l], &hc = lv[l + 1];
+            join();
+            launch_rows<false>("mg_coarsen_mask", sfk::mg_coarsen_mask_kernel<T>,
+                               [&](Slab& sl) {
+                                   return sfk::MgMaskArgs<T>{{nullptr, nullptr, sl.field[mg_r(l + 1)], l == 0 ? sl.geom : level_geom(sl, hf)},
+                                                             sl.field[mg_code(l)]};
+                               },
+                               [&](Slab& sl) {
+                                   return std::vector<Acc>{{sl.field[mg_code(l)], false, hf.G, hf.G + hf.nzl},
+                                                           {sl.field[mg_r(l + 1)], true, hc.G, hc.G + hc.nzl}};
+                               }, &hc);
+            publish_from_cs(mg_r(l + 1), &hc);
+            join();
+            launch_rows("mg_face_code", sfk::face_code_kernel<T>,
+                        [&](Slab& sl) { return sfk::FaceCodeArgs<T>{sl.field[mg_r(l + 1)], sl.field[mg_code(l + 1)]}; },
+                        [&](Slab& sl) {
+                            return std::vector<Acc>{{sl.field[mg_r(l + 1)], false, hc.G - 1, hc.G + hc.nzl + 1},
+                                                    {sl.field[mg_code(l + 1)], true, hc.G, hc.G + hc.nzl}};
+                        }, &hc);
+        }
+        mg_codes_ok_ = true;
+    }
     // One symmetric V-cycle z = V(0, r) (SPEC §11.3): down with nu sweeps from zero and the restricted residual per
     // level, nu_c sweeps on the coarsest, up with the correction and nu sweeps. Every kernel runs on the compute stream
     // of its slab; the ghost planes of z on a level travel after every sweep and after the correction (so they are
     // current before each sweep and before the residual), those of the coarse right-hand sides never (read on own planes
     // only). Leaves the compute streams joined.
-    void op_vcycle(int z, int r) {
+    // masked (SPEC §16): the same cycle with the masked sibling of every kernel, which reads the face codes of its level
+    // (restrict and prolong: of the fine level) besides.
+    void op_vcycle(int z, int r, bool masked = false) {
         const std::vector<Level> lv = mg_levels();
         const int nl = (int)lv.size();
         for (Slab& sl : slabs_)
             for (int l = 1; l < nl; ++l)
                 for (int f : {mg_z(l), mg_zp(l), mg_r(l)})
                     if (!sl.field[f]) sl.field[f] = alloc_field(&lv[l]);
+        if (masked && !mg_codes_ok_) mg_codes_build(lv);
         auto zs = [&](int l) { return l == 0 ? z : mg_z(l); };
         auto ps = [&](int l) { return l == 0 ? CG_ZP : mg_zp(l); };
         auto rs = [&](int l) { return l == 0 ? r : mg_r(l); };
@@ -3158,6 +3224,17 @@ private:
         auto written = [&](Slab& sl, int l, const T* buf) {
             const Level& h = lv[l];
             return Acc{buf, true, sl.geom.wall_lo ? h.G - 1 : h.G, h.G + h.nzl + (sl.geom.wall_hi ? 1 : 0)};
+        };
+        // the masked forms: the sibling's argument and accesses, and the codes of level l on its own planes
+        auto margs = [&](auto args, int l) {
+            return [args, l](Slab& sl) { return sfk::MgMaskArgs<T>{args(sl), sl.field[mg_code(l)]}; };
+        };
+        auto macc = [&](auto acc, int l) {
+            return [acc, l, &lv](Slab& sl) {
+                std::vector<Acc> a = acc(sl);
+                a.push_back({sl.field[mg_code(l)], false, lv[l].G, lv[l].G + lv[l].nzl});
+                return a;
+            };
         };
         auto sweeps = [&](int l, int count, bool from_zero) {
             const Level& h = lv[l];
@@ -3170,7 +3247,11 @@ private:
                     if (!first) a.push_back({sl.field[zs(l)], false, h.G - 1, h.G + h.nzl + 1});
                     return a;
                 };
-                if (first)
+                if (masked && first)
+                    launch_rows<false>("mg_smooth0_masked", sfk::mg_smooth_masked_kernel<T, true>, margs(args, l), macc(acc, l), lp(l));
+                else if (masked)
+                    launch_rows<false>("mg_smooth_masked", sfk::mg_smooth_masked_kernel<T, false>, margs(args, l), macc(acc, l), lp(l));
+                else if (first)
                     launch_rows<false>("mg_smooth0", sfk::mg_smooth_kernel<T, true>, args, acc, lp(l));
                 else
                     launch_rows<false>("mg_smooth", sfk::mg_smooth_kernel<T, false>, args, acc, lp(l));
@@ -3183,24 +3264,30 @@ private:
             if (l == nl - 1) break;
             const Level &hf = lv[l], &hc = lv[l + 1];
             join();  // the residual reads z's ghost planes
-            launch_rows<false>("mg_restrict", sfk::mg_restrict_kernel<T>,
-                               [&](Slab& sl) { return sfk::MgArgs<T>{sl.field[zs(l)], sl.field[rs(l)], sl.field[rs(l + 1)], geom(sl, l)}; },
-                               [&](Slab& sl) {
-                                   return std::vector<Acc>{{sl.field[zs(l)], false, hf.G - 1, hf.G + hf.nzl + 1},
-                                                           {sl.field[rs(l)], false, hf.G, hf.G + hf.nzl},
-                                                           {sl.field[rs(l + 1)], true, hc.G, hc.G + hc.nzl}};
-                               }, &hc);
+            auto args = [&](Slab& sl) { return sfk::MgArgs<T>{sl.field[zs(l)], sl.field[rs(l)], sl.field[rs(l + 1)], geom(sl, l)}; };
+            auto acc = [&](Slab& sl) {
+                return std::vector<Acc>{{sl.field[zs(l)], false, hf.G - 1, hf.G + hf.nzl + 1},
+                                        {sl.field[rs(l)], false, hf.G, hf.G + hf.nzl},
+                                        {sl.field[rs(l + 1)], true, hc.G, hc.G + hc.nzl}};
+            };
+            if (masked)
+                launch_rows<false>("mg_restrict_masked", sfk::mg_restrict_masked_kernel<T>, margs(args, l), macc(acc, l), &hc);
+            else
+                launch_rows<false>("mg_restrict", sfk::mg_restrict_kernel<T>, args, acc, &hc);
         }
         for (int l = nl - 2; l >= 0; --l) {
             const Level &hf = lv[l], &hc = lv[l + 1];
             join();
-            launch_rows<false>("mg_prolong", sfk::mg_prolong_kernel<T>,
-                               [&](Slab& sl) { return sfk::MgArgs<T>{sl.field[zs(l + 1)], nullptr, sl.field[zs(l)], geom(sl, l + 1)}; },
-                               [&](Slab& sl) {
-                                   return std::vector<Acc>{{sl.field[zs(l + 1)], false, hc.G, hc.G + hc.nzl},
-                                                           {sl.field[zs(l)], false, hf.G, hf.G + hf.nzl},
-                                                           written(sl, l, sl.field[zs(l)])};
-                               }, lp(l));
+            auto args = [&](Slab& sl) { return sfk::MgArgs<T>{sl.field[zs(l + 1)], nullptr, sl.field[zs(l)], geom(sl, l + 1)}; };
+            auto acc = [&](Slab& sl) {
+                return std::vector<Acc>{{sl.field[zs(l + 1)], false, hc.G, hc.G + hc.nzl},
+                                        {sl.field[zs(l)], false, hf.G, hf.G + hf.nzl},
+                                        written(sl, l, sl.field[zs(l)])};
+            };
+            if (masked)
+                launch_rows<false>("mg_prolong_masked", sfk::mg_prolong_masked_kernel<T>, margs(args, l), macc(acc, l), lp(l));
+            else
+                launch_rows<false>("mg_prolong", sfk::mg_prolong_kernel<T>, args, acc, lp(l));
             publish_from_cs(zs(l), lp(l));
             sweeps(l, mg_nu_, false);
         }
@@ -3285,7 +3372,7 @@ private:
         // z = M(r), gamma = r.z, then the direction from z: d = z (the first one) or z + beta * d
         auto direction_pc = [&](auto first) {
             constexpr bool INIT = decltype(first)::value;
-            op_precondition(pm);
+            op_precondition(pm, CG_Z, CG_R, masked);
             launch_rows("cg_dot", sfk::cg_dot_kernel<T, DEV>, args(CG_Z, T(0)), acc(dot_acc));
             if (!cg_sum<DEV, INIT ? sfk::STAGE_GAMMA0 : sfk::STAGE_GAMMA>(st, 0.0)) return false;
             launch_rows<false>("cg_direction_z", sfk::cg_direction_z_kernel<T, DEV, INIT>, args(CG_Z, st.bT),
@@ -3338,7 +3425,7 @@ private:
 
     void op_project_cg(int u, int v, int w, int p, int div, double tol, int max_iters, bool mirror_u = false) {
         mirror_u = mirror_u && ishell_skip_;
-        SF_REQUIRE(!(obst_on_ && mg_nu_ > 0),
+        SF_REQUIRE(!(obst_on_ && mg_nu_ > 0) || obst_mg_,
                    "project_cg: obstacles with the multigrid preconditioner in force are not supported (its coarse "
                    "operators do not know the mask); switch one of them off");
         records_alloc();
@@ -3741,6 +3828,8 @@ private:
     int check_every_ = 0, host_waits_ = 0;  // sf_set_pressure_sync; host waits of the last CG projection
     int precond_ = SF_PRECOND_NONE, precond_sweeps_ = 0;  // sf_set_pressure_preconditioner (SPEC §11.2)
     int mg_nu_ = 0, mg_maxl_ = 0, mg_nuc_ = 8;            // sf_set_pressure_multigrid (SPEC §11.3); nu = 0: off
+    bool obst_mg_ = false;      // sf_set_obstacle_multigrid (SPEC §16): a masked solve under the V-cycle runs, masked
+    bool mg_codes_ok_ = false;  // the face codes of the coarse levels match the mask and the levels in force
     bool obst_on_ = false;    // sf_set_obstacles (SPEC §15): the face codes of OBST_SLOT are in force
     long long n_fluid_ = 0;   // fluid interior cells under them
     long long host_waits_total_ = 0;

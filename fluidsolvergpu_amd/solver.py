@@ -53,6 +53,7 @@ ABI_SYMBOLS = (
     "sf_set_pressure_preconditioner", "sf_pressure_preconditioner_get",
     "sf_set_pressure_multigrid", "sf_pressure_multigrid_get", "sf_precondition",
     "sf_set_obstacles", "sf_obstacles_get",
+    "sf_set_obstacle_multigrid", "sf_obstacle_multigrid_get", "sf_precondition_masked",
     "sf_render", "sf_render_read", "sf_light",
     "sf_render_view", "sf_render_view_read", "sf_view_frame",
     "sf_render_camera", "sf_camera_passes_get", "sf_camera_frame",
@@ -164,6 +165,9 @@ lib.sf_pressure_multigrid_get.argtypes = [_ctx, C.POINTER(SfPressureMultigrid)]
 lib.sf_precondition.argtypes = [_ctx, C.c_int, C.c_int]
 lib.sf_set_obstacles.argtypes = [_ctx, C.c_int]
 lib.sf_obstacles_get.argtypes = [_ctx, C.POINTER(SfObstacles)]
+lib.sf_set_obstacle_multigrid.argtypes = [_ctx, C.c_int]
+lib.sf_obstacle_multigrid_get.argtypes = [_ctx, C.POINTER(C.c_int)]
+lib.sf_precondition_masked.argtypes = [_ctx, C.c_int, C.c_int]
 lib.sf_render.argtypes = [_ctx, C.POINTER(SfRenderParams)]
 lib.sf_render_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
 lib.sf_light.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
@@ -464,6 +468,24 @@ class FluidSolver:
         d = SfObstacles()
         self._ck(lib.sf_obstacles_get(self._h, C.byref(d)))
         return {n: getattr(d, n) for n, _ in SfObstacles._fields_}
+
+    # -- obstacle-aware multigrid (docs/SPEC.md §16) ------------------------------------------------
+    def set_obstacle_multigrid(self, on):
+        """on = True: a masked solve with the V-cycle in force runs the masked V-cycle of §16 (coarse cells solid iff all
+        eight children are) instead of being refused; False (the default) keeps the refusal. Valid in any order with
+        set_obstacles and set_pressure_multigrid. Collective on several ranks; synchronises."""
+        self._ck(lib.sf_set_obstacle_multigrid(self._h, 1 if on else 0))
+
+    def obstacle_multigrid(self):
+        """The setting of set_obstacle_multigrid (sf_obstacle_multigrid_get)."""
+        on = C.c_int(0)
+        self._ck(lib.sf_obstacle_multigrid_get(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def precondition_masked(self, z, r):
+        """z = V_m(0, r), the masked V-cycle of §16 singly: needs obstacles, the V-cycle and set_obstacle_multigrid(True).
+        r is read on interior cells (solid cells never), z is written whole."""
+        self._ck(lib.sf_precondition_masked(self._h, _fid(z), _fid(r)))
 
     # -- volume rendering and light marching (docs/SPEC.md §12) ---------------------------------
     def render(self, dens="dens", emit=None, axis=2, from_high=0, sigma=1.0):

@@ -346,7 +346,7 @@ int sf_precondition(sf_ctx* ctx, int z, int r);
  *       called again. From then on sf_project_cg, sf_poisson_residual and both projections of sf_vel_step are the masked
  *       forms of §15 and sf_dens_step zeroes the density of solid cells; sf_vel_step then needs SF_PRESSURE_CG
  *       (SF_ERR_INVALID otherwise), and a masked solve while the multigrid V-cycle is in force is SF_ERR_INVALID with
- *       a message. sf_project and sf_precondition are never masked. mask_slot = -1 switches obstacles off and restores
+ *       a message unless sf_set_obstacle_multigrid(1) was called (below). sf_project and sf_precondition are never masked. mask_slot = -1 switches obstacles off and restores
  *       the launches of a context that never set any. With a mask without a solid cell every result has the bits of
  *       the unmasked call. Same bits for every decomposition, transport and check_every. Collective, the same on
  *       every rank; it synchronises (the fluid cells are counted as a §10 sum) and drops the graphs SF_GRAPH has
@@ -355,6 +355,23 @@ int sf_precondition(sf_ctx* ctx, int z, int r);
 typedef struct sf_obstacles { int enabled; long long fluid_cells; } sf_obstacles;
 int sf_set_obstacles(sf_ctx* ctx, int mask_slot);
 int sf_obstacles_get(const sf_ctx* ctx, sf_obstacles* out);
+
+/* Obstacle-aware multigrid (docs/SPEC.md §16): the V-cycle of §11.3 with every level knowing the mask. A coarse cell
+ * is solid iff all eight of its children are; smoother, residual and correction are the masked forms (a closed
+ * neighbour reads as the cell itself, solid cells hold +0). A mask without a solid cell gives the bits of §11.3.
+ *   sf_set_obstacle_multigrid(on): 0 (the default) keeps the refusal above, with its messages and launches; 1 makes a
+ *       masked solve with the V-cycle in force run with z = V_m(0, r) where §15 says z = M(r). Valid in any order with
+ *       sf_set_obstacles and sf_set_pressure_multigrid, each of which makes the next masked V-cycle build the face
+ *       codes of the coarse levels afresh (one more field per coarse level, allocated by the first one). Same bits for
+ *       every admissible decomposition, transport and check_every. Collective; it synchronises and drops the graphs
+ *       SF_GRAPH has cached. on outside 0 / 1: SF_ERR_INVALID, and the setting is unchanged.
+ *   sf_obstacle_multigrid_get: on as last set.
+ *   sf_precondition_masked(z, r): the operator singly, z = V_m(0, r); r read on interior cells (what it stores in solid
+ *       cells is never used), z written whole. SF_ERR_INVALID unless obstacles are on, the V-cycle is in force and the
+ *       setting is on, or if z == r. sf_precondition stays unmasked. */
+int sf_set_obstacle_multigrid(sf_ctx* ctx, int on);
+int sf_obstacle_multigrid_get(const sf_ctx* ctx, int* on);
+int sf_precondition_masked(sf_ctx* ctx, int z, int r);
 
 /* Axis-aligned volume rendering and light marching of docs/SPEC.md §12: an N x N image of the smoke from data that
  * already sits in device memory, instead of a (N+2)^3 frame over the bus. One ray per pixel runs along axis (0: i,

@@ -20,7 +20,9 @@ under its own time limit (--limit seconds, SIGALRM: the process ends with status
               iterations; without, on the host), the iterations to tol = 1e-3 from the same state and the time of that
               projection, and, for --step-case, the step with CG at each --tols. --mg NU[:LEVELS[:COARSE]],... adds the
               multigrid V-cycle of SPEC §11.3 at each of those settings to the same table (rows with "mg"), measured
-              on the same context, after the sweep counts.
+              on the same context, after the sweep counts. With --obstacle the masked runs take those settings too
+              (sf_set_obstacle_multigrid, SPEC §16), and every "mg" row carries vcycle_ms: one z = M(r) alone
+              (sf_precondition, or sf_precondition_masked under the mask), the best of --reps batches of ten.
   step        vel_step + dens_step per step (host wall time of --steps steps between syncs) with Jacobi K = 20 and with
               CG at each --tols, the iterations per step, and sf_poisson_residual / max_div of what the last step left.
 
@@ -29,6 +31,7 @@ under its own time limit (--limit seconds, SIGALRM: the process ends with status
   python tools/pressure_bench.py --sync --cases 64:f32 128:f32 256:f32 512:f32 256:f64   # where the scalars live
   python tools/pressure_bench.py --precond 0,2,4,8 --sync 8 --cases 64:f32 128:f32 256:f32 512:f32 256:f64
   python tools/pressure_bench.py --precond 0,8 --mg 2,2:0:16,1,2:4 --cases 64:f32 128:f32 256:f32 512:f32 256:f64
+  python tools/pressure_bench.py --precond 8 --mg 2:0:8,2:4:8 --obstacle centred --sync 8 --no-step --cases 256:f32 256:f64 512:f32
 """
 import argparse
 import json
@@ -178,6 +181,22 @@ def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters, obstacle
     fs.set_pressure_sync(check_every)
     if obstacle:
         fs.set_obstacles(obstacle_mask(N, dtype, obstacle), slot="dens0")
+        fs.set_obstacle_multigrid(True)  # (the V-cycle rows run the masked cycle of SPEC §16)
+
+    def vcycle_ms():
+        """One z = M(r) alone, between syncs: ten in a row, the best batch."""
+        apply = fs.precondition_masked if obstacle else fs.precondition
+        fs.upload("v0", state["u"])  # (any right-hand side: the cycle's time does not depend on it)
+        apply("u0", "v0")
+        best = 1e30
+        for _ in range(reps):
+            fs.sync()
+            t0 = time.perf_counter()
+            for _ in range(10):
+                apply("u0", "v0")
+            fs.sync()
+            best = min(best, (time.perf_counter() - t0) * 1e2)
+        return round(best, 5)
 
     def solve(tol, limit):
         for n, a in state.items():
@@ -201,6 +220,8 @@ def precond_case(N, dtype, iters, reps, sweeps, check_every, max_iters, obstacle
                      "iterations_1e-3": done["iterations"], "status_1e-3": done["status"],
                      "rel_residual": done["rel_residual"], "poisson_residual": fs.poisson_residual("u0", "v0"),
                      "projection_ms": round(tp, 4)})
+        if isinstance(m, tuple):
+            rows[-1]["vcycle_ms"] = vcycle_ms()
     fs.close()
     return rows
 
