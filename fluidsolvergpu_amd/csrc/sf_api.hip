@@ -279,6 +279,20 @@ int sf_obstacle_multigrid_get(const sf_ctx* ctx, int* on) {
 int sf_precondition_masked(sf_ctx* ctx, int z, int r) {
     return guarded(ctx, [&](SolverBase& s) { s.precondition_masked(z, r); });
 }
+int sf_set_obstacle_transport(sf_ctx* ctx, int on) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_obstacle_transport(on); });
+}
+int sf_obstacle_transport_get(const sf_ctx* ctx, int* on) {
+    if (!ctx || !ctx->impl || !on) return SF_ERR_INVALID;
+    ctx->impl->obstacle_transport(on);
+    return SF_OK;
+}
+int sf_diffuse_masked(sf_ctx* ctx, int b, int x, int x0, double diff) {
+    return guarded(ctx, [&](SolverBase& s) { s.diffuse_masked(b, x, x0, diff); });
+}
+int sf_advect_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w) {
+    return guarded(ctx, [&](SolverBase& s) { s.advect_masked(b, d, d0, u, v, w); });
+}
 int sf_render(sf_ctx* ctx, const sf_render_params* p) {
     return guarded(ctx, [&](SolverBase& s) { s.render(p); });
 }

@@ -28,7 +28,8 @@
 //             [--monitor M] [--pressure jacobi|cg[:tol[:max_iters]]] [--pressure-sync M]
 //             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
 //             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]
-//             [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]... [--obstacle-mg] [--help]
+//             [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]... [--obstacle-mg]
+//             [--obstacle-transport] [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -54,6 +55,8 @@
 // cells of docs/SPEC.md §15, in cell indices: the cells of the inclusive index box, or those whose centre index lies
 // within R of (CX, CY, CZ) — squared distance, in double, <= R^2. The union of all of them is the mask of sf_set_obstacles.
 // --obstacle-mg: lets --obstacle go with --pressure-mg: the masked V-cycle of docs/SPEC.md §16 (sf_set_obstacle_multigrid).
+// --obstacle-transport: diffusion and advection honour the obstacles too (docs/SPEC.md §17, sf_set_obstacle_transport);
+// needs --obstacle and does not go with --maccormack.
 // --render VIEW:SIGMA[:LIGHT]: at every output step an image of the density (docs/SPEC.md §12) next to the frame,
 // "render_<frame, 4 digits>.pgm" (several processes: "render_GPU<rank>_<frame>.pgm", each rank the pixel rows it holds).
 // VIEW and LIGHT are one of i+ i- j+ j- k+ k-: the axis of the rays and the side they enter from (+: at index 1). SIGMA
@@ -118,6 +121,7 @@ struct Options {
     };
     std::vector<Obstacle> obstacles;  // --obstacle (docs/SPEC.md §15)
     bool obstacle_mg = false;         // --obstacle-mg (docs/SPEC.md §16)
+    bool obstacle_transport = false;  // --obstacle-transport (docs/SPEC.md §17)
     double cg_tol = 1e-3;
     int render_axis = -1, render_high = 0, light_axis = -1, light_high = 0;  // --render (axis -1: off / no light)
     double render_sigma = 0.0;
@@ -205,6 +209,7 @@ static void usage(FILE* to) {
             "                 [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]   a pinhole camera at E looking at T\n"
             "                 [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]...   solid cells (with --pressure cg), up to 16\n"
             "                 [--obstacle-mg]   --obstacle together with --pressure-mg: the masked V-cycle\n"
+            "                 [--obstacle-transport]   diffusion and advection honour --obstacle too (not with --maccormack)\n"
             "                 [--loopback --rank R --world W] [--help]\n");
 }
 
@@ -439,6 +444,7 @@ static Options parse(int argc, char** argv) {
             o.obstacles.push_back(ob);
         }
         else if (s == "--obstacle-mg") o.obstacle_mg = true;
+        else if (s == "--obstacle-transport") o.obstacle_transport = true;
         else if (s == "--render") {
             // VIEW:SIGMA[:LIGHT]
             const std::string spec = next();
@@ -539,6 +545,14 @@ static Options parse(int argc, char** argv) {
     }
     if (!o.obstacles.empty() && (o.pressure != SF_PRESSURE_CG || (o.mg_sweeps > 0 && !o.obstacle_mg))) {
         fprintf(stderr, "--obstacle needs --pressure cg and does not go with --pressure-mg (docs/SPEC.md §15)\n");
+        exit(2);
+    }
+    if (o.obstacle_transport && o.obstacles.empty()) {
+        fprintf(stderr, "--obstacle-transport needs --obstacle (docs/SPEC.md §17)\n");
+        exit(2);
+    }
+    if (o.obstacle_transport && (o.advect_vel == SF_ADVECT_MACCORMACK || o.advect_dens == SF_ADVECT_MACCORMACK)) {
+        fprintf(stderr, "--obstacle-transport does not go with --maccormack (docs/SPEC.md §17)\n");
         exit(2);
     }
     // frames go to <out>/: create it (the reference writes into the working directory, which always exists)
@@ -794,6 +808,7 @@ static int run(const Options& o) {
         SF_CHECK_RETURN(sf_set_pressure_preconditioner(g_ctx, o.cg_precond, o.cg_precond_sweeps));
     if (o.mg_sweeps > 0) SF_CHECK_RETURN(sf_set_pressure_multigrid(g_ctx, o.mg_sweeps, o.mg_levels, o.mg_coarse));
     if (o.obstacle_mg) SF_CHECK_RETURN(sf_set_obstacle_multigrid(g_ctx, 1));
+    if (o.obstacle_transport) SF_CHECK_RETURN(sf_set_obstacle_transport(g_ctx, 1));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

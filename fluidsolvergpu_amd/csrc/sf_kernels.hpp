@@ -3554,6 +3554,192 @@ __global__ void __launch_bounds__(256) zero_solid_kernel(Geom g, ProjectMaskArgs
     }
 }
 
+// ---- Mask-aware transport (SPEC §17) ----
+// +0 into every shell entry of the face codes on the planes a slab is the owner of (face_code_kernel writes interior
+// cells only): advect_masked reads the code at its sample cells, and a sample in the shell is never solid. One thread
+// per stored row (j = 0 .. N+1) of the planes [kb, ke): the two i-shell cells, and the whole row where j or k is a
+// shell index.
+template <class T>
+__global__ void __launch_bounds__(256) code_shell_kernel(Geom g, T* __restrict__ code, int kb, int ke) {
+    const int S = g.N + 2;
+    const long t = (long)blockIdx.x * 256 + (long)threadIdx.x;
+    if (t >= (long)S * (ke - kb)) return;
+    const int kq = (int)(t / S);
+    const int kl = kb + kq, j = (int)(t - (long)kq * S);
+    const int kg = g.kg0 + kl;
+    const long r = row0(g, j, kl);
+    const bool whole = j == 0 || j == g.N + 1 || kg == 0 || kg == g.N + 1;
+    code[r] = T(0);
+    code[r + g.N + 1] = T(0);
+    if (whole)
+        for (int i = 1; i <= g.N; ++i) code[r + i] = T(0);
+}
+
+// lin_solve_masked: one Jacobi sweep of SPEC §3 with the neighbour operands of a fluid cell replaced by set_bnd's mirror
+// rule at a closed face (effn on the field's own axis, eff elsewhere), +0 on solid cells, set_bnd(b, x') fused. The row
+// shape, the lane exchange and the wave-uniform seam loads are cg_stencil_masked's; the NF fields share the row's code
+// vector. An empty mask (all codes 0) takes every stored neighbour: the bits of §3.
+template <class T, int NF>
+struct LinSolveMaskArgs {
+    const T* x[NF];
+    const T* x0[NF];
+    T* xn[NF];
+    int b[NF];
+    const T* code;
+    T a, inv;
+};
+
+template <class T, int NF>
+__global__ void __launch_bounds__(256) lin_solve_masked_kernel(Geom g, LinSolveMaskArgs<T, NF> A) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    const int lane = (int)threadIdx.x & 63;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V cv = ldv(A.code + q);
+        const int nv = cg_valid<W>(g, i0);
+        const int first = 1 + 64 * W * m;
+        const int next = first + 64 * W;
+        const int end = next < g.N + 1 ? next : g.N + 1;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            const T* __restrict__ x = A.x[f];
+            const V xc = ldv(x + q), bv = ldv(A.x0[f] + q);
+            const V jm = ldv(x + q - g.px), jp = ldv(x + q + g.px);
+            const V km = ldv(x + q - g.plane), kp = ldv(x + q + g.plane);
+            const T lo = x[r + first - 1], hi = x[r + end];
+            T left = lane_up(xc[W - 1]), right = lane_dn(xc[0]);
+            if (lane == 0) left = lo;
+            if (i0 + W == end) right = hi;
+            const int b = A.b[f];
+            T out[W];
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const int c = (int)cv[e];
+                const T self = xc[e];
+                const T mi = (b == 1) ? -self : self, mj = (b == 2) ? -self : self, mk = (b == 3) ? -self : self;
+                T l = (e == 0) ? left : xc[e - 1];
+                T rt = (e == W - 1) ? right : xc[e + 1];
+                l = (c & FC_ILO) ? mi : l;
+                rt = (c & FC_IHI) ? mi : rt;
+                const T a = (c & FC_JLO) ? mj : jm[e], bb = (c & FC_JHI) ? mj : jp[e];
+                const T d = (c & FC_KLO) ? mk : km[e], ff = (c & FC_KHI) ? mk : kp[e];
+                const T v = (bv[e] + A.a * (((l + rt) + (a + bb)) + (d + ff))) * A.inv;
+                out[e] = (c & FC_SOLID) ? T(0) : v;
+            }
+            if (nv > 0) {
+                store_cells<T, W>(A.xn[f], r, i0, out, nv);
+                emit_shells<T, W>(A.xn[f], g, b, i0, j, kl, out, nv);
+            }
+        }
+    }
+}
+
+// advect_masked: advect_kernel (the flat gather form, its clamps and its NaN guard) with each of
+// the eight samples of a fluid cell replaced by wv where the sample cell is solid: wv = d0[c] for b = 0, T(0) for
+// b = 1, 2, 3. The face codes are gathered as corner pairs at the sample addresses, once for the NF fields (a shell
+// entry holds +0: never solid), every replacement is a select on loaded values, +0 on solid cells, set_bnd(b, d) fused.
+// The trace does not stop at a solid. Unlike advect_kernel, whose source runs three loops over the W cells of the lane
+// (all back-traces, all gathers, the interpolation), this one is written as one loop over the cells, fully unrolled,
+// with every store after it. The three phases are then the scheduler's: in the ISA of all four instantiations every
+// gather of the lane (fp32: 32 / 64 pair loads for NF = 1 / 3, fp64: 16 / 32) is issued in one batch after the W
+// back-traces and before the first wait on it, as in the sibling (docs/NEXT.md). NF = 3: 185 / 174 VGPRs in fp32 /
+// fp64, no scratch.
+template <class T, int NF>
+struct AdvectMaskArgs {
+    AdvectArgs<T, NF> a;
+    const T* code;
+};
+
+template <class T, int NF>
+__global__ void __launch_bounds__(256) advect_masked_kernel(Geom g, AdvectMaskArgs<T, NF> M, int kb, int ke, TileMap m) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    typedef T Pair __attribute__((ext_vector_type(2), aligned(sizeof(T))));
+    const AdvectArgs<T, NF>& A = M.a;
+    const T* __restrict__ code = M.code;
+    int i0, j, kl, nv;
+    if (!flat_cell<W>(g, m, kb, ke, i0, j, kl, nv)) return;
+    const int N = g.N;
+    const T Nf = (T)N;
+    const T lo = T(0.5), hi = Nf + T(0.5);
+    const long q = row0(g, j, kl) + i0;
+    const V uu = ldv(A.u + q), vv = ldv(A.v + q), ww = ldv(A.w + q), cown = ldv(code + q);
+    V own[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) own[f] = ldv(A.d0[f] + q);
+    const int kg = g.kg0 + kl;
+    T out[NF][W];
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+        T x = (T)(i0 + e) - A.dt0 * uu[e];
+        T y = (T)j - A.dt0 * vv[e];
+        T z = (T)kg - A.dt0 * ww[e];
+        if (x < lo) x = lo;
+        if (x > hi) x = hi;
+        if (y < lo) y = lo;
+        if (y > hi) y = hi;
+        if (z < lo) z = lo;
+        if (z > hi) z = hi;
+        int ia = (x == x) ? (int)x : 0;
+        int ja = (y == y) ? (int)y : 0;
+        int ka = (z == z) ? (int)z : 0;
+        ia = ia < 0 ? 0 : (ia > N ? N : ia);
+        ja = ja < 0 ? 0 : (ja > N ? N : ja);
+        ka = ka < 0 ? 0 : (ka > N ? N : ka);
+        const T s1 = x - (T)ia, t1 = y - (T)ja, r1 = z - (T)ka;
+        int kla = ka - g.kg0;  // local plane of k0; k1 = kla + 1 must also be stored
+        if (kla < 0 || kla > g.np - 2) {
+            bad |= (e < nv);
+            kla = kla < 0 ? 0 : g.np - 2;
+        }
+        const long p00 = row0(g, ja, kla) + ia;  // (i0,j0,k0); +plane: k1; +px: j1
+        const long off[4] = {0, g.plane, g.px, g.px + g.plane};
+        Pair K[4], C[NF][4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) K[c] = *reinterpret_cast<const Pair*>(code + p00 + off[c]);
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) C[f][c] = *reinterpret_cast<const Pair*>(A.d0[f] + p00 + off[c]);
+        const T s0 = T(1) - s1, t0 = T(1) - t1, r0 = T(1) - r1;
+        bool sol[4][2];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            sol[c][0] = ((int)K[c][0] & FC_SOLID) != 0;
+            sol[c][1] = ((int)K[c][1] & FC_SOLID) != 0;
+        }
+        const bool solid = ((int)cown[e] & FC_SOLID) != 0;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            const T wv = (A.b[f] == 0) ? own[f][e] : T(0);
+            T c0[4], c1[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                c0[c] = sol[c][0] ? wv : C[f][c][0];
+                c1[c] = sol[c][1] ? wv : C[f][c][1];
+            }
+            const T val = s0 * (t0 * (r0 * c0[0] + r1 * c0[1]) + t1 * (r0 * c0[2] + r1 * c0[3])) +
+                          s1 * (t0 * (r0 * c1[0] + r1 * c1[1]) + t1 * (r0 * c1[2] + r1 * c1[3]));
+            out[f][e] = solid ? T(0) : val;
+        }
+    }
+    if (bad) atomicOr(A.flag, 1);
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        store_cells<T, W>(A.d[f], q - i0, i0, out[f], nv);
+        emit_shells<T, W>(A.d[f], g, A.b[f], i0, j, kl, out[f], nv);
+    }
+}
+
 // ---- Multigrid V-cycle preconditioner (SPEC §11.3) ----
 // Three row kernels on the fields of one level (a Geom of its own: n_l cells per axis, one ghost plane per side on the
 // coarse levels) with the row shape, the clamped unconditional loads and the stencil of the CG kernels above. They know

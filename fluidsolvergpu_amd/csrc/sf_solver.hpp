@@ -684,6 +684,10 @@ public:
         SF_REQUIRE(!(obst_on_ && mg_nu_ > 0) || obst_mg_,
                    "vel_step: obstacles with the multigrid preconditioner in force are not supported");
         const bool dead = ishell_skip_ && K_ >= 1 && dead_ishell_opt_ && !obst_on_;
+        // SPEC §17: diffuse and advect under the mask (sources added first; bound ones copied first: the same bits)
+        const bool masked_tr = obst_on_ && obst_tr_;
+        SF_REQUIRE(!(masked_tr && mc_vel_ == SF_ADVECT_MACCORMACK),
+                   "vel_step: MacCormack advection of the velocity under sf_set_obstacle_transport(1) is not supported");
         // SPEC §8: with a force on, the sources (bound slots, or the x0 slots themselves) plus the forces go into the
         // x0 slots first, and the step continues as with unbound sources
         const bool forces = eps_ != T(0) || beta_ != T(0);
@@ -692,7 +696,7 @@ public:
             for (int q = 0; q < 3; ++q) src[q] = bound_[q] >= 0 ? bound_[q] : vel0[q];
             op_add_forces(SF_U, SF_V, SF_W, SF_DENS, src, vel0);
         }
-        if (!forces && bound_[0] >= 0 && bound_[1] >= 0 && bound_[2] >= 0) {
+        if (!masked_tr && !forces && bound_[0] >= 0 && bound_[1] >= 0 && bound_[2] >= 0) {
             const int src[3] = {bound_[0], bound_[1], bound_[2]};
             op_diffuse_src<3>(vel, vel0, b123, src, a, T(1) + T(6) * a, K_, dead);
         } else {
@@ -702,7 +706,10 @@ public:
             swap_slots(SF_U0, SF_U);
             swap_slots(SF_V0, SF_V);
             swap_slots(SF_W0, SF_W);
-            op_lin_solve<3>(vel, vel0, b123, a, T(1) + T(6) * a, K_, dead);
+            if (masked_tr)
+                op_lin_solve_masked<3>(vel, vel0, b123, a, T(1) + T(6) * a, K_);
+            else
+                op_lin_solve<3>(vel, vel0, b123, a, T(1) + T(6) * a, K_, dead);
         }
         const bool cg = pressure_ == SF_PRESSURE_CG;
         if (cg)
@@ -713,7 +720,9 @@ public:
         swap_slots(SF_V0, SF_V);
         swap_slots(SF_W0, SF_W);
         // the advected velocity goes straight into the second projection: same argument as for the diffused one
-        if (mc_vel_ == SF_ADVECT_MACCORMACK)
+        if (masked_tr)
+            op_advect_masked<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0);
+        else if (mc_vel_ == SF_ADVECT_MACCORMACK)
             op_advect_mc<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
         else
             op_advect<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
@@ -727,6 +736,17 @@ public:
     void dens_step_body() {
         const int x[1] = {SF_DENS}, x0[1] = {SF_DENS0}, b0[1] = {0};
         const T a = diffusion_a(diff_);
+        if (obst_on_ && obst_tr_) {  // SPEC §17: nothing enters a solid, so nothing is zeroed at the end
+            SF_REQUIRE(mc_dens_ != SF_ADVECT_MACCORMACK,
+                       "dens_step: MacCormack advection of the density under sf_set_obstacle_transport(1) is not supported");
+            if (bound_[3] >= 0) copy_field(SF_DENS0, bound_[3]);
+            op_add_source<1>(x, x0);
+            swap_slots(SF_DENS0, SF_DENS);
+            op_lin_solve_masked<1>(x, x0, b0, a, T(1) + T(6) * a, K_);
+            swap_slots(SF_DENS0, SF_DENS);
+            op_advect_masked<1>(x, x0, b0, SF_U, SF_V, SF_W);
+            return;
+        }
         if (bound_[3] >= 0) {
             const int src[1] = {bound_[3]};
             op_diffuse_src<1>(x, x0, b0, src, a, T(1) + T(6) * a, K_, false);
@@ -1232,6 +1252,7 @@ public:
         finish_records(1, 1, 0, n);
         n_fluid_ = (long long)n[0];
         obst_on_ = true;
+        if (obst_tr_) code_shells_publish();
     }
     void obstacles(sf_obstacles* out) const override {
         out->enabled = obst_on_ ? 1 : 0;
@@ -1259,6 +1280,37 @@ public:
             for (int f : {z, r}) ensure(sl, f);
         join();
         op_precondition(mg_nu_, z, r, true);
+    }
+    // SPEC §17: with obstacles on, the diffuse and advect of both steps are the masked forms
+    void set_obstacle_transport(int on) override {
+        SF_REQUIRE(on == 0 || on == 1, "obstacle transport: on must be 0 or 1");
+        SF_HIP(hipSetDevice(device_));
+        sync();
+        for (GraphEntry& e : graph_cache_) (void)hipGraphExecDestroy(e.exec);  // a step of the other form
+        graph_cache_.clear();
+        obst_tr_ = on != 0;
+        if (obst_tr_ && obst_on_) code_shells_publish();
+    }
+    void obstacle_transport(int* on) const override { *on = obst_tr_ ? 1 : 0; }
+    void diffuse_masked(int b, int x, int x0, double diff) override {
+        check_field(x);
+        check_field(x0);
+        check_b(b);
+        SF_REQUIRE(x != x0, "diffuse_masked: x and x0 must be different fields");
+        SF_REQUIRE(obst_on_ && obst_tr_, "diffuse_masked: needs obstacles (sf_set_obstacles) and sf_set_obstacle_transport(1)");
+        SF_HIP(hipSetDevice(device_));
+        const int xs[1] = {x}, x0s[1] = {x0}, bs[1] = {b};
+        const T a = diffusion_a((T)diff);
+        op_lin_solve_masked<1>(xs, x0s, bs, a, T(1) + T(6) * a, K_);
+    }
+    void advect_masked(int b, int d, int d0, int u, int v, int w) override {
+        for (int f : {d, d0, u, v, w}) check_field(f);
+        check_b(b);
+        SF_REQUIRE(d != d0 && d != u && d != v && d != w, "advect_masked: output must not alias an input");
+        SF_REQUIRE(obst_on_ && obst_tr_, "advect_masked: needs obstacles (sf_set_obstacles) and sf_set_obstacle_transport(1)");
+        SF_HIP(hipSetDevice(device_));
+        const int ds[1] = {d}, d0s[1] = {d0}, bs[1] = {b};
+        op_advect_masked<1>(ds, d0s, bs, u, v, w);
     }
     void pressure_info(sf_pressure_info* out) const override { *out = info_; }
     void set_pressure_sync(int check_every) override {
@@ -2972,6 +3024,96 @@ private:
         publish_from_cs(x);
     }
 
+    // ---- mask-aware transport (SPEC §17) ----
+    // advect_masked reads the face codes at its sample cells: +0 into the shell entries of OBST_SLOT on the planes each
+    // slab is the owner of (face_code_kernel writes interior cells only), then its ghost planes.
+    void code_shells_publish() {
+        join();
+        for (Slab& sl : slabs_) {
+            const int kb = G_ - (sl.geom.wall_lo ? 1 : 0), ke = G_ + nzl_ + (sl.geom.wall_hi ? 1 : 0);
+            const long rows = (long)(N_ + 2) * (ke - kb);
+            hipLaunchKernelGGL(sfk::code_shell_kernel<T>, dim3((unsigned)ceil_div(rows, 256L)), dim3(256), 0, sl.cs, sl.geom,
+                               sl.field[OBST_SLOT], kb, ke);
+            SF_HIP(hipGetLastError());
+            tr_op("code_shells", sl, sl.cs, {{sl.field[OBST_SLOT], true, kb, ke}});
+        }
+        publish_from_cs(OBST_SLOT);
+    }
+    // K masked Jacobi sweeps on NF fields at once (§17 lin_solve_masked): one row launch per sweep and slab on the
+    // compute stream, the ghost planes of the new iterate after each; ping-pong with scratch[f] as op_lin_solve.
+    template <int NF>
+    void op_lin_solve_masked(const int (&x)[NF], const int (&x0)[NF], const int (&b)[NF], T a, T c, int K) {
+        static_assert(NF <= NSCRATCH, "not enough scratch buffers");
+        const T inv = T(1) / c;
+        for (Slab& sl : slabs_)
+            for (int f = 0; f < NF; ++f) {
+                ensure(sl, x[f]);
+                ensure(sl, x0[f]);
+            }
+        for (int it = 0; it < K; ++it) {
+            join();  // the ghost planes of the iterate
+            launch_rows<false>("lin_solve_masked", sfk::lin_solve_masked_kernel<T, NF>,
+                               [&](Slab& sl) {
+                                   sfk::LinSolveMaskArgs<T, NF> A{};
+                                   for (int f = 0; f < NF; ++f) {
+                                       A.x[f] = sl.field[x[f]];
+                                       A.x0[f] = sl.field[x0[f]];
+                                       A.xn[f] = sl.scratch[f];
+                                       A.b[f] = b[f];
+                                   }
+                                   A.code = sl.field[OBST_SLOT];
+                                   A.a = a;
+                                   A.inv = inv;
+                                   return A;
+                               },
+                               [&](Slab& sl) {
+                                   std::vector<Acc> acc{{sl.field[OBST_SLOT], false, G_, G_ + nzl_}};
+                                   for (int f = 0; f < NF; ++f) {
+                                       acc.push_back({sl.field[x[f]], false, G_ - 1, G_ + nzl_ + 1});
+                                       acc.push_back({sl.field[x0[f]], false, G_, G_ + nzl_});
+                                       acc.push_back(rows_written(sl, sl.scratch[f]));
+                                   }
+                                   return acc;
+                               });
+            // the new iterate becomes the field; the old buffer becomes scratch
+            for (Slab& sl : slabs_)
+                for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
+            if (P_ == 1) continue;
+            for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
+            exchange<NF>(x);
+        }
+    }
+    // §17 advect_masked: op_advect with the masked sibling of the gather form (the one form there is), which also
+    // reads the face codes wherever it reads d0.
+    template <int NF>
+    void op_advect_masked(const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u, int v, int w) {
+        for (Slab& sl : slabs_) {
+            for (int f = 0; f < NF; ++f) {
+                ensure(sl, d[f]);
+                ensure(sl, d0[f]);
+            }
+            for (int f : {u, v, w}) ensure(sl, f);
+        }
+        auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            for (int f = 0; f < NF; ++f) {
+                acc.push_back({sl.field[d0[f]], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[d[f]], true, lo, hi});
+            }
+            acc.push_back({sl.field[OBST_SLOT], false, a - 1, b_ + 1});
+            for (int q : {u, v, w}) acc.push_back({sl.field[q], false, a, b_});
+        };
+        for_planes("advect_masked", accesses, [&](const Launch& L) {
+            sfk::AdvectMaskArgs<T, NF> A;
+            fill_advect_args(A.a, L.sl, d, d0, b, u, v, w, false);
+            A.code = L.sl.field[OBST_SLOT];
+            dim3 block;
+            unsigned nblocks;
+            const sfk::TileMap m = flat_map(L, block, nblocks);
+            launch_k(L, sfk::advect_masked_kernel<T, NF>, dim3(nblocks), block, A, m);
+        }, 1, 0, /*interior_reads_ghosts=*/true);  // a long back-trace may reach a ghost plane from any plane
+        exchange<NF>(d);
+    }
+
     void note_solve(int solver, int status, int iterations, double rel) {
         info_.solver = solver;
         info_.status = status;
@@ -3828,6 +3970,7 @@ private:
     int check_every_ = 0, host_waits_ = 0;  // sf_set_pressure_sync; host waits of the last CG projection
     int precond_ = SF_PRECOND_NONE, precond_sweeps_ = 0;  // sf_set_pressure_preconditioner (SPEC §11.2)
     int mg_nu_ = 0, mg_maxl_ = 0, mg_nuc_ = 8;            // sf_set_pressure_multigrid (SPEC §11.3); nu = 0: off
+    bool obst_tr_ = false;      // sf_set_obstacle_transport (SPEC §17): with obstacles on, diffuse and advect are masked
     bool obst_mg_ = false;      // sf_set_obstacle_multigrid (SPEC §16): a masked solve under the V-cycle runs, masked
     bool mg_codes_ok_ = false;  // the face codes of the coarse levels match the mask and the levels in force
     bool obst_on_ = false;    // sf_set_obstacles (SPEC §15): the face codes of OBST_SLOT are in force

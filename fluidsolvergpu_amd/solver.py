@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     "sf_set_pressure_multigrid", "sf_pressure_multigrid_get", "sf_precondition",
     "sf_set_obstacles", "sf_obstacles_get",
     "sf_set_obstacle_multigrid", "sf_obstacle_multigrid_get", "sf_precondition_masked",
+    "sf_set_obstacle_transport", "sf_obstacle_transport_get", "sf_diffuse_masked", "sf_advect_masked",
     "sf_render", "sf_render_read", "sf_light",
     "sf_render_view", "sf_render_view_read", "sf_view_frame",
     "sf_render_camera", "sf_camera_passes_get", "sf_camera_frame",
@@ -168,6 +169,10 @@ lib.sf_obstacles_get.argtypes = [_ctx, C.POINTER(SfObstacles)]
 lib.sf_set_obstacle_multigrid.argtypes = [_ctx, C.c_int]
 lib.sf_obstacle_multigrid_get.argtypes = [_ctx, C.POINTER(C.c_int)]
 lib.sf_precondition_masked.argtypes = [_ctx, C.c_int, C.c_int]
+lib.sf_set_obstacle_transport.argtypes = [_ctx, C.c_int]
+lib.sf_obstacle_transport_get.argtypes = [_ctx, C.POINTER(C.c_int)]
+lib.sf_diffuse_masked.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_double]
+lib.sf_advect_masked.argtypes = [_ctx] + [C.c_int] * 6
 lib.sf_render.argtypes = [_ctx, C.POINTER(SfRenderParams)]
 lib.sf_render_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
 lib.sf_light.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
@@ -486,6 +491,28 @@ class FluidSolver:
         """z = V_m(0, r), the masked V-cycle of §16 singly: needs obstacles, the V-cycle and set_obstacle_multigrid(True).
         r is read on interior cells (solid cells never), z is written whole."""
         self._ck(lib.sf_precondition_masked(self._h, _fid(z), _fid(r)))
+
+    # -- mask-aware transport (docs/SPEC.md §17) ------------------------------------------------------
+    def set_obstacle_transport(self, on):
+        """on = True: with obstacles on, the diffuse and advect of vel_step and dens_step are the masked forms of §17
+        (nothing leaks into a solid; dens_step no longer zeroes the solids at its end); False (the default) keeps the
+        steps of §15. A step advected with MacCormack is refused while it is on. Valid in any order with
+        set_obstacles. Collective on several ranks; synchronises."""
+        self._ck(lib.sf_set_obstacle_transport(self._h, int(on) if isinstance(on, int) else (1 if on else 0)))
+
+    def obstacle_transport(self):
+        """The setting of set_obstacle_transport (sf_obstacle_transport_get)."""
+        on = C.c_int(0)
+        self._ck(lib.sf_obstacle_transport_get(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def diffuse_masked(self, b, x, x0, diff):
+        """diffuse under the mask (§17 diffuse_masked): needs obstacles and set_obstacle_transport(True)."""
+        self._ck(lib.sf_diffuse_masked(self._h, int(b), _fid(x), _fid(x0), float(diff)))
+
+    def advect_masked(self, b, d, d0, u, v, w):
+        """advect under the mask (§17 advect_masked): needs obstacles and set_obstacle_transport(True)."""
+        self._ck(lib.sf_advect_masked(self._h, int(b), _fid(d), _fid(d0), _fid(u), _fid(v), _fid(w)))
 
     # -- volume rendering and light marching (docs/SPEC.md §12) ---------------------------------
     def render(self, dens="dens", emit=None, axis=2, from_high=0, sigma=1.0):

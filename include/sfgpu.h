@@ -373,6 +373,30 @@ int sf_set_obstacle_multigrid(sf_ctx* ctx, int on);
 int sf_obstacle_multigrid_get(const sf_ctx* ctx, int* on);
 int sf_precondition_masked(sf_ctx* ctx, int z, int r);
 
+/* Mask-aware transport (docs/SPEC.md §17): diffusion and advection that honour the mask of §15, so that nothing leaks
+ * into a solid and has to be zeroed again. A Jacobi sweep reads a closed neighbour by set_bnd's mirror rule (the cell
+ * itself, negated for the field's own velocity component: b = 0 no flux into a solid, b = 1, 2, 3 no flow through it
+ * and free slip along it); advect replaces a sample that lies in a solid cell by the cell's own value (b = 0) or by 0
+ * (b = 1, 2, 3). Solid cells hold +0 after either. All selects on loaded values: a NaN parked in a solid cell reaches
+ * no fluid cell. A mask without a solid cell gives the bits of sf_diffuse / sf_advect. The back-trace is not stopped by
+ * a solid: a path across a thin one samples the far side.
+ *   sf_set_obstacle_transport(on): 0 (the default) keeps the steps of §15 with their launches; 1 makes, while obstacles
+ *       are on, the three diffuse and advect of sf_vel_step and those of sf_dens_step the masked forms (sources are
+ *       added first, bound ones copied into the x0 slots first: the same bits), and sf_dens_step no longer ends by
+ *       zeroing the solids. A step whose fields are advected with SF_ADVECT_MACCORMACK is then SF_ERR_INVALID with a
+ *       message. Valid in any order with sf_set_obstacles; while the setting is on, sf_set_obstacles also zeroes the
+ *       shell entries of the face codes and exchanges their ghost planes. Same bits for every decomposition and
+ *       transport. Collective; it synchronises and drops the graphs SF_GRAPH has cached. on outside 0 / 1:
+ *       SF_ERR_INVALID, and the setting is unchanged.
+ *   sf_obstacle_transport_get: on as last set.
+ *   sf_diffuse_masked(b, x, x0, diff), sf_advect_masked(b, d, d0, u, v, w): the operators singly, with the arguments,
+ *       the aliasing rules and (advect) the halo condition of sf_diffuse / sf_advect. SF_ERR_INVALID unless obstacles
+ *       are on and the setting is on. */
+int sf_set_obstacle_transport(sf_ctx* ctx, int on);
+int sf_obstacle_transport_get(const sf_ctx* ctx, int* on);
+int sf_diffuse_masked(sf_ctx* ctx, int b, int x, int x0, double diff);
+int sf_advect_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w);
+
 /* Axis-aligned volume rendering and light marching of docs/SPEC.md §12: an N x N image of the smoke from data that
  * already sits in device memory, instead of a (N+2)^3 frame over the bus. One ray per pixel runs along axis (0: i,
  * 1: j, 2: k) through the N interior cells of a line, entering at index 1 (from_high = 0) or N (from_high = 1). A cell
