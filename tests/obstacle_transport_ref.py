@@ -17,12 +17,58 @@ I = (slice(1, -1),) * 3
 AXIS = {"ilo": 1, "ihi": 1, "jlo": 2, "jhi": 2, "klo": 3, "khi": 3}
 WRONG = ("closed_stored", "eff_everywhere", "no_slip", "solids_not_zeroed", "sample_stored", "wv_zero_b0", "wv_own_bn",
          "solidity_of_i0", "shell_solid", "code_ghost_stale", "dens_zero_solid")
+# Wrong readings that only special values in the fluid tell from §17 (tests/test_obstacle_special_inputs_ref.py): two
+# names for `wrong`, and four stable_ref.Ops for `ops`: plausible rewrites of a masked kernel's arithmetic, the same
+# ones tests/test_stable_inputs_ref.py holds the unmasked §3 operators against.
+SPECIAL_WRONG = ("solid_as_product", "replace_as_blend")
 
 
-def sweep_masked(b, x, x0, a, inv, mk, wrong=None):
+def flush(x):
+    """Subnormals to a zero of the same sign."""
+    return np.where(np.abs(x) < np.finfo(x.dtype).tiny, x.dtype.type(0) * x, x)
+
+
+def hw_clamp(x, lo, hi):
+    return np.fmax(lo, np.fmin(hi, x))  # a hardware min / max: a NaN operand is ignored
+
+
+class ClampMinMax(S3.Ops):  # the advect clamps as fmax(lo, fmin(hi, x))
+    def trace(self, vel, dt0):
+        T = vel[0].dtype.type
+        N = vel[0].shape[0] - 2
+        idx, pos = [], []
+        for ax, comp in enumerate(vel):
+            shape = [1, 1, 1]
+            shape[2 - ax] = N
+            with np.errstate(invalid="ignore"):
+                x = hw_clamp(np.arange(1, N + 1).astype(T).reshape(shape) - dt0 * comp[I], T(0.5), T(N) + T(0.5))
+            idx.append(np.clip(x.astype(np.int64), 0, N))
+            pos.append(x)
+        return idx, pos
+
+
+class Flush(S3.Ops):  # subnormals flushed to zero on the way in and out of a masked sweep
+    def sweep_io(self, x):
+        return flush(x)
+
+
+class FaceMinus(S3.Ops):  # effn as T(0) - x
+    def neg(self, x):
+        return x.dtype.type(0) - x
+
+
+class SkipZeroWeight(S3.Ops):  # advect skips the i0 + 1 samples where s1 == 0
+    def combine(self, s0, lo, s1, hi):
+        return np.where(s1 == 0, s0 * lo, s0 * lo + s1 * hi)
+
+
+MUTANTS = (ClampMinMax, Flush, FaceMinus, SkipZeroWeight)
+
+
+def sweep_masked(b, x, x0, a, inv, mk, wrong=None, ops=S3.SPEC):
     """The interior of one sweep of lin_solve_masked: the neighbour operand of a face on axis A is effn when b == A and
     eff otherwise; +0 on solid cells."""
-    T = x.dtype.type
+    x, x0 = ops.sweep_io(x), ops.sweep_io(x0)
 
     def e(face):
         if wrong == "closed_stored":
@@ -32,14 +78,14 @@ def sweep_masked(b, x, x0, a, inv, mk, wrong=None):
             sign = 1
         if wrong == "no_slip" and b != 0:
             sign = -1
-        return mk.eff(x, face, sign)
+        return mk.eff(x, face, sign, ops)
 
     with np.errstate(invalid="ignore", over="ignore"):
         val = (x0[I] + a * (((e("ilo") + e("ihi")) + (e("jlo") + e("jhi"))) + (e("klo") + e("khi")))) * inv
-    return val if wrong == "solids_not_zeroed" else np.where(mk.solid, T(0), val)
+    return val if wrong == "solids_not_zeroed" else mk.zeroed(ops.sweep_io(val), wrong)
 
 
-def lin_solve_masked(b, x, x0, a, c, K, mask, wrong=None):
+def lin_solve_masked(b, x, x0, a, c, K, mask, wrong=None, ops=S3.SPEC):
     """§17 lin_solve_masked, in place in x (K = 0: a no-op)."""
     T = x.dtype.type
     mk = OB.Mask(mask)
@@ -47,20 +93,20 @@ def lin_solve_masked(b, x, x0, a, c, K, mask, wrong=None):
     cur = x.copy()
     for _ in range(K):
         nxt = np.zeros_like(cur)
-        nxt[I] = sweep_masked(b, cur, x0, a, inv, mk, wrong)
+        nxt[I] = sweep_masked(b, cur, x0, a, inv, mk, wrong, ops)
         S3.set_bnd(b, nxt)
         cur = nxt
     x[...] = cur
 
 
-def diffuse_masked(b, x, x0, diff, dt, K, mask, wrong=None):
+def diffuse_masked(b, x, x0, diff, dt, K, mask, wrong=None, ops=S3.SPEC):
     T = x.dtype.type
     Nf = T(x.shape[0] - 2)
     a = ((T(dt) * T(diff)) * Nf) * Nf
-    lin_solve_masked(b, x, x0, a, T(1) + T(6) * a, K, mask, wrong)
+    lin_solve_masked(b, x, x0, a, T(1) + T(6) * a, K, mask, wrong, ops)
 
 
-def advect_masked(b, d, d0, u, v, w, dt, mask, wrong=None, slabs=1):
+def advect_masked(b, d, d0, u, v, w, dt, mask, wrong=None, slabs=1, ops=S3.SPEC):
     """§17 advect_masked: §3's advect with each sample solid(s) ? wv : d0[s], +0 on solid cells, set_bnd(b, d).
     slabs (wrong "code_ghost_stale" only): the k-slabs whose codes a stale ghost plane hides from each other."""
     T = d.dtype.type
@@ -71,7 +117,7 @@ def advect_masked(b, d, d0, u, v, w, dt, mask, wrong=None, slabs=1):
         with np.errstate(invalid="ignore"):
             solid = mask > 0
     dt0 = T(dt) * T(N)
-    (i0, j0, k0), (x, y, z) = S3.SPEC.trace((u, v, w), dt0)
+    (i0, j0, k0), (x, y, z) = ops.trace((u, v, w), dt0)
     own = d0[I]
     carries = b == 0  # wv = d0[c] for b = 0, T(0) for a velocity component
     if wrong == "wv_zero_b0" and b == 0:
@@ -92,17 +138,19 @@ def advect_masked(b, d, d0, u, v, w, dt, mask, wrong=None, slabs=1):
             if wrong == "code_ghost_stale":  # the code across a slab boundary reads as fluid
                 inner = (ks >= 1) & (ks <= N)
                 sol = sol & ~(inner & ((ks - 1) // nzl != (kc - 1) // nzl))
+            if wrong == "replace_as_blend":  # val + s (wv - val) with s = 1 on a solid sample, 0 on a fluid one
+                return val + sol.astype(T) * (wv - val)
             return val if wrong == "sample_stored" else np.where(sol, wv, val)
 
         def plane(di):
             return (t0 * (r0 * at(di, 0, 0) + r1 * at(di, 0, 1)) + t1 * (r0 * at(di, 1, 0) + r1 * at(di, 1, 1)))
 
-        val = s0 * plane(0) + s1 * plane(1)
-    d[I] = np.where(mk.solid, T(0), val)
+        val = ops.combine(s0, plane(0), s1, plane(1))
+        d[I] = mk.zeroed(val, wrong)
     S3.set_bnd(b, d)
 
 
-def vel_step(f, mask, K, dt, visc, project, sources=None, forces=None, wrong=None):
+def vel_step(f, mask, K, dt, visc, project, sources=None, forces=None, wrong=None, ops=S3.SPEC):
     """§17 vel_step on copies of the velocity fields of f. project(u, v, w): the masked projection in force, returning
     the dict of obstacles_ref.project_cg. sources: bound sources, copied into the x0 fields first; forces: the keywords
     of forces_ref.add_forces (SPEC §8; reads f["dens"]). Returns the second projection's outcome."""
@@ -115,24 +163,24 @@ def vel_step(f, mask, K, dt, visc, project, sources=None, forces=None, wrong=Non
         S3.add_source(x, s, dt)
     u, u0, v, v0, w, w0 = u0, u, v0, v, w0, w
     for b, x, x0 in ((1, u, u0), (2, v, v0), (3, w, w0)):
-        diffuse_masked(b, x, x0, visc, dt, K, mask, wrong)
+        diffuse_masked(b, x, x0, visc, dt, K, mask, wrong, ops)
     out = project(u, v, w)
     u0, v0, w0 = out["u"], out["v"], out["w"]
     u, v, w = (np.zeros_like(u0) for _ in range(3))
     for b, d, d0 in ((1, u, u0), (2, v, v0), (3, w, w0)):
-        advect_masked(b, d, d0, u0, v0, w0, dt, mask, wrong)
+        advect_masked(b, d, d0, u0, v0, w0, dt, mask, wrong, ops=ops)
     return project(u, v, w)
 
 
-def dens_step(dens, dens0, u, v, w, mask, K, dt, diff, source=None, wrong=None):
+def dens_step(dens, dens0, u, v, w, mask, K, dt, diff, source=None, wrong=None, ops=S3.SPEC):
     """§17 dens_step on copies: add_source, diffuse_masked(0), advect_masked(0); no zero_solid. Returns the density."""
     x, x0 = dens.copy(), (source if source is not None else dens0).copy()
     S3.add_source(x, x0, dt)
     x, x0 = x0, x
-    diffuse_masked(0, x, x0, diff, dt, K, mask, wrong)
+    diffuse_masked(0, x, x0, diff, dt, K, mask, wrong, ops)
     x, x0 = x0, x
     if wrong == "dens_zero_solid":  # §15's end of the step kept: the unmasked advect, then the solids zeroed
         S3.advect(0, x, x0, u, v, w, dt)
         return OB.zero_solids(x, mask)
-    advect_masked(0, x, x0, u, v, w, dt, mask, wrong)
+    advect_masked(0, x, x0, u, v, w, dt, mask, wrong, ops=ops)
     return x

@@ -21,6 +21,9 @@ FACES = (("ilo", (I, I, M)), ("ihi", (I, I, P)), ("jlo", (I, M, I)), ("jhi", (I,
          ("khi", (P, I, I)))
 WRONG = ("closed_zero", "div_stored", "mu_n3", "grad_unmasked", "solids_not_zeroed", "faces_swapped", "nan_solid",
          "ghost_fluid", "r_not_zeroed")
+# wrong readings that only special values (zeros of either sign, subnormals, non-finite values) in the fluid tell from the
+# SPEC's: tests/test_obstacle_special_inputs_ref.py. FaceMinus is an `ops` (stable_ref.Ops with neg as T(0) - x).
+SPECIAL_WRONG = ("grad_add", "solid_as_product")
 
 
 def solid_cells(mask, wrong=None):
@@ -51,23 +54,30 @@ class Mask:
             self.closed = {"ilo": c["ihi"], "ihi": c["ilo"], "jlo": c["jhi"], "jhi": c["jlo"], "klo": c["khi"],
                            "khi": c["klo"]}
 
-    def eff(self, x, face, sign=1):
+    def eff(self, x, face, sign=1, ops=S3.SPEC):
         """eff (sign 1) / effn (sign -1) of one face on all interior cells: the cell itself where the face is closed,
         the neighbour as stored where it is open."""
         nb = dict(FACES)[face]
-        own = x[I, I, I] if sign == 1 else -x[I, I, I]
+        own = x[I, I, I] if sign == 1 else ops.neg(x[I, I, I])
         return np.where(self.closed[face], own, x[nb])
 
+    def zeroed(self, val, wrong=None):
+        """solid ? +0 : val."""
+        if wrong == "solid_as_product":
+            with np.errstate(invalid="ignore"):
+                return val * self.fluid.astype(val.dtype)
+        return np.where(self.solid, val.dtype.type(0), val)
 
-def divergence(u, v, w, mk, wrong=None):
+
+def divergence(u, v, w, mk, wrong=None, ops=S3.SPEC):
     """§15 step 1: (p, div) with both set_bnd(0, .)."""
     T = u.dtype.type
     N = u.shape[0] - 2
     c_div = T(-0.5) * (T(1) / T(N))
-    e = (lambda x, f: x[dict(FACES)[f]]) if wrong == "div_stored" else (lambda x, f: mk.eff(x, f, -1))
+    e = (lambda x, f: x[dict(FACES)[f]]) if wrong == "div_stored" else (lambda x, f: mk.eff(x, f, -1, ops))
     div = np.zeros_like(u)
     val = c_div * (((e(u, "ihi") - e(u, "ilo")) + (e(v, "jhi") - e(v, "jlo"))) + (e(w, "khi") - e(w, "klo")))
-    div[I, I, I] = np.where(mk.solid, T(0), val)
+    div[I, I, I] = mk.zeroed(val, wrong)
     R.set_bnd(0, div)
     return np.zeros_like(u), div
 
@@ -87,14 +97,17 @@ def subtract_gradient(u, v, w, p, mk, wrong=None):
     c_grad = T(0.5) * T(N)
     e = (lambda f: p[dict(FACES)[f]]) if wrong == "grad_unmasked" else (lambda f: mk.eff(p, f))
     for x, lo, hi in ((u, "ilo", "ihi"), (v, "jlo", "jhi"), (w, "klo", "khi")):
-        val = x[I, I, I] - c_grad * (e(hi) - e(lo))
-        x[I, I, I] = val if wrong == "solids_not_zeroed" else np.where(mk.solid, T(0), val)
+        if wrong == "grad_add":
+            val = x[I, I, I] + c_grad * (e(lo) - e(hi))
+        else:
+            val = x[I, I, I] - c_grad * (e(hi) - e(lo))
+        x[I, I, I] = val if wrong == "solids_not_zeroed" else mk.zeroed(val, wrong)
     R.set_bnd(1, u)
     R.set_bnd(2, v)
     R.set_bnd(3, w)
 
 
-def project_cg(u, v, w, mask, tol, max_iters, m=0, slabs=1, history=None, wrong=None):
+def project_cg(u, v, w, mask, tol, max_iters, m=0, slabs=1, history=None, wrong=None, ops=S3.SPEC):
     """SPEC §15 masked project_cg (m Jacobi sweeps of §11.2 as the preconditioner; 0: §11) on copies of u, v, w. Returns
     the dict of pressure_cg_ref.project_cg."""
     dtype = u.dtype
@@ -104,7 +117,7 @@ def project_cg(u, v, w, mask, tol, max_iters, m=0, slabs=1, history=None, wrong=
     u, v, w = u.copy(), v.copy(), w.copy()
     pc = m > 0
     with np.errstate(all="ignore"):
-        p, div = divergence(u, v, w, mk, wrong)
+        p, div = divergence(u, v, w, mk, wrong, ops)
         s = R.tree_sum(div[I, I, I].astype(np.float64), dtype, slabs)
         count = N ** 3 if wrong == "mu_n3" else mk.n_fluid
         mu = T(s / float(count)) if count else T(0)

@@ -53,6 +53,16 @@ class Ops:
         """The clamp of a tracer coordinate (SPEC §6)."""
         return where_clamp(x, lo, hi)
 
+    # the masked operators (SPEC §15 to §17: obstacles_ref, obstacles_mg_ref, obstacle_transport_ref) state their own
+    # stencils; what they share with the methods above is trace, combine and these two
+    def neg(self, x):
+        """effn: the cell's own value as the operand across a closed face on the field's own axis."""
+        return -x
+
+    def sweep_io(self, x):
+        """A field as a masked sweep loads it, and the values the sweep stores."""
+        return x
+
 
 SPEC = Ops()
 
