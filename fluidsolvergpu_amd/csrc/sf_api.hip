@@ -293,6 +293,17 @@ int sf_diffuse_masked(sf_ctx* ctx, int b, int x, int x0, double diff) {
 int sf_advect_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w) {
     return guarded(ctx, [&](SolverBase& s) { s.advect_masked(b, d, d0, u, v, w); });
 }
+int sf_set_obstacle_maccormack(sf_ctx* ctx, int on) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_obstacle_maccormack(on); });
+}
+int sf_obstacle_maccormack_get(const sf_ctx* ctx, int* on) {
+    if (!ctx || !ctx->impl || !on) return SF_ERR_INVALID;
+    ctx->impl->obstacle_maccormack(on);
+    return SF_OK;
+}
+int sf_advect_maccormack_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w) {
+    return guarded(ctx, [&](SolverBase& s) { s.advect_maccormack_masked(b, d, d0, u, v, w); });
+}
 int sf_render(sf_ctx* ctx, const sf_render_params* p) {
     return guarded(ctx, [&](SolverBase& s) { s.render(p); });
 }

@@ -127,6 +127,9 @@ public:
     virtual void obstacle_transport(int* on) const = 0;
     virtual void diffuse_masked(int b, int x, int x0, double diff) = 0;
     virtual void advect_masked(int b, int d, int d0, int u, int v, int w) = 0;
+    virtual void set_obstacle_maccormack(int on) = 0;
+    virtual void obstacle_maccormack(int* on) const = 0;
+    virtual void advect_maccormack_masked(int b, int d, int d0, int u, int v, int w) = 0;
     virtual void render(const sf_render_params* p) = 0;
     virtual void render_read(void* colour, void* transmittance) = 0;
     virtual void light(int dst, int dens, int axis, int from_high, double sigma) = 0;

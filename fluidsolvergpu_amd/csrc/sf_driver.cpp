@@ -29,7 +29,7 @@
 //             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
 //             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]
 //             [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]... [--obstacle-mg]
-//             [--obstacle-transport] [--help]
+//             [--obstacle-transport] [--obstacle-maccormack] [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -57,6 +57,8 @@
 // --obstacle-mg: lets --obstacle go with --pressure-mg: the masked V-cycle of docs/SPEC.md §16 (sf_set_obstacle_multigrid).
 // --obstacle-transport: diffusion and advection honour the obstacles too (docs/SPEC.md §17, sf_set_obstacle_transport);
 // needs --obstacle and does not go with --maccormack.
+// --obstacle-maccormack: lets --obstacle-transport go with --maccormack: the masked MacCormack advection of
+// docs/SPEC.md §18 (sf_set_obstacle_maccormack); needs --obstacle-transport.
 // --render VIEW:SIGMA[:LIGHT]: at every output step an image of the density (docs/SPEC.md §12) next to the frame,
 // "render_<frame, 4 digits>.pgm" (several processes: "render_GPU<rank>_<frame>.pgm", each rank the pixel rows it holds).
 // VIEW and LIGHT are one of i+ i- j+ j- k+ k-: the axis of the rays and the side they enter from (+: at index 1). SIGMA
@@ -122,6 +124,7 @@ struct Options {
     std::vector<Obstacle> obstacles;  // --obstacle (docs/SPEC.md §15)
     bool obstacle_mg = false;         // --obstacle-mg (docs/SPEC.md §16)
     bool obstacle_transport = false;  // --obstacle-transport (docs/SPEC.md §17)
+    bool obstacle_mc = false;         // --obstacle-maccormack (docs/SPEC.md §18)
     double cg_tol = 1e-3;
     int render_axis = -1, render_high = 0, light_axis = -1, light_high = 0;  // --render (axis -1: off / no light)
     double render_sigma = 0.0;
@@ -210,6 +213,7 @@ static void usage(FILE* to) {
             "                 [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]...   solid cells (with --pressure cg), up to 16\n"
             "                 [--obstacle-mg]   --obstacle together with --pressure-mg: the masked V-cycle\n"
             "                 [--obstacle-transport]   diffusion and advection honour --obstacle too (not with --maccormack)\n"
+            "                 [--obstacle-maccormack]   --obstacle-transport together with --maccormack: masked MacCormack\n"
             "                 [--loopback --rank R --world W] [--help]\n");
 }
 
@@ -445,6 +449,7 @@ static Options parse(int argc, char** argv) {
         }
         else if (s == "--obstacle-mg") o.obstacle_mg = true;
         else if (s == "--obstacle-transport") o.obstacle_transport = true;
+        else if (s == "--obstacle-maccormack") o.obstacle_mc = true;
         else if (s == "--render") {
             // VIEW:SIGMA[:LIGHT]
             const std::string spec = next();
@@ -551,7 +556,12 @@ static Options parse(int argc, char** argv) {
         fprintf(stderr, "--obstacle-transport needs --obstacle (docs/SPEC.md §17)\n");
         exit(2);
     }
-    if (o.obstacle_transport && (o.advect_vel == SF_ADVECT_MACCORMACK || o.advect_dens == SF_ADVECT_MACCORMACK)) {
+    if (o.obstacle_mc && !o.obstacle_transport) {
+        fprintf(stderr, "--obstacle-maccormack needs --obstacle-transport (docs/SPEC.md §18)\n");
+        exit(2);
+    }
+    if (o.obstacle_transport && !o.obstacle_mc &&
+        (o.advect_vel == SF_ADVECT_MACCORMACK || o.advect_dens == SF_ADVECT_MACCORMACK)) {
         fprintf(stderr, "--obstacle-transport does not go with --maccormack (docs/SPEC.md §17)\n");
         exit(2);
     }
@@ -809,6 +819,7 @@ static int run(const Options& o) {
     if (o.mg_sweeps > 0) SF_CHECK_RETURN(sf_set_pressure_multigrid(g_ctx, o.mg_sweeps, o.mg_levels, o.mg_coarse));
     if (o.obstacle_mg) SF_CHECK_RETURN(sf_set_obstacle_multigrid(g_ctx, 1));
     if (o.obstacle_transport) SF_CHECK_RETURN(sf_set_obstacle_transport(g_ctx, 1));
+    if (o.obstacle_mc) SF_CHECK_RETURN(sf_set_obstacle_maccormack(g_ctx, 1));
 
     // frame buffers: the planes this process owns, nothing else
     const size_t n = ((size_t)o.n + 2) * ((size_t)o.n + 2) * (size_t)(own_ke - own_kb);

@@ -3740,6 +3740,94 @@ __global__ void __launch_bounds__(256) advect_masked_kernel(Geom g, AdvectMaskAr
     }
 }
 
+// advect_mc_masked (SPEC §18 pass 2): advect_mc_kernel (the flat gather form, mc_trace and mc_cell as they are) with
+// the fallback of a cell extended from `either trace clamped` to `either trace clamped or any of its sixteen sample
+// cells solid`, and +0 on solid cells. hat is the result of advect_masked_kernel. The face codes are gathered as corner
+// pairs at the sample addresses of both traces (8 pair loads per cell, a shell entry holds +0: never solid) and reduced
+// to one bool per cell before the field loop, which is the sibling's: all gathers of d0 and hat of a field requested,
+// then consumed. Whatever mn, mx or bar picked up from a solid sample is discarded by the last select of mc_cell.
+template <class T, int NF>
+struct AdvectMcMaskArgs {
+    AdvectMcArgs<T, NF> a;
+    const T* code;
+};
+
+template <class T, int NF>
+__global__ void __launch_bounds__(256) advect_mc_masked_kernel(Geom g, AdvectMcMaskArgs<T, NF> M, int kb, int ke,
+                                                               TileMap m) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    typedef T Pair __attribute__((ext_vector_type(2), aligned(sizeof(T))));
+    const AdvectMcArgs<T, NF>& A = M.a;
+    const T* __restrict__ code = M.code;
+    int i0, j, kl, nv;
+    if (!flat_cell<W>(g, m, kb, ke, i0, j, kl, nv)) return;
+    const long q = row0(g, j, kl) + i0;
+    const V uu = ldv(A.u + q), vv = ldv(A.v + q), ww = ldv(A.w + q), cown = ldv(code + q);
+    const int kg = g.kg0 + kl;
+    // (cells past the row end: as in advect_mc_kernel)
+    McTrace<T> F[W], R[W];
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+        const T au = A.dt0 * uu[e], av = A.dt0 * vv[e], aw = A.dt0 * ww[e];
+        F[e] = mc_trace<T>(g, (T)(i0 + e) - au, (T)j - av, (T)kg - aw);
+        R[e] = mc_trace<T>(g, (T)(i0 + e) + au, (T)j + av, (T)kg + aw);
+        bad |= (e < nv) && (F[e].outside || R[e].outside);
+    }
+    const long off[4] = {0, g.plane, g.px, g.px + g.plane};
+    bool fallback[W], solid[W];
+    {
+        Pair KF[W][4], KR[W][4];
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                KF[e][c] = *reinterpret_cast<const Pair*>(code + F[e].p00 + off[c]);
+                KR[e][c] = *reinterpret_cast<const Pair*>(code + R[e].p00 + off[c]);
+            }
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            int any = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) any |= (int)KF[e][c][0] | (int)KF[e][c][1] | (int)KR[e][c][0] | (int)KR[e][c][1];
+            fallback[e] = F[e].clamped || R[e].clamped || (any & FC_SOLID) != 0;
+            solid[e] = ((int)cown[e] & FC_SOLID) != 0;
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const T* __restrict__ d0 = A.d0[f];
+        const T* __restrict__ hat = A.hat[f];
+        Pair CA[W][4], CH[W][4];
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                CA[e][c] = *reinterpret_cast<const Pair*>(d0 + F[e].p00 + off[c]);
+                CH[e][c] = *reinterpret_cast<const Pair*>(hat + R[e].p00 + off[c]);
+            }
+        const V dq = ldv(d0 + q), hq = ldv(hat + q);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            T a0[4], a1[4], h0[4], h1[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                a0[c] = CA[e][c][0];
+                a1[c] = CA[e][c][1];
+                h0[c] = CH[e][c][0];
+                h1[c] = CH[e][c][1];
+            }
+            const T r = mc_cell<T>(a0, a1, h0, h1, R[e], hq[e], dq[e], fallback[e]);
+            out[e] = solid[e] ? T(0) : r;
+        }
+        store_cells<T, W>(A.d[f], q - i0, i0, out, nv);
+        emit_shells<T, W>(A.d[f], g, A.b[f], i0, j, kl, out, nv);
+    }
+    if (bad) atomicOr(A.flag, 1);
+}
+
 // ---- Multigrid V-cycle preconditioner (SPEC §11.3) ----
 // Three row kernels on the fields of one level (a Geom of its own: n_l cells per axis, one ghost plane per side on the
 // coarse levels) with the row shape, the clamped unconditional loads and the stencil of the CG kernels above. They know

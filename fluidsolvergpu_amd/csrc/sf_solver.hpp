@@ -686,7 +686,7 @@ public:
         const bool dead = ishell_skip_ && K_ >= 1 && dead_ishell_opt_ && !obst_on_;
         // SPEC §17: diffuse and advect under the mask (sources added first; bound ones copied first: the same bits)
         const bool masked_tr = obst_on_ && obst_tr_;
-        SF_REQUIRE(!(masked_tr && mc_vel_ == SF_ADVECT_MACCORMACK),
+        SF_REQUIRE(!(masked_tr && mc_vel_ == SF_ADVECT_MACCORMACK) || obst_mc_,
                    "vel_step: MacCormack advection of the velocity under sf_set_obstacle_transport(1) is not supported");
         // SPEC §8: with a force on, the sources (bound slots, or the x0 slots themselves) plus the forces go into the
         // x0 slots first, and the step continues as with unbound sources
@@ -720,7 +720,9 @@ public:
         swap_slots(SF_V0, SF_V);
         swap_slots(SF_W0, SF_W);
         // the advected velocity goes straight into the second projection: same argument as for the diffused one
-        if (masked_tr)
+        if (masked_tr && mc_vel_ == SF_ADVECT_MACCORMACK)  // SPEC §18 (obst_mc_: required above)
+            op_advect_mc_masked<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0);
+        else if (masked_tr)
             op_advect_masked<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0);
         else if (mc_vel_ == SF_ADVECT_MACCORMACK)
             op_advect_mc<3>(vel, vel0, b123, SF_U0, SF_V0, SF_W0, dead);
@@ -737,14 +739,17 @@ public:
         const int x[1] = {SF_DENS}, x0[1] = {SF_DENS0}, b0[1] = {0};
         const T a = diffusion_a(diff_);
         if (obst_on_ && obst_tr_) {  // SPEC §17: nothing enters a solid, so nothing is zeroed at the end
-            SF_REQUIRE(mc_dens_ != SF_ADVECT_MACCORMACK,
+            SF_REQUIRE(mc_dens_ != SF_ADVECT_MACCORMACK || obst_mc_,
                        "dens_step: MacCormack advection of the density under sf_set_obstacle_transport(1) is not supported");
             if (bound_[3] >= 0) copy_field(SF_DENS0, bound_[3]);
             op_add_source<1>(x, x0);
             swap_slots(SF_DENS0, SF_DENS);
             op_lin_solve_masked<1>(x, x0, b0, a, T(1) + T(6) * a, K_);
             swap_slots(SF_DENS0, SF_DENS);
-            op_advect_masked<1>(x, x0, b0, SF_U, SF_V, SF_W);
+            if (mc_dens_ == SF_ADVECT_MACCORMACK)  // SPEC §18
+                op_advect_mc_masked<1>(x, x0, b0, SF_U, SF_V, SF_W);
+            else
+                op_advect_masked<1>(x, x0, b0, SF_U, SF_V, SF_W);
             return;
         }
         if (bound_[3] >= 0) {
@@ -1311,6 +1316,26 @@ public:
         SF_HIP(hipSetDevice(device_));
         const int ds[1] = {d}, d0s[1] = {d0}, bs[1] = {b};
         op_advect_masked<1>(ds, d0s, bs, u, v, w);
+    }
+    // SPEC §18: with obstacles and transport on, a MacCormack scheme runs advect_mc_masked instead of the refusal
+    void set_obstacle_maccormack(int on) override {
+        SF_REQUIRE(on == 0 || on == 1, "obstacle maccormack: on must be 0 or 1");
+        SF_HIP(hipSetDevice(device_));
+        sync();
+        for (GraphEntry& e : graph_cache_) (void)hipGraphExecDestroy(e.exec);  // a step of the other form
+        graph_cache_.clear();
+        obst_mc_ = on != 0;
+    }
+    void obstacle_maccormack(int* on) const override { *on = obst_mc_ ? 1 : 0; }
+    void advect_maccormack_masked(int b, int d, int d0, int u, int v, int w) override {
+        for (int f : {d, d0, u, v, w}) check_field(f);
+        check_b(b);
+        SF_REQUIRE(d != d0 && d != u && d != v && d != w, "advect_maccormack_masked: output must not alias an input");
+        SF_REQUIRE(obst_on_ && obst_tr_,
+                   "advect_maccormack_masked: needs obstacles (sf_set_obstacles) and sf_set_obstacle_transport(1)");
+        SF_HIP(hipSetDevice(device_));
+        const int ds[1] = {d}, d0s[1] = {d0}, bs[1] = {b};
+        op_advect_mc_masked<1>(ds, d0s, bs, u, v, w);
     }
     void pressure_info(sf_pressure_info* out) const override { *out = info_; }
     void set_pressure_sync(int check_every) override {
@@ -3113,6 +3138,44 @@ private:
         }, 1, 0, /*interior_reads_ghosts=*/true);  // a long back-trace may reach a ghost plane from any plane
         exchange<NF>(d);
     }
+    // §18 advect_mc_masked: pass 1 is op_advect_masked into `hat` (every shell written, ghost planes exchanged), pass 2
+    // the masked sibling of advect_mc's gather form, which reads the face codes wherever either trace samples.
+    template <int NF>
+    void op_advect_mc_masked(const int (&d)[NF], const int (&d0)[NF], const int (&b)[NF], int u, int v, int w) {
+        static_assert(NF <= NSCRATCH, "not enough scratch buffers");
+        for (Slab& sl : slabs_) {
+            for (int f = 0; f < NF; ++f) {
+                ensure(sl, d[f]);
+                ensure(sl, d0[f]);
+            }
+            for (int f : {u, v, w}) ensure(sl, f);
+        }
+        // hat lives in the scratch buffers, addressed through the HAT slots while this operator is issued
+        ScratchAlias hat_slots(slabs_, NF);
+        int hat[NF];
+        for (int f = 0; f < NF; ++f) hat[f] = HAT_SLOT + f;
+        op_advect_masked<NF>(hat, d0, b, u, v, w);
+        auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
+            for (int f = 0; f < NF; ++f) {
+                acc.push_back({sl.field[d0[f]], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[hat[f]], false, a - 1, b_ + 1});
+                acc.push_back({sl.field[d[f]], true, lo, hi});
+            }
+            acc.push_back({sl.field[OBST_SLOT], false, a - 1, b_ + 1});
+            for (int q : {u, v, w}) acc.push_back({sl.field[q], false, a, b_});
+        };
+        for_planes("advect_mc_masked", accesses, [&](const Launch& L) {
+            sfk::AdvectMcMaskArgs<T, NF> A;
+            fill_advect_args(A.a, L.sl, d, d0, b, u, v, w, false);
+            for (int f = 0; f < NF; ++f) A.a.hat[f] = L.sl.field[hat[f]];
+            A.code = L.sl.field[OBST_SLOT];
+            dim3 block;
+            unsigned nblocks;
+            const sfk::TileMap m = flat_map(L, block, nblocks);
+            launch_k(L, sfk::advect_mc_masked_kernel<T, NF>, dim3(nblocks), block, A, m);
+        }, 1, 0, /*interior_reads_ghosts=*/true);  // either trace may reach a ghost plane from any plane
+        exchange<NF>(d);
+    }
 
     void note_solve(int solver, int status, int iterations, double rel) {
         info_.solver = solver;
@@ -3971,6 +4034,7 @@ private:
     int precond_ = SF_PRECOND_NONE, precond_sweeps_ = 0;  // sf_set_pressure_preconditioner (SPEC §11.2)
     int mg_nu_ = 0, mg_maxl_ = 0, mg_nuc_ = 8;            // sf_set_pressure_multigrid (SPEC §11.3); nu = 0: off
     bool obst_tr_ = false;      // sf_set_obstacle_transport (SPEC §17): with obstacles on, diffuse and advect are masked
+    bool obst_mc_ = false;      // sf_set_obstacle_maccormack (SPEC §18): MacCormack under masked transport runs, masked
     bool obst_mg_ = false;      // sf_set_obstacle_multigrid (SPEC §16): a masked solve under the V-cycle runs, masked
     bool mg_codes_ok_ = false;  // the face codes of the coarse levels match the mask and the levels in force
     bool obst_on_ = false;    // sf_set_obstacles (SPEC §15): the face codes of OBST_SLOT are in force

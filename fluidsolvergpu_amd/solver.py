@@ -55,6 +55,7 @@ ABI_SYMBOLS = (
     "sf_set_obstacles", "sf_obstacles_get",
     "sf_set_obstacle_multigrid", "sf_obstacle_multigrid_get", "sf_precondition_masked",
     "sf_set_obstacle_transport", "sf_obstacle_transport_get", "sf_diffuse_masked", "sf_advect_masked",
+    "sf_set_obstacle_maccormack", "sf_obstacle_maccormack_get", "sf_advect_maccormack_masked",
     "sf_render", "sf_render_read", "sf_light",
     "sf_render_view", "sf_render_view_read", "sf_view_frame",
     "sf_render_camera", "sf_camera_passes_get", "sf_camera_frame",
@@ -173,6 +174,9 @@ lib.sf_set_obstacle_transport.argtypes = [_ctx, C.c_int]
 lib.sf_obstacle_transport_get.argtypes = [_ctx, C.POINTER(C.c_int)]
 lib.sf_diffuse_masked.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_double]
 lib.sf_advect_masked.argtypes = [_ctx] + [C.c_int] * 6
+lib.sf_set_obstacle_maccormack.argtypes = [_ctx, C.c_int]
+lib.sf_obstacle_maccormack_get.argtypes = [_ctx, C.POINTER(C.c_int)]
+lib.sf_advect_maccormack_masked.argtypes = [_ctx] + [C.c_int] * 6
 lib.sf_render.argtypes = [_ctx, C.POINTER(SfRenderParams)]
 lib.sf_render_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
 lib.sf_light.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
@@ -513,6 +517,24 @@ class FluidSolver:
     def advect_masked(self, b, d, d0, u, v, w):
         """advect under the mask (§17 advect_masked): needs obstacles and set_obstacle_transport(True)."""
         self._ck(lib.sf_advect_masked(self._h, int(b), _fid(d), _fid(d0), _fid(u), _fid(v), _fid(w)))
+
+    # -- MacCormack under the mask (docs/SPEC.md §18) -------------------------------------------------
+    def set_obstacle_maccormack(self, on):
+        """on = True: with obstacles and set_obstacle_transport on, a step advected with MacCormack runs the masked
+        MacCormack of §18 instead of being refused; False (the default) keeps the refusal. No effect without obstacles
+        or without the transport setting. Valid in any order with set_obstacles, set_obstacle_transport and
+        set_advection. Collective on several ranks; synchronises."""
+        self._ck(lib.sf_set_obstacle_maccormack(self._h, int(on) if isinstance(on, int) else (1 if on else 0)))
+
+    def obstacle_maccormack(self):
+        """The setting of set_obstacle_maccormack (sf_obstacle_maccormack_get)."""
+        on = C.c_int(0)
+        self._ck(lib.sf_obstacle_maccormack_get(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def advect_maccormack_masked(self, b, d, d0, u, v, w):
+        """MacCormack advect under the mask (§18 advect_mc_masked): needs obstacles and set_obstacle_transport(True)."""
+        self._ck(lib.sf_advect_maccormack_masked(self._h, int(b), _fid(d), _fid(d0), _fid(u), _fid(v), _fid(w)))
 
     # -- volume rendering and light marching (docs/SPEC.md §12) ---------------------------------
     def render(self, dens="dens", emit=None, axis=2, from_high=0, sigma=1.0):

@@ -384,7 +384,7 @@ int sf_precondition_masked(sf_ctx* ctx, int z, int r);
  *       are on, the three diffuse and advect of sf_vel_step and those of sf_dens_step the masked forms (sources are
  *       added first, bound ones copied into the x0 slots first: the same bits), and sf_dens_step no longer ends by
  *       zeroing the solids. A step whose fields are advected with SF_ADVECT_MACCORMACK is then SF_ERR_INVALID with a
- *       message. Valid in any order with sf_set_obstacles; while the setting is on, sf_set_obstacles also zeroes the
+ *       message, unless sf_set_obstacle_maccormack(1). Valid in any order with sf_set_obstacles; while the setting is on, sf_set_obstacles also zeroes the
  *       shell entries of the face codes and exchanges their ghost planes. Same bits for every decomposition and
  *       transport. Collective; it synchronises and drops the graphs SF_GRAPH has cached. on outside 0 / 1:
  *       SF_ERR_INVALID, and the setting is unchanged.
@@ -396,6 +396,25 @@ int sf_set_obstacle_transport(sf_ctx* ctx, int on);
 int sf_obstacle_transport_get(const sf_ctx* ctx, int* on);
 int sf_diffuse_masked(sf_ctx* ctx, int b, int x, int x0, double diff);
 int sf_advect_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w);
+
+/* MacCormack under the mask (docs/SPEC.md §18): the second-order advection of §9 composed with the masked transport of
+ * §17. Pass 1 is sf_advect_masked into a temporary; pass 2 is §9's limited correction with one more rule: a cell whose
+ * forward or reverse trace was clamped at a wall, or sampled a solid cell at any of its sixteen sample cells, keeps the
+ * first-order value. Solid cells hold +0. All selects on loaded values: a NaN parked in a solid cell reaches no fluid
+ * cell. A mask without a solid cell gives the bits of sf_advect_maccormack. Neither trace is stopped by a solid.
+ *   sf_set_obstacle_maccormack(on): 0 (the default) keeps the refusal of sf_set_obstacle_transport; 1 makes, while
+ *       obstacles and the transport setting are on, a velocity advected with SF_ADVECT_MACCORMACK in sf_vel_step and a
+ *       density so advected in sf_dens_step run this operator. Without obstacles or without the transport setting it has
+ *       no effect. Valid in any order with sf_set_obstacles, sf_set_obstacle_transport and sf_set_advection. Same bits
+ *       for every decomposition and transport. Collective; it synchronises and drops the graphs SF_GRAPH has cached.
+ *       on outside 0 / 1: SF_ERR_INVALID, and the setting is unchanged.
+ *   sf_obstacle_maccormack_get: on as last set.
+ *   sf_advect_maccormack_masked(b, d, d0, u, v, w): the operator singly, with the arguments, the aliasing rules and the
+ *       halo condition (both traces) of sf_advect_maccormack. SF_ERR_INVALID unless obstacles are on and
+ *       sf_set_obstacle_transport(1); the setting above governs the steps only. */
+int sf_set_obstacle_maccormack(sf_ctx* ctx, int on);
+int sf_obstacle_maccormack_get(const sf_ctx* ctx, int* on);
+int sf_advect_maccormack_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w);
 
 /* Axis-aligned volume rendering and light marching of docs/SPEC.md §12: an N x N image of the smoke from data that
  * already sits in device memory, instead of a (N+2)^3 frame over the bus. One ray per pixel runs along axis (0: i,

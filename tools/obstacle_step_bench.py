@@ -11,7 +11,11 @@ and starts nothing more). After --warmup steps, with sf_set_obstacle_transport o
   operators   sf_diffuse / sf_diffuse_masked (K sweeps: ms per sweep) and sf_advect / sf_advect_masked on the density,
               ten calls between syncs, best of --reps.
 
-  python tools/obstacle_step_bench.py --cases 256:f32 256:f64
+--maccormack adds the column of SPEC §18: a third step row with the setting on, both schemes SF_ADVECT_MACCORMACK and
+sf_set_obstacle_maccormack(1), and the operators sf_advect_maccormack / sf_advect_maccormack_masked next to the four
+above, with the cost of each second pass alone (the operator minus its first pass) and their ratio.
+
+  python tools/obstacle_step_bench.py --cases 256:f32 256:f64 [--maccormack]
 """
 import argparse
 import json
@@ -47,8 +51,11 @@ def case(N, dtype, a):
     fs.set_obstacle_multigrid(True)
     fs.set_obstacles(obstacle_mask(N, dtype, ["centred"]), slot="dens0")
     rows = []
-    for on in (False, True):
+    for on, mc in ((False, False), (True, False)) + (((True, True),) if a.maccormack else ()):
         fs.set_obstacle_transport(on)
+        if a.maccormack:
+            fs.set_obstacle_maccormack(mc)
+            fs.set_advection(1 if mc else 0, 1 if mc else 0)
         for _ in range(a.warmup):
             fs.vel_step()
             fs.dens_step()
@@ -57,7 +64,7 @@ def case(N, dtype, a):
         vel = best_of(fs, a.reps, a.steps, fs.vel_step)
         its = (fs.pressure_info()["iterations_total"] - i0) / (2.0 * a.steps * a.reps)
         dens = best_of(fs, a.reps, a.steps, fs.dens_step)
-        rows.append({"case": "step", "grid": N, "dtype": dtype, "obstacle_transport": on, "mg": a.mg, "tol": a.tol,
+        rows.append({"case": "step", "grid": N, "dtype": dtype, "obstacle_transport": on, "obstacle_maccormack": mc, "mg": a.mg, "tol": a.tol,
                      "vel_step_ms": round(vel, 4), "dens_step_ms": round(dens, 4), "step_ms": round(vel + dens, 4),
                      "iterations_per_projection": round(its, 2), "last_status": fs.pressure_info()["status"]})
     # the single operators on the density (one field): u0 and v0 are scratch between steps
@@ -67,14 +74,25 @@ def case(N, dtype, a):
            "diffuse_masked": lambda: fs.diffuse_masked(0, "u0", "dens", DIFF),
            "advect": lambda: fs.advect(0, "v0", "dens", "u", "v", "w"),
            "advect_masked": lambda: fs.advect_masked(0, "v0", "dens", "u", "v", "w")}
+    if a.maccormack:
+        fs.set_advection(0, 0)
+        ops["advect_maccormack"] = lambda: fs.advect_maccormack(0, "v0", "dens", "u", "v", "w")
+        ops["advect_maccormack_masked"] = lambda: fs.advect_maccormack_masked(0, "v0", "dens", "u", "v", "w")
+    took = {}
     for name, call in ops.items():
         call()
         ms = best_of(fs, a.reps, 10, call)
+        took[name] = ms
         row = {"case": "operator", "grid": N, "dtype": dtype, "op": name, "ms": round(ms, 5)}
         if name.startswith("diffuse"):
             row["sweeps"] = K
             row["ms_per_sweep"] = round(ms / K, 5)
         rows.append(row)
+    if a.maccormack:
+        p2, p2m = took["advect_maccormack"] - took["advect"], took["advect_maccormack_masked"] - took["advect_masked"]
+        rows.append({"case": "second_pass", "grid": N, "dtype": dtype, "advect_mc_ms": round(p2, 5),
+                     "advect_mc_masked_ms": round(p2m, 5), "ratio": round(p2m / p2, 3),
+                     "operator_ratio": round(took["advect_maccormack_masked"] / took["advect_maccormack"], 3)})
     gbps = fs.copy_bandwidth_gbps(1 << 30, 5)
     word = 4 if dtype == "f32" else 8
     rows.append({"case": "bytes", "grid": N, "dtype": dtype, "copy_gbps": round(gbps, 1),
@@ -94,6 +112,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--limit", type=int, default=150)
+    ap.add_argument("--maccormack", action="store_true", help="add the step and the operators of SPEC §18")
     a = ap.parse_args()
     for c in a.cases:
         n, t = c.split(":")
