@@ -1,7 +1,7 @@
 """Reads the kernel-resource remarks of one compile (hipcc -Rpass-analysis=kernel-resource-usage, stderr kept in a file),
 prints what is not a remark (warnings), and checks the instantiations of sfk::view_march_kernel (docs/SPEC.md §13) and
 sfk::camera_march_kernel (§14) against the limits of §13: no scratch, no LDS, no AGPRs, at most 128 VGPRs (four waves
-per SIMD resident), and the masked kernels of §15 to §18 against theirs: no scratch, no LDS, no AGPRs. Prints their
+per SIMD resident), and the masked kernels of §15 to §19 against theirs: no scratch, no LDS, no AGPRs. Prints their
 table."""
 import re
 import sys
@@ -19,7 +19,10 @@ MASKED_KERNELS = ("face_code_kernel", "cg_init_masked_kernel", "cg_apply_dot_mas
                   # mask-aware transport (§17)
                   "lin_solve_masked_kernel", "advect_masked_kernel",
                   # MacCormack under the mask (§18)
-                  "advect_mc_masked_kernel")
+                  "advect_mc_masked_kernel",
+                  # moving solids (§19): siblings of the two project halves, the sweep and the advect
+                  "project_div_moving_kernel", "project_sub_moving_kernel", "lin_solve_moving_kernel",
+                  "advect_moving_kernel")
 MASKED_LIMITS = {k: v for k, v in LIMITS.items() if k != "VGPRs"}
 
 

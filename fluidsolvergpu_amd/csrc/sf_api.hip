@@ -301,6 +301,14 @@ int sf_obstacle_maccormack_get(const sf_ctx* ctx, int* on) {
     ctx->impl->obstacle_maccormack(on);
     return SF_OK;
 }
+int sf_set_obstacle_velocity(sf_ctx* ctx, int su, int sv, int sw) {
+    return guarded(ctx, [&](SolverBase& s) { s.set_obstacle_velocity(su, sv, sw); });
+}
+int sf_obstacle_velocity_get(const sf_ctx* ctx, int* on) {
+    if (!ctx || !ctx->impl || !on) return SF_ERR_INVALID;
+    ctx->impl->obstacle_velocity(on);
+    return SF_OK;
+}
 int sf_advect_maccormack_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w) {
     return guarded(ctx, [&](SolverBase& s) { s.advect_maccormack_masked(b, d, d0, u, v, w); });
 }

@@ -129,6 +129,8 @@ public:
     virtual void advect_masked(int b, int d, int d0, int u, int v, int w) = 0;
     virtual void set_obstacle_maccormack(int on) = 0;
     virtual void obstacle_maccormack(int* on) const = 0;
+    virtual void set_obstacle_velocity(int su, int sv, int sw) = 0;
+    virtual void obstacle_velocity(int* on) const = 0;
     virtual void advect_maccormack_masked(int b, int d, int d0, int u, int v, int w) = 0;
     virtual void render(const sf_render_params* p) = 0;
     virtual void render_read(void* colour, void* transmittance) = 0;

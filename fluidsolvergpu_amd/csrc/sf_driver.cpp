@@ -29,7 +29,7 @@
 //             [--pressure-precond none|jacobi:M] [--pressure-mg NU[:LEVELS[:COARSE]]] [--render VIEW:SIGMA[:LIGHT]]
 //             [--render-view DX,DY,DZ:WxH:SIGMA[:STEP]] [--render-camera EX,EY,EZ:TX,TY,TZ:WxH:SIGMA[:FOV_DEG[:STEP]]]
 //             [--obstacle box:I0,J0,K0:I1,J1,K1 | sphere:CX,CY,CZ:R]... [--obstacle-mg]
-//             [--obstacle-transport] [--obstacle-maccormack] [--help]
+//             [--obstacle-transport] [--obstacle-maccormack] [--obstacle-velocity VX,VY,VZ] [--help]
 // --vorticity / --buoyancy switch on the smoke forces of docs/SPEC.md §8 (vorticity confinement, buoyancy
 // BETA*(dens - A) on velocity component --buoyancy-axis: 0 u, 1 v (the direction of the v0 source), 2 w).
 // --maccormack advects the velocity, the density or both with the limited MacCormack scheme of docs/SPEC.md §9
@@ -59,6 +59,14 @@
 // needs --obstacle and does not go with --maccormack.
 // --obstacle-maccormack: lets --obstacle-transport go with --maccormack: the masked MacCormack advection of
 // docs/SPEC.md §18 (sf_set_obstacle_maccormack); needs --obstacle-transport.
+// --obstacle-velocity VX,VY,VZ: every --obstacle moves with this velocity (docs/SPEC.md §19, sf_set_obstacle_velocity),
+// in domain units per unit time, the unit of the velocity fields: advect traces a cell back by dt0 * u = dt * N * u
+// cells, so a solid of velocity V is displaced by V * t * N cells at time t = step * dt, and the solid velocity the
+// solver is given is the constant V itself. Before each step the mask is rasterised afresh (the offset of a box rounded
+// to whole cells, the centre of a sphere kept in double, both clipped to the interior) and set again with the velocity.
+// This happens before the step's timer starts: the reported step times leave out the rasterisation, the upload and the
+// two setters (docs/NEXT.md, "Moving solids", has their cost). Needs --obstacle-transport; does not go with
+// --maccormack vel|both.
 // --render VIEW:SIGMA[:LIGHT]: at every output step an image of the density (docs/SPEC.md §12) next to the frame,
 // "render_<frame, 4 digits>.pgm" (several processes: "render_GPU<rank>_<frame>.pgm", each rank the pixel rows it holds).
 // VIEW and LIGHT are one of i+ i- j+ j- k+ k-: the axis of the rays and the side they enter from (+: at index 1). SIGMA
@@ -125,6 +133,8 @@ struct Options {
     bool obstacle_mg = false;         // --obstacle-mg (docs/SPEC.md §16)
     bool obstacle_transport = false;  // --obstacle-transport (docs/SPEC.md §17)
     bool obstacle_mc = false;         // --obstacle-maccormack (docs/SPEC.md §18)
+    bool obstacle_moving = false;     // --obstacle-velocity (docs/SPEC.md §19)
+    double obstacle_vel[3] = {0.0, 0.0, 0.0};
     double cg_tol = 1e-3;
     int render_axis = -1, render_high = 0, light_axis = -1, light_high = 0;  // --render (axis -1: off / no light)
     double render_sigma = 0.0;
@@ -214,6 +224,10 @@ static void usage(FILE* to) {
             "                 [--obstacle-mg]   --obstacle together with --pressure-mg: the masked V-cycle\n"
             "                 [--obstacle-transport]   diffusion and advection honour --obstacle too (not with --maccormack)\n"
             "                 [--obstacle-maccormack]   --obstacle-transport together with --maccormack: masked MacCormack\n"
+            "                 [--obstacle-velocity VX,VY,VZ]   every --obstacle moves: domain units per unit time, the unit of\n"
+            "                      the velocity fields (advect traces back dt*N*u cells, so the solids are displaced by V*t*N\n"
+            "                      cells); needs --obstacle-transport, not with --maccormack vel|both; the mask and the\n"
+            "                      velocity are set again before each step, outside the reported step time\n"
             "                 [--loopback --rank R --world W] [--help]\n");
 }
 
@@ -450,6 +464,13 @@ static Options parse(int argc, char** argv) {
         else if (s == "--obstacle-mg") o.obstacle_mg = true;
         else if (s == "--obstacle-transport") o.obstacle_transport = true;
         else if (s == "--obstacle-maccormack") o.obstacle_mc = true;
+        else if (s == "--obstacle-velocity") {
+            if (!parse_triple(next(), false, o.obstacle_vel)) {
+                fprintf(stderr, "--obstacle-velocity takes VX,VY,VZ (finite numbers, domain units per unit time)\n");
+                exit(2);
+            }
+            o.obstacle_moving = true;
+        }
         else if (s == "--render") {
             // VIEW:SIGMA[:LIGHT]
             const std::string spec = next();
@@ -565,6 +586,14 @@ static Options parse(int argc, char** argv) {
         fprintf(stderr, "--obstacle-transport does not go with --maccormack (docs/SPEC.md §17)\n");
         exit(2);
     }
+    if (o.obstacle_moving && !o.obstacle_transport) {
+        fprintf(stderr, "--obstacle-velocity needs --obstacle-transport (docs/SPEC.md §19)\n");
+        exit(2);
+    }
+    if (o.obstacle_moving && o.advect_vel == SF_ADVECT_MACCORMACK) {
+        fprintf(stderr, "--obstacle-velocity does not go with --maccormack vel|both (docs/SPEC.md §19)\n");
+        exit(2);
+    }
     // frames go to <out>/: create it (the reference writes into the working directory, which always exists)
     if (o.every > 0) {
         std::error_code ec;
@@ -606,21 +635,28 @@ static std::vector<T> make_input(int which, int N, int kb, int ke, double dt, bo
 }
 
 // The mask of --obstacle on the global planes [kb, ke): 1 in the cells of any obstacle, 0 elsewhere (docs/SPEC.md §15).
+// time: every obstacle displaced by --obstacle-velocity * time * N cells (docs/SPEC.md §19; a box by whole cells).
 template <class T>
-static std::vector<T> make_mask(const Options& o, int kb, int ke) {
+static std::vector<T> make_mask(const Options& o, int kb, int ke, double time = 0.0) {
     const int N = o.n;
     const size_t S = (size_t)N + 2;
     std::vector<T> f(S * S * (size_t)(ke - kb), T(0));
+    double sh[3], shw[3];
+    for (int q = 0; q < 3; ++q) {
+        sh[q] = o.obstacle_vel[q] * time * N;
+        shw[q] = std::nearbyint(sh[q]);
+    }
     for (const Options::Obstacle& ob : o.obstacles)
         for (int k = std::max(kb, 1); k < std::min(ke, N + 1); ++k)
             for (int j = 1; j <= N; ++j)
                 for (int i = 1; i <= N; ++i) {
                     bool in;
                     if (ob.sphere) {
-                        const double dx = i - ob.a[0], dy = j - ob.a[1], dz = k - ob.a[2];
+                        const double dx = i - (ob.a[0] + sh[0]), dy = j - (ob.a[1] + sh[1]), dz = k - (ob.a[2] + sh[2]);
                         in = (dx * dx + dy * dy) + dz * dz <= ob.a[3] * ob.a[3];
                     } else {
-                        in = i >= ob.a[0] && i <= ob.a[3] && j >= ob.a[1] && j <= ob.a[4] && k >= ob.a[2] && k <= ob.a[5];
+                        const double ci = i - shw[0], cj = j - shw[1], ck = k - shw[2];
+                        in = ci >= ob.a[0] && ci <= ob.a[3] && cj >= ob.a[1] && cj <= ob.a[4] && ck >= ob.a[2] && ck <= ob.a[5];
                     }
                     if (in) f[(size_t)i + S * ((size_t)j + S * (size_t)(k - kb))] = T(1);
                 }
@@ -886,6 +922,16 @@ static int run(const Options& o) {
     for (int t = 0; t < o.steps; t++) {
         if (!o.quiet && talk) std::cout << "t= " << t << "\n";
         float elapsedTime = 0.f;
+        // --obstacle-velocity: the mask at this step's time and the solid velocity, through slots that are scratch
+        // between steps while their sources are bound (SF_DENS0, SF_U0, SF_V0, SF_W0); each is read once, by its call
+        if (o.obstacle_moving) {
+            SF_CHECK_RETURN(sf_upload_planes(g_ctx, SF_DENS0, st_kb, st_ke, make_mask<T>(o, st_kb, st_ke, t * dt).data()));
+            SF_CHECK_RETURN(sf_set_obstacles(g_ctx, SF_DENS0));
+            SF_CHECK_RETURN(sf_fill(g_ctx, SF_DENS0, 0.0));
+            const int vs[3] = {SF_U0, SF_V0, SF_W0};
+            for (int q = 0; q < 3; ++q) SF_CHECK_RETURN(sf_fill(g_ctx, vs[q], o.obstacle_vel[q]));
+            SF_CHECK_RETURN(sf_set_obstacle_velocity(g_ctx, SF_U0, SF_V0, SF_W0));
+        }
         SF_CHECK_RETURN(sf_timer_start(g_ctx));
         SF_CHECK_RETURN(vel_step(g_ctx));  // sources are bound (sf_bind_sources above)
         SF_CHECK_RETURN(dens_step(g_ctx));

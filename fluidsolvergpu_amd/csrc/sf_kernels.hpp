@@ -3828,6 +3828,310 @@ __global__ void __launch_bounds__(256) advect_mc_masked_kernel(Geom g, AdvectMcM
     if (bad) atomicOr(A.flag, 1);
 }
 
+// ---- Moving solids (SPEC §19) ----
+// A solid has a velocity of its own: three fields us, vs, ws, of which only the values in interior solid cells are
+// ever operands. On the axis of a velocity component the ghost value at a closed face becomes
+// effv(x, xs, c, nb) = (xs[nb] + xs[nb]) - x[c] instead of -x[c]; the tangential axes and every b = 0 field keep eff.
+// The four kernels are siblings of the masked ones above (their row and gather mappings, their sums, their fused
+// set_bnd), not template parameters on them: the masked kernels are untouched. Every use of the solid velocity is a
+// select after an unconditional load, so what its fluid and shell entries hold (a NaN included) reaches nothing.
+template <class T>
+struct ProjectMovingArgs {
+    ProjectMaskArgs<T> a;
+    const T* us;
+    const T* vs;
+    const T* ws;
+};
+
+// project_div_masked_kernel with effv on each component's own axis; +0 on solid cells; set_bnd(0, div)
+template <class T>
+__global__ void __launch_bounds__(256) project_div_moving_kernel(Geom g, ProjectMovingArgs<T> M) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    const ProjectMaskArgs<T>& A = M.a;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V uc = ldv(A.u + q), vc = ldv(A.v + q), wc = ldv(A.w + q), cv = ldv(A.code + q);
+        const T um = A.u[q - 1], up = A.u[q + W];
+        const V vm = ldv(A.v + q - g.px), vp = ldv(A.v + q + g.px);
+        const V wm = ldv(A.w + q - g.plane), wp = ldv(A.w + q + g.plane);
+        const V sc = ldv(M.us + q);
+        const T sm = M.us[q - 1], sp = M.us[q + W];
+        const V sjm = ldv(M.vs + q - g.px), sjp = ldv(M.vs + q + g.px);
+        const V skm = ldv(M.ws + q - g.plane), skp = ldv(M.ws + q + g.plane);
+        const int nv = cg_valid<W>(g, i0);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const int c = (int)cv[e];
+            T left = (e == 0) ? um : uc[e - 1];
+            T right = (e == W - 1) ? up : uc[e + 1];
+            const T sl = (e == 0) ? sm : sc[e - 1];
+            const T sr = (e == W - 1) ? sp : sc[e + 1];
+            left = (c & FC_ILO) ? (sl + sl) - uc[e] : left;
+            right = (c & FC_IHI) ? (sr + sr) - uc[e] : right;
+            const T a = (c & FC_JLO) ? (sjm[e] + sjm[e]) - vc[e] : vm[e];
+            const T b = (c & FC_JHI) ? (sjp[e] + sjp[e]) - vc[e] : vp[e];
+            const T d = (c & FC_KLO) ? (skm[e] + skm[e]) - wc[e] : wm[e];
+            const T f = (c & FC_KHI) ? (skp[e] + skp[e]) - wc[e] : wp[e];
+            const T val = A.c_div * (((right - left) + (b - a)) + (f - d));
+            out[e] = (c & FC_SOLID) ? T(0) : val;
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.div, r, i0, out, nv);
+            emit_shells<T, W>(A.div, g, 0, i0, j, kl, out, nv);
+        }
+    }
+}
+
+// project_sub_masked_kernel with u = us[c], v = vs[c], w = ws[c] on solid cells instead of +0; the three set_bnd
+template <class T>
+__global__ void __launch_bounds__(256) project_sub_moving_kernel(Geom g, ProjectMovingArgs<T> M) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    const ProjectMaskArgs<T>& A = M.a;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    const T* __restrict__ pr = A.p;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V pc = ldv(pr + q), cv = ldv(A.code + q);
+        const T pm = pr[q - 1], pp = pr[q + W];
+        const V pjm = ldv(pr + q - g.px), pjp = ldv(pr + q + g.px);
+        const V pkm = ldv(pr + q - g.plane), pkp = ldv(pr + q + g.plane);
+        const V uc = ldv(A.u + q), vc = ldv(A.v + q), wc = ldv(A.w + q);
+        const V su = ldv(M.us + q), sv = ldv(M.vs + q), sw = ldv(M.ws + q);
+        const int nv = cg_valid<W>(g, i0);
+        T ou[W], ov[W], ow[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const int c = (int)cv[e];
+            const T self = pc[e];
+            T left = (e == 0) ? pm : pc[e - 1];
+            T right = (e == W - 1) ? pp : pc[e + 1];
+            left = (c & FC_ILO) ? self : left;
+            right = (c & FC_IHI) ? self : right;
+            const T a = (c & FC_JLO) ? self : pjm[e], b = (c & FC_JHI) ? self : pjp[e];
+            const T d = (c & FC_KLO) ? self : pkm[e], f = (c & FC_KHI) ? self : pkp[e];
+            const T nu = uc[e] - A.c_grad * (right - left);
+            const T nvv = vc[e] - A.c_grad * (b - a);
+            const T nw = wc[e] - A.c_grad * (f - d);
+            const bool solid = (c & FC_SOLID) != 0;
+            ou[e] = solid ? su[e] : nu;
+            ov[e] = solid ? sv[e] : nvv;
+            ow[e] = solid ? sw[e] : nw;
+        }
+        if (nv > 0) {
+            store_cells<T, W>(A.u, r, i0, ou, nv);
+            store_cells<T, W>(A.v, r, i0, ov, nv);
+            store_cells<T, W>(A.w, r, i0, ow, nv);
+            emit_shells<T, W>(A.u, g, 1, i0, j, kl, ou, nv);
+            emit_shells<T, W>(A.v, g, 2, i0, j, kl, ov, nv);
+            emit_shells<T, W>(A.w, g, 3, i0, j, kl, ow, nv);
+        }
+    }
+}
+
+// lin_solve_masked_kernel with effv as the own-axis operand of a field with b = 1, 2, 3; xs[f] is the solid velocity of
+// that axis (any of the three for b = 0, where nothing of it is used and the bits are §17's). b stays a run-time
+// argument and no load is branched round: the own vector of xs with the lane exchange and the wave-uniform seam cells
+// serves b = 1, and ONE pair of neighbour rows at a wave-uniform stride chosen from b (px for b = 2, plane for b = 3,
+// 0 otherwise: the own row again, a cache hit) serves b = 2 and 3; the operands are then selected by b.
+template <class T, int NF>
+struct LinSolveMovingArgs {
+    LinSolveMaskArgs<T, NF> a;
+    const T* xs[NF];
+};
+
+template <class T, int NF>
+__global__ void __launch_bounds__(256) lin_solve_moving_kernel(Geom g, LinSolveMovingArgs<T, NF> M) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    const LinSolveMaskArgs<T, NF>& A = M.a;
+    int j, p;
+    if (!reduce_row(g, j, p)) return;
+    const int kl = g.G + p;
+    const long r = row0(g, j, kl);
+    const int nm = (g.N + 64 * W - 1) / (64 * W);
+    const int lane = (int)threadIdx.x & 63;
+    for (int m = 0; m < nm; ++m) {
+        int i0, i0c;
+        reduce_vec<W>(g, m, i0, i0c);
+        const long q = r + i0c;
+        const V cv = ldv(A.code + q);
+        const int nv = cg_valid<W>(g, i0);
+        const int first = 1 + 64 * W * m;
+        const int next = first + 64 * W;
+        const int end = next < g.N + 1 ? next : g.N + 1;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            const T* __restrict__ x = A.x[f];
+            const T* __restrict__ xs = M.xs[f];
+            const int b = A.b[f];
+            const long st = (b == 2) ? (long)g.px : ((b == 3) ? g.plane : 0L);
+            const V xc = ldv(x + q), bv = ldv(A.x0[f] + q);
+            const V jm = ldv(x + q - g.px), jp = ldv(x + q + g.px);
+            const V km = ldv(x + q - g.plane), kp = ldv(x + q + g.plane);
+            const T lo = x[r + first - 1], hi = x[r + end];
+            const V sc = ldv(xs + q), sm = ldv(xs + q - st), sp = ldv(xs + q + st);
+            const T slo = xs[r + first - 1], shi = xs[r + end];
+            T left = lane_up(xc[W - 1]), right = lane_dn(xc[0]);
+            T sleft = lane_up(sc[W - 1]), sright = lane_dn(sc[0]);
+            if (lane == 0) left = lo;
+            if (i0 + W == end) right = hi;
+            if (lane == 0) sleft = slo;
+            if (i0 + W == end) sright = shi;
+            T out[W];
+#pragma unroll
+            for (int e = 0; e < W; ++e) {
+                const int c = (int)cv[e];
+                const T self = xc[e];
+                T l = (e == 0) ? left : xc[e - 1];
+                T rt = (e == W - 1) ? right : xc[e + 1];
+                const T sl = (e == 0) ? sleft : sc[e - 1];
+                const T sr = (e == W - 1) ? sright : sc[e + 1];
+                const T mil = (b == 1) ? (sl + sl) - self : self, mih = (b == 1) ? (sr + sr) - self : self;
+                const T wl = (sm[e] + sm[e]) - self, wh = (sp[e] + sp[e]) - self;
+                const T mjl = (b == 2) ? wl : self, mjh = (b == 2) ? wh : self;
+                const T mkl = (b == 3) ? wl : self, mkh = (b == 3) ? wh : self;
+                l = (c & FC_ILO) ? mil : l;
+                rt = (c & FC_IHI) ? mih : rt;
+                const T a = (c & FC_JLO) ? mjl : jm[e], bb = (c & FC_JHI) ? mjh : jp[e];
+                const T d = (c & FC_KLO) ? mkl : km[e], ff = (c & FC_KHI) ? mkh : kp[e];
+                const T v = (bv[e] + A.a * (((l + rt) + (a + bb)) + (d + ff))) * A.inv;
+                out[e] = (c & FC_SOLID) ? T(0) : v;
+            }
+            if (nv > 0) {
+                store_cells<T, W>(A.xn[f], r, i0, out, nv);
+                emit_shells<T, W>(A.xn[f], g, b, i0, j, kl, out, nv);
+            }
+        }
+    }
+}
+
+// advect_masked_kernel with wv = xs_b[s], the solid's velocity at the SAMPLE cell, for a field with b = 1, 2, 3
+// (b = 0: wv = d0[c] as in §17; xs[f] is then any of the three and nothing of it is used). The solid velocity is
+// gathered as corner pairs at the sample addresses, as d0 and the face codes are. The sibling takes the cells of a
+// lane in sequence and the NF fields of a cell together; with four more pair gathers per cell and field that form
+// has no room for NF = 3 in the register file, so this one takes the fields in sequence, as advect_mc_masked_kernel
+// does: the W back-traces and the face codes of their samples first (reduced to one bit per sample), then per field
+// all gathers of d0 and xs of the lane requested, each S folded into its C, the interpolation, the stores. The
+// arithmetic of a cell is the sibling's to the letter.
+template <class T, int NF>
+struct AdvectMovingArgs {
+    AdvectMaskArgs<T, NF> m;
+    const T* xs[NF];
+};
+
+template <class T, int NF>
+__global__ void __launch_bounds__(256) advect_moving_kernel(Geom g, AdvectMovingArgs<T, NF> MV, int kb, int ke, TileMap m) {
+    constexpr int W = VecT<T>::W;
+    typedef typename VecT<T>::type V;
+    typedef T Pair __attribute__((ext_vector_type(2), aligned(sizeof(T))));
+    const AdvectArgs<T, NF>& A = MV.m.a;
+    const T* __restrict__ code = MV.m.code;
+    int i0, j, kl, nv;
+    if (!flat_cell<W>(g, m, kb, ke, i0, j, kl, nv)) return;
+    const int N = g.N;
+    const T Nf = (T)N;
+    const T lo = T(0.5), hi = Nf + T(0.5);
+    const long q = row0(g, j, kl) + i0;
+    const V uu = ldv(A.u + q), vv = ldv(A.v + q), ww = ldv(A.w + q), cown = ldv(code + q);
+    const int kg = g.kg0 + kl;
+    const long off[4] = {0, g.plane, g.px, g.px + g.plane};
+    long p00[W];
+    T s1[W], t1[W], r1[W];
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < W; ++e) {
+        T x = (T)(i0 + e) - A.dt0 * uu[e];
+        T y = (T)j - A.dt0 * vv[e];
+        T z = (T)kg - A.dt0 * ww[e];
+        if (x < lo) x = lo;
+        if (x > hi) x = hi;
+        if (y < lo) y = lo;
+        if (y > hi) y = hi;
+        if (z < lo) z = lo;
+        if (z > hi) z = hi;
+        int ia = (x == x) ? (int)x : 0;
+        int ja = (y == y) ? (int)y : 0;
+        int ka = (z == z) ? (int)z : 0;
+        ia = ia < 0 ? 0 : (ia > N ? N : ia);
+        ja = ja < 0 ? 0 : (ja > N ? N : ja);
+        ka = ka < 0 ? 0 : (ka > N ? N : ka);
+        s1[e] = x - (T)ia, t1[e] = y - (T)ja, r1[e] = z - (T)ka;
+        int kla = ka - g.kg0;  // local plane of k0; k1 = kla + 1 must also be stored
+        if (kla < 0 || kla > g.np - 2) {
+            bad |= (e < nv);
+            kla = kla < 0 ? 0 : g.np - 2;
+        }
+        p00[e] = row0(g, ja, kla) + ia;  // (i0,j0,k0); +plane: k1; +px: j1
+    }
+    int sol[W];  // bit 2c + h: the sample of corner pair c, half h, is solid
+    {
+        Pair K[W][4];
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) K[e][c] = *reinterpret_cast<const Pair*>(code + p00[e] + off[c]);
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            int s = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                s |= ((int)K[e][c][0] & FC_SOLID) ? (1 << (2 * c)) : 0;
+                s |= ((int)K[e][c][1] & FC_SOLID) ? (2 << (2 * c)) : 0;
+            }
+            sol[e] = s;
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        const T* __restrict__ d0 = A.d0[f];
+        const T* __restrict__ xs = MV.xs[f];
+        const bool still = A.b[f] == 0;
+        Pair C[W][4], S[W][4];
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                C[e][c] = *reinterpret_cast<const Pair*>(d0 + p00[e] + off[c]);
+                S[e][c] = *reinterpret_cast<const Pair*>(xs + p00[e] + off[c]);
+            }
+        const V own = ldv(d0 + q);
+        T out[W];
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const T s0 = T(1) - s1[e], t0 = T(1) - t1[e], r0 = T(1) - r1[e];
+            T c0[4], c1[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const T w0 = still ? own[e] : S[e][c][0], w1 = still ? own[e] : S[e][c][1];
+                c0[c] = (sol[e] & (1 << (2 * c))) ? w0 : C[e][c][0];
+                c1[c] = (sol[e] & (2 << (2 * c))) ? w1 : C[e][c][1];
+            }
+            const T val = s0 * (t0 * (r0 * c0[0] + r1[e] * c0[1]) + t1[e] * (r0 * c0[2] + r1[e] * c0[3])) +
+                          s1[e] * (t0 * (r0 * c1[0] + r1[e] * c1[1]) + t1[e] * (r0 * c1[2] + r1[e] * c1[3]));
+            out[e] = ((int)cown[e] & FC_SOLID) ? T(0) : val;
+        }
+        store_cells<T, W>(A.d[f], q - i0, i0, out, nv);
+        emit_shells<T, W>(A.d[f], g, A.b[f], i0, j, kl, out, nv);
+    }
+    if (bad) atomicOr(A.flag, 1);
+}
+
 // ---- Multigrid V-cycle preconditioner (SPEC §11.3) ----
 // Three row kernels on the fields of one level (a Geom of its own: n_l cells per axis, one ghost plane per side on the
 // coarse levels) with the row shape, the clamped unconditional loads and the stencil of the CG kernels above. They know

@@ -48,6 +48,9 @@ class Solver final : public SolverBase {
     // The face codes of the coarse levels l >= 1 under obstacles (SPEC §16): one owning slot per level, written when the
     // first masked V-cycle after sf_set_obstacles / sf_set_pressure_multigrid builds them. Level 0 is OBST_SLOT.
     static constexpr int mg_code(int l) { return OBST_SLOT + l; }
+    // The solid velocity in force (SPEC §19): three owning slots (us, vs, ws) with buffers of their own from the first
+    // sf_set_obstacle_velocity on, written by that call only (whole copies of the caller's slots, ghost planes current).
+    static constexpr int OBSTV_SLOT = OBST_SLOT + MG_MAXL;
 
     // The geometry of the fields an operator runs on: the solver-wide one (lv0_, the default everywhere) or a coarse
     // level of the multigrid hierarchy, whose fields have n cells per axis, n / P planes per slab and one ghost plane.
@@ -59,7 +62,7 @@ class Solver final : public SolverBase {
     struct Slab {
         int gid = 0;  // global slab index 0..P-1
         sfk::Geom geom{};
-        T* field[SF_NUM_FIELDS + NSCRATCH + 2 + 3 * (MG_MAXL - 1) + 1 + (MG_MAXL - 1)] = {};
+        T* field[SF_NUM_FIELDS + NSCRATCH + 2 + 3 * (MG_MAXL - 1) + 1 + (MG_MAXL - 1) + 3] = {};
         T* scratch[NSCRATCH] = {};
         T* snap[4] = {};               // snapshot buffers for asynchronous output
         hipStream_t os = nullptr;      // output (copy) stream
@@ -686,6 +689,12 @@ public:
         const bool dead = ishell_skip_ && K_ >= 1 && dead_ishell_opt_ && !obst_on_;
         // SPEC §17: diffuse and advect under the mask (sources added first; bound ones copied first: the same bits)
         const bool masked_tr = obst_on_ && obst_tr_;
+        // SPEC §19: a solid velocity needs the masked transport and has no MacCormack form
+        SF_REQUIRE(!obstv_on_ || obst_tr_,
+                   "vel_step: a solid velocity (sf_set_obstacle_velocity) needs sf_set_obstacle_transport(1)");
+        SF_REQUIRE(!(obstv_on_ && mc_vel_ == SF_ADVECT_MACCORMACK),
+                   "vel_step: MacCormack advection of the velocity under a solid velocity (sf_set_obstacle_velocity) "
+                   "is not supported");
         SF_REQUIRE(!(masked_tr && mc_vel_ == SF_ADVECT_MACCORMACK) || obst_mc_,
                    "vel_step: MacCormack advection of the velocity under sf_set_obstacle_transport(1) is not supported");
         // SPEC §8: with a force on, the sources (bound slots, or the x0 slots themselves) plus the forces go into the
@@ -1327,12 +1336,48 @@ public:
         obst_mc_ = on != 0;
     }
     void obstacle_maccormack(int* on) const override { *on = obst_mc_ ? 1 : 0; }
+    // SPEC §19: the slots su, sv, sw are copied whole into the three OBSTV slots; all -1: off
+    void set_obstacle_velocity(int su, int sv, int sw) override {
+        const bool off = su == -1 && sv == -1 && sw == -1;
+        if (!off) {
+            for (int f : {su, sv, sw})
+                SF_REQUIRE(f >= 0 && f < SF_NUM_FIELDS,
+                           "set_obstacle_velocity: slot out of range (three slots, or -1, -1, -1: off)");
+            SF_REQUIRE(su != sv && su != sw && sv != sw, "set_obstacle_velocity: the three slots must be different fields");
+        }
+        SF_HIP(hipSetDevice(device_));
+        sync();
+        for (GraphEntry& e : graph_cache_) (void)hipGraphExecDestroy(e.exec);  // a step of the other form
+        graph_cache_.clear();
+        if (off) {
+            obstv_on_ = false;
+            return;
+        }
+        const int src[3] = {su, sv, sw}, dst[3] = {OBSTV_SLOT, OBSTV_SLOT + 1, OBSTV_SLOT + 2};
+        for (Slab& sl : slabs_)
+            for (int q = 0; q < 3; ++q) {
+                ensure(sl, src[q]);
+                if (!sl.field[dst[q]]) sl.field[dst[q]] = alloc_field();
+                SF_HIP(hipMemcpyAsync(sl.field[dst[q]], sl.field[src[q]], (size_t)field_elems_ * sizeof(T),
+                                      hipMemcpyDeviceToDevice, sl.cs));
+                tr_whole("solid_velocity", sl, {sl.field[src[q]]}, {sl.field[dst[q]]});
+            }
+        obstv_on_ = true;
+        if (P_ == 1) return;
+        for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
+        exchange<3>(dst);
+    }
+    void obstacle_velocity(int* on) const override { *on = obstv_on_ ? 1 : 0; }
     void advect_maccormack_masked(int b, int d, int d0, int u, int v, int w) override {
         for (int f : {d, d0, u, v, w}) check_field(f);
         check_b(b);
         SF_REQUIRE(d != d0 && d != u && d != v && d != w, "advect_maccormack_masked: output must not alias an input");
         SF_REQUIRE(obst_on_ && obst_tr_,
                    "advect_maccormack_masked: needs obstacles (sf_set_obstacles) and sf_set_obstacle_transport(1)");
+        // SPEC §19: there is no MacCormack form under a solid velocity; pass 1 would be the moving advect
+        SF_REQUIRE(!(obstv_on_ && b != 0),
+                   "advect_maccormack_masked: a velocity component (b = 1, 2, 3) under a solid velocity "
+                   "(sf_set_obstacle_velocity) is not supported");
         SF_HIP(hipSetDevice(device_));
         const int ds[1] = {d}, d0s[1] = {d0}, bs[1] = {b};
         op_advect_mc_masked<1>(ds, d0s, bs, u, v, w);
@@ -3000,12 +3045,33 @@ private:
         wr_range(sl, G_, G_ + nzl_, lo, hi);
         return Acc{buf, true, lo, hi};
     }
+    // SPEC §19: the argument of the moving siblings, and the solid velocity as the two halves read it
+    sfk::ProjectMovingArgs<T> project_moving_args(Slab& sl, int u, int v, int w, int p, int div) {
+        return sfk::ProjectMovingArgs<T>{project_mask_args(sl, u, v, w, p, div), sl.field[OBSTV_SLOT], sl.field[OBSTV_SLOT + 1],
+                                         sl.field[OBSTV_SLOT + 2]};
+    }
     void project_first_half_masked(int u, int v, int w, int p, int div) {
         join();
         for (Slab& sl : slabs_) {
             for (int f : {u, v, w, p, div}) ensure(sl, f);
             SF_HIP(hipMemsetAsync(sl.field[p], 0, (size_t)field_elems_ * sizeof(T), sl.cs));
             tr_whole("zero_p", sl, {}, {sl.field[p]});
+        }
+        if (obstv_on_) {
+            launch_rows<false>("project_div_moving", sfk::project_div_moving_kernel<T>,
+                               [&](Slab& sl) { return project_moving_args(sl, u, v, w, p, div); },
+                               [&](Slab& sl) {
+                                   return std::vector<Acc>{{sl.field[u], false, G_, G_ + nzl_},
+                                                           {sl.field[v], false, G_, G_ + nzl_},
+                                                           {sl.field[w], false, G_ - 1, G_ + nzl_ + 1},
+                                                           {sl.field[OBST_SLOT], false, G_, G_ + nzl_},
+                                                           {sl.field[OBSTV_SLOT], false, G_, G_ + nzl_},
+                                                           {sl.field[OBSTV_SLOT + 1], false, G_, G_ + nzl_},
+                                                           {sl.field[OBSTV_SLOT + 2], false, G_ - 1, G_ + nzl_ + 1},
+                                                           rows_written(sl, sl.field[div])};
+                               });
+            publish_from_cs(div);
+            return;
         }
         launch_rows<false>("project_div_masked", sfk::project_div_masked_kernel<T>,
                            [&](Slab& sl) { return project_mask_args(sl, u, v, w, p, div); },
@@ -3020,17 +3086,22 @@ private:
     }
     void project_second_half_masked(int u, int v, int w, int p, int div) {
         join();  // p's ghost planes
-        launch_rows<false>("project_sub_masked", sfk::project_sub_masked_kernel<T>,
-                           [&](Slab& sl) { return project_mask_args(sl, u, v, w, p, div); },
-                           [&](Slab& sl) {
-                               std::vector<Acc> a{{sl.field[p], false, G_ - 1, G_ + nzl_ + 1},
-                                                  {sl.field[OBST_SLOT], false, G_, G_ + nzl_}};
-                               for (int q : {u, v, w}) {
-                                   a.push_back({sl.field[q], false, G_, G_ + nzl_});
-                                   a.push_back(rows_written(sl, sl.field[q]));
-                               }
-                               return a;
-                           });
+        auto acc = [&](Slab& sl) {
+            std::vector<Acc> a{{sl.field[p], false, G_ - 1, G_ + nzl_ + 1}, {sl.field[OBST_SLOT], false, G_, G_ + nzl_}};
+            for (int q : {u, v, w}) {
+                a.push_back({sl.field[q], false, G_, G_ + nzl_});
+                a.push_back(rows_written(sl, sl.field[q]));
+            }
+            if (obstv_on_)
+                for (int q = 0; q < 3; ++q) a.push_back({sl.field[OBSTV_SLOT + q], false, G_, G_ + nzl_});
+            return a;
+        };
+        if (obstv_on_)  // SPEC §19
+            launch_rows<false>("project_sub_moving", sfk::project_sub_moving_kernel<T>,
+                               [&](Slab& sl) { return project_moving_args(sl, u, v, w, p, div); }, acc);
+        else
+            launch_rows<false>("project_sub_masked", sfk::project_sub_masked_kernel<T>,
+                               [&](Slab& sl) { return project_mask_args(sl, u, v, w, p, div); }, acc);
         if (P_ == 1) return;
         for (Slab& sl : slabs_) ev_record(sl, &Slab::boundary_done, sl.cs);
         const int uvw[3] = {u, v, w};
@@ -3075,31 +3146,50 @@ private:
                 ensure(sl, x[f]);
                 ensure(sl, x0[f]);
             }
+        // SPEC §19: the moving sibling when a solid velocity is set and some field is a velocity component (a b = 0
+        // field in such a launch reads us and uses nothing of it)
+        bool moving = false;
+        for (int f = 0; f < NF; ++f) moving = moving || (obstv_on_ && b[f] != 0);
+        auto xs_slot = [&](int f) { return OBSTV_SLOT + (b[f] > 0 ? b[f] - 1 : 0); };
+        auto margs = [&](Slab& sl) {
+            sfk::LinSolveMaskArgs<T, NF> A{};
+            for (int f = 0; f < NF; ++f) {
+                A.x[f] = sl.field[x[f]];
+                A.x0[f] = sl.field[x0[f]];
+                A.xn[f] = sl.scratch[f];
+                A.b[f] = b[f];
+            }
+            A.code = sl.field[OBST_SLOT];
+            A.a = a;
+            A.inv = inv;
+            return A;
+        };
+        auto macc = [&](Slab& sl) {
+            std::vector<Acc> acc{{sl.field[OBST_SLOT], false, G_, G_ + nzl_}};
+            for (int f = 0; f < NF; ++f) {
+                acc.push_back({sl.field[x[f]], false, G_ - 1, G_ + nzl_ + 1});
+                acc.push_back({sl.field[x0[f]], false, G_, G_ + nzl_});
+                acc.push_back(rows_written(sl, sl.scratch[f]));
+                if (moving) {  // the k-neighbour rows of ws for b = 3, the slab's own planes otherwise
+                    const int g = b[f] == 3 ? 1 : 0;
+                    acc.push_back({sl.field[xs_slot(f)], false, G_ - g, G_ + nzl_ + g});
+                }
+            }
+            return acc;
+        };
         for (int it = 0; it < K; ++it) {
             join();  // the ghost planes of the iterate
-            launch_rows<false>("lin_solve_masked", sfk::lin_solve_masked_kernel<T, NF>,
-                               [&](Slab& sl) {
-                                   sfk::LinSolveMaskArgs<T, NF> A{};
-                                   for (int f = 0; f < NF; ++f) {
-                                       A.x[f] = sl.field[x[f]];
-                                       A.x0[f] = sl.field[x0[f]];
-                                       A.xn[f] = sl.scratch[f];
-                                       A.b[f] = b[f];
-                                   }
-                                   A.code = sl.field[OBST_SLOT];
-                                   A.a = a;
-                                   A.inv = inv;
-                                   return A;
-                               },
-                               [&](Slab& sl) {
-                                   std::vector<Acc> acc{{sl.field[OBST_SLOT], false, G_, G_ + nzl_}};
-                                   for (int f = 0; f < NF; ++f) {
-                                       acc.push_back({sl.field[x[f]], false, G_ - 1, G_ + nzl_ + 1});
-                                       acc.push_back({sl.field[x0[f]], false, G_, G_ + nzl_});
-                                       acc.push_back(rows_written(sl, sl.scratch[f]));
-                                   }
-                                   return acc;
-                               });
+            if (moving)
+                launch_rows<false>("lin_solve_moving", sfk::lin_solve_moving_kernel<T, NF>,
+                                   [&](Slab& sl) {
+                                       sfk::LinSolveMovingArgs<T, NF> A{};
+                                       A.a = margs(sl);
+                                       for (int f = 0; f < NF; ++f) A.xs[f] = sl.field[xs_slot(f)];
+                                       return A;
+                                   },
+                                   macc);
+            else
+                launch_rows<false>("lin_solve_masked", sfk::lin_solve_masked_kernel<T, NF>, margs, macc);
             // the new iterate becomes the field; the old buffer becomes scratch
             for (Slab& sl : slabs_)
                 for (int f = 0; f < NF; ++f) std::swap(sl.field[x[f]], sl.scratch[f]);
@@ -3119,6 +3209,10 @@ private:
             }
             for (int f : {u, v, w}) ensure(sl, f);
         }
+        // SPEC §19: the moving sibling when a solid velocity is set and some field is a velocity component
+        bool moving = false;
+        for (int f = 0; f < NF; ++f) moving = moving || (obstv_on_ && b[f] != 0);
+        auto xs_slot = [&](int f) { return OBSTV_SLOT + (b[f] > 0 ? b[f] - 1 : 0); };
         auto accesses = [&](Slab& sl, int a, int b_, int lo, int hi, std::vector<Acc>& acc) {
             for (int f = 0; f < NF; ++f) {
                 acc.push_back({sl.field[d0[f]], false, a - 1, b_ + 1});
@@ -3126,15 +3220,24 @@ private:
             }
             acc.push_back({sl.field[OBST_SLOT], false, a - 1, b_ + 1});
             for (int q : {u, v, w}) acc.push_back({sl.field[q], false, a, b_});
+            if (moving)
+                for (int f = 0; f < NF; ++f) acc.push_back({sl.field[xs_slot(f)], false, a - 1, b_ + 1});
         };
-        for_planes("advect_masked", accesses, [&](const Launch& L) {
+        for_planes(moving ? "advect_moving" : "advect_masked", accesses, [&](const Launch& L) {
             sfk::AdvectMaskArgs<T, NF> A;
             fill_advect_args(A.a, L.sl, d, d0, b, u, v, w, false);
             A.code = L.sl.field[OBST_SLOT];
             dim3 block;
             unsigned nblocks;
             const sfk::TileMap m = flat_map(L, block, nblocks);
-            launch_k(L, sfk::advect_masked_kernel<T, NF>, dim3(nblocks), block, A, m);
+            if (moving) {
+                sfk::AdvectMovingArgs<T, NF> MV;
+                MV.m = A;
+                for (int f = 0; f < NF; ++f) MV.xs[f] = L.sl.field[xs_slot(f)];
+                launch_k(L, sfk::advect_moving_kernel<T, NF>, dim3(nblocks), block, MV, m);
+            } else {
+                launch_k(L, sfk::advect_masked_kernel<T, NF>, dim3(nblocks), block, A, m);
+            }
         }, 1, 0, /*interior_reads_ghosts=*/true);  // a long back-trace may reach a ghost plane from any plane
         exchange<NF>(d);
     }
@@ -4037,6 +4140,7 @@ private:
     bool obst_mc_ = false;      // sf_set_obstacle_maccormack (SPEC §18): MacCormack under masked transport runs, masked
     bool obst_mg_ = false;      // sf_set_obstacle_multigrid (SPEC §16): a masked solve under the V-cycle runs, masked
     bool mg_codes_ok_ = false;  // the face codes of the coarse levels match the mask and the levels in force
+    bool obstv_on_ = false;   // sf_set_obstacle_velocity (SPEC §19): the solid velocity of the OBSTV slots is in force
     bool obst_on_ = false;    // sf_set_obstacles (SPEC §15): the face codes of OBST_SLOT are in force
     long long n_fluid_ = 0;   // fluid interior cells under them
     long long host_waits_total_ = 0;

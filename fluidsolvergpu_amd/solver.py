@@ -56,6 +56,7 @@ ABI_SYMBOLS = (
     "sf_set_obstacle_multigrid", "sf_obstacle_multigrid_get", "sf_precondition_masked",
     "sf_set_obstacle_transport", "sf_obstacle_transport_get", "sf_diffuse_masked", "sf_advect_masked",
     "sf_set_obstacle_maccormack", "sf_obstacle_maccormack_get", "sf_advect_maccormack_masked",
+    "sf_set_obstacle_velocity", "sf_obstacle_velocity_get",
     "sf_render", "sf_render_read", "sf_light",
     "sf_render_view", "sf_render_view_read", "sf_view_frame",
     "sf_render_camera", "sf_camera_passes_get", "sf_camera_frame",
@@ -176,6 +177,8 @@ lib.sf_diffuse_masked.argtypes = [_ctx, C.c_int, C.c_int, C.c_int, C.c_double]
 lib.sf_advect_masked.argtypes = [_ctx] + [C.c_int] * 6
 lib.sf_set_obstacle_maccormack.argtypes = [_ctx, C.c_int]
 lib.sf_obstacle_maccormack_get.argtypes = [_ctx, C.POINTER(C.c_int)]
+lib.sf_set_obstacle_velocity.argtypes = [_ctx, C.c_int, C.c_int, C.c_int]
+lib.sf_obstacle_velocity_get.argtypes = [_ctx, C.POINTER(C.c_int)]
 lib.sf_advect_maccormack_masked.argtypes = [_ctx] + [C.c_int] * 6
 lib.sf_render.argtypes = [_ctx, C.POINTER(SfRenderParams)]
 lib.sf_render_read.argtypes = [_ctx, C.c_void_p, C.c_void_p]
@@ -535,6 +538,36 @@ class FluidSolver:
     def advect_maccormack_masked(self, b, d, d0, u, v, w):
         """MacCormack advect under the mask (§18 advect_mc_masked): needs obstacles and set_obstacle_transport(True)."""
         self._ck(lib.sf_advect_maccormack_masked(self._h, int(b), _fid(d), _fid(d0), _fid(u), _fid(v), _fid(w)))
+
+    # -- moving solids (docs/SPEC.md §19) -----------------------------------------------------------------
+    def set_obstacle_velocity(self, us, vs, ws, slots=("user0", "user1", "user2")):
+        """The velocity of the solids, one field per axis, of which only the values in interior solid cells are used.
+        All three None switch it off; field names or ids take what those slots hold; (N+2)^3 arrays are uploaded into
+        `slots` first, over what they hold: the default slots are the ones bind_sources binds by default, so name
+        slots that are scratch at that moment (("u0", "v0", "w0") between steps) where sources are bound. The three
+        fields are copied by this call, so the slots are free again afterwards. While it is set (and obstacles are on) project_cg, diffuse_masked, advect_masked and vel_step follow
+        §19; vel_step then needs set_obstacle_transport(True) and a first-order velocity advection. Collective on
+        several ranks; synchronises."""
+        vals = (us, vs, ws)
+        if all(v is None for v in vals):
+            self._ck(lib.sf_set_obstacle_velocity(self._h, -1, -1, -1))
+            return
+        ids = []
+        for v, slot in zip(vals, slots):
+            if v is None:
+                ids.append(-1)  # a mix of None and fields: the library refuses it
+            elif isinstance(v, (str, int)):
+                ids.append(_fid(v))
+            else:
+                self.upload(slot, v)
+                ids.append(_fid(slot))
+        self._ck(lib.sf_set_obstacle_velocity(self._h, *ids))
+
+    def obstacle_velocity(self):
+        """True while a solid velocity is set (sf_obstacle_velocity_get)."""
+        on = C.c_int(0)
+        self._ck(lib.sf_obstacle_velocity_get(self._h, C.byref(on)))
+        return bool(on.value)
 
     # -- volume rendering and light marching (docs/SPEC.md §12) ---------------------------------
     def render(self, dens="dens", emit=None, axis=2, from_high=0, sigma=1.0):

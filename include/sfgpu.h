@@ -416,6 +416,29 @@ int sf_set_obstacle_maccormack(sf_ctx* ctx, int on);
 int sf_obstacle_maccormack_get(const sf_ctx* ctx, int* on);
 int sf_advect_maccormack_masked(sf_ctx* ctx, int b, int d, int d0, int u, int v, int w);
 
+/* Moving solids (docs/SPEC.md §19): obstacles with a velocity of their own, three fields us, vs, ws of which only the
+ * values in interior solid cells are ever used (selects on loaded values: a NaN parked anywhere else reaches nothing).
+ * On the axis of a velocity component the ghost value at a closed face becomes (xs[nb] + xs[nb]) - x[c], whose mean
+ * with the cell is the solid's velocity, in the divergence of the projection and in the masked sweep; the tangential
+ * axes stay free slip and b = 0 fields are §17's. The gradient subtraction writes us, vs, ws into solid cells instead
+ * of +0, and the masked advect of b = 1, 2, 3 reads the solid's velocity at a solid SAMPLE cell instead of 0. The
+ * operator A, CG, the preconditioners and §16 are unchanged. With us = vs = ws = +0 every output compares equal to
+ * §15 / §17 (a -0 may come out as +0).
+ *   sf_set_obstacle_velocity(su, sv, sw): the three slots are copied whole into internal fields (three more fields,
+ *       allocated by the first call; ghost planes exchanged), so later writes to the slots change nothing until the
+ *       next call. -1, -1, -1 switches it off and restores every launch of §15 - §18. A mix of -1 and slots, a slot
+ *       out of range or two equal slots: SF_ERR_INVALID, and the setting is unchanged. Valid in any order with
+ *       sf_set_obstacles and the other obstacle settings. While it is set and obstacles are on, sf_project_cg,
+ *       sf_diffuse_masked, sf_advect_masked and sf_vel_step follow §19; sf_dens_step is §17's with the same launches.
+ *       sf_vel_step is then SF_ERR_INVALID with a message without sf_set_obstacle_transport(1), and with a velocity
+ *       advected by SF_ADVECT_MACCORMACK (whatever sf_set_obstacle_maccormack says; a MacCormack density is
+ *       unaffected), and sf_advect_maccormack_masked with b = 1, 2, 3 is SF_ERR_INVALID with a message (b = 0 is
+ *       §18's, unchanged): there is no MacCormack form under a solid velocity. Same bits for every decomposition and transport. Collective; it synchronises and drops the graphs
+ *       SF_GRAPH has cached.
+ *   sf_obstacle_velocity_get: 1 while a solid velocity is set, 0 otherwise. */
+int sf_set_obstacle_velocity(sf_ctx* ctx, int su, int sv, int sw);
+int sf_obstacle_velocity_get(const sf_ctx* ctx, int* on);
+
 /* Axis-aligned volume rendering and light marching of docs/SPEC.md §12: an N x N image of the smoke from data that
  * already sits in device memory, instead of a (N+2)^3 frame over the bus. One ray per pixel runs along axis (0: i,
  * 1: j, 2: k) through the N interior cells of a line, entering at index 1 (from_high = 0) or N (from_high = 1). A cell
